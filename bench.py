@@ -10,6 +10,12 @@ synthetic masks") per GPU: forward, CE(weight [1,4], label_smoothing 1e-3) + Dic
 batch-stat BatchNorm are live.  Inputs are resident in HBM before the timed region.  For N > 1 the
 mini-batch is sharded 8 images per GPU (weak scaling) with bucketed RCCL gradient all-reduce
 overlapped with backward (lm_net_amd/ddp.py).  Rank 0 prints ONE JSON line.
+
+The timed steps start from one training state, and the last of them restores it first (parameters and AdamW moments: three
+device copies inside the timed region); every step runs in the default mode.  That state is reached before the warm-up by as many
+steps as precede the last timed one, run untimed in deterministic mode, so it is the same in every run, and what the last timed
+step computes differs between runs only by the rounding of one step (float atomics).  After many chained default-mode steps it
+would not: AdamW amplifies that rounding step by step.
 """
 import argparse
 import json
@@ -374,6 +380,7 @@ class Run:
         self.x, self.y = make_batch(B, size, size, dev, 1234 + rank)    # rank-offset data seed (train.py:42)
         self.crit = SegLoss(ce_weight=(1.0, 4.0), dice_weight=(1.0, 4.0), label_smoothing=0.001).to(dev)   # fused CE + Dice
         self.B, self.size, self.dtype = B, size, dtype
+        self.keep_out, self.out = False, None       # keep_out: the step keeps its logits in self.out (--dump-outputs)
 
     def step(self):
         out = self.model(self.x)
@@ -381,15 +388,49 @@ class Run:
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         self.opt.step()
+        if self.keep_out:
+            self.out = out.detach()
         return loss
 
-    def timed(self, steps, world, dev):
-        """EXACTLY `steps` steps between barrier + synchronize pairs; max over ranks."""
+    def snapshot(self):
+        """The training state the next step starts from: parameters, AdamW moments (device copies) and the AdamW step count."""
+        return [t.detach().clone() for t in (self.opt.flat_p, self.opt.exp_avg, self.opt.exp_avg_sq)], self.opt.step_count
+
+    def restore(self, snap):
+        """Back to a snapshot(): three device copies on the current stream (the parameters are views of flat_p)."""
+        for dst, src in zip((self.opt.flat_p, self.opt.exp_avg, self.opt.exp_avg_sq), snap[0]):
+            dst.copy_(src)
+        self.opt.step_count = snap[1]
+
+    def reproducible_start(self, n):
+        """`n` training steps from the freshly built model in deterministic mode (fixed-order reductions: the same state bit for bit
+        in every run), launched from the host -- call it before any pass is recorded as a plan or graph; returns the snapshot().
+        In the default mode float atomics add up in arrival order, and AdamW turns that rounding into parameter differences that
+        grow with every further step."""
+        saved = (self.net.use_plans, self.net.use_graphs)
+        self.net.use_plans = self.net.use_graphs = False
+        self.net.deterministic = True
+        try:
+            for _ in range(n):
+                self.step()
+        finally:
+            self.net.deterministic = False
+            self.net.use_plans, self.net.use_graphs = saved
+        torch.cuda.synchronize()
+        return self.snapshot()
+
+    def timed(self, steps, world, dev, start=None):
+        """EXACTLY `steps` steps between barrier + synchronize pairs; max over ranks.  start: a snapshot() that the first step starts
+        from and the last step restores first, so that the last step computes from the same inputs in every run."""
+        if start is not None:
+            self.restore(start)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
+            if start is not None and 0 < i == steps - 1:
+                self.restore(start)
             loss = self.step()
         torch.cuda.synchronize()
         if world > 1:
@@ -400,6 +441,35 @@ class Run:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         return dt, loss
+
+
+DUMP_LOGITS_MAX = 1 << 22      # logits elements written in full by --dump-outputs; a larger output is sampled (fixed seed)
+
+
+def dump_outputs(run, loss, out_dir):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files under `out_dir` (at most ~50 MB, ~40 MB at the default shape):
+    loss, logits (every element up to DUMP_LOGITS_MAX, else that many at sorted positions drawn with seed 0), and the model
+    after the step -- parameters, their gradients and the float buffers (BatchNorm running statistics), each flattened and
+    concatenated in named_parameters() / named_buffers() order.  Call it before any further step."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    net = run.net
+    logits = run.out.float().flatten()
+    if logits.numel() > DUMP_LOGITS_MAX:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(logits.numel(), generator=g)[:DUMP_LOGITS_MAX].sort().values
+        logits = logits[idx.to(logits.device)]
+    params = [p for _, p in net.named_parameters()]
+    arrays = {
+        "loss": loss.detach().float().reshape(1),
+        "logits": logits,
+        "parameters": torch.cat([p.detach().float().flatten() for p in params]),
+        "gradients": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().flatten() for p in params]),
+        "buffers": torch.cat([b.detach().float().flatten() for _, b in net.named_buffers() if b.is_floating_point()]),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    return sorted(name + ".npy" for name in arrays)
 
 
 def deterministic_check(dev, B, size, steps=5):
@@ -504,7 +574,13 @@ def main():
     ap.add_argument("--graphs", action="store_true",
                     help="replay the step as two hipGraphs (wins when the host is the bottleneck, e.g. batch 1; at batch 8 "
                          "the step is GPU-bound and host launches measured 7 %% faster than the replay)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, logits, parameters, gradients, "
+                         "BatchNorm buffers) as float32 DIR/<name>.npy; inputs and weights are seeded, so runs with the same "
+                         "arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (got %d)" % args.steps)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args.gpus, sys.argv[1:])            # never returns; nothing has touched the GPU yet
@@ -537,7 +613,11 @@ def main():
     net, step = run.net, run.step
     B, H, W = args.batch, args.size, args.size
 
-    for _ in range(max(args.warmup, 4 if (args.graphs or args.plans) else 0)):   # graph capture happens on the 3rd step of a shape
+    n_before = max(args.warmup, 4 if (args.graphs or args.plans) else 0) + 2    # warm-up + the two survey steps below
+    # the state the timed steps start from: as many steps as precede the last timed one in a run of consecutive steps, in
+    # deterministic mode, so what the timed path computes is the same in every run up to the rounding of one step
+    start = run.reproducible_start(n_before + args.steps - 1)
+    for _ in range(n_before - 2):   # graph capture happens on the 3rd step of a shape
         step()
     # ---- which kernel dominates?  Two extra untimed steps with the in-library timer on EVERY kernel launch (HIP events on
     # the launch stream, lm_net_amd/csrc/runtime.hip); graph replays run no host code, so this survey uses host launches
@@ -571,8 +651,13 @@ def main():
     head = [dominant] + [k for k in survey if "wgrad_reduce" in k and "wgrad" in dominant]
     if not net.use_graphs and not nolive:
         hip.prof_begin(flt(head))
-    dt, loss = run.timed(args.steps, world, dev)
+    run.keep_out = args.dump_outputs is not None and rank == 0
+    dt, loss = run.timed(args.steps, world, dev, start)
     live = hip.prof_end() if not net.use_graphs and not nolive else {}
+    if run.keep_out:                # before the untimed steps below change the model
+        dumped = dump_outputs(run, loss, args.dump_outputs)
+        print("bench.py: wrote %s to %s" % (", ".join(dumped), args.dump_outputs), file=sys.stderr)
+        run.keep_out, run.out = False, None
     if not net.use_graphs:
         rows = [k for k in watch if k.split("<")[0] not in set(h.split("<")[0] for h in head)] if not nolive else watch
         if rows:

@@ -4,9 +4,9 @@ A from-scratch restatement of the reference forward graph, written against the
 reference's semantics (file:line cited per class) with the SAME ``state_dict``
 key names and tensor shapes, so one weight set drives the reference, this
 oracle and the HIP product.  It is pinned against the real reference code by
-``tests/golden/*`` (made by ``tools/make_golden.py``, which imports
-/root/reference here) and, when /root/reference is present, directly by
-``tests/test_oracle_vs_reference.py``.  The neighborhood-attention core is
+``tests/golden/*`` (made by ``tools/make_golden*.py``, which import the
+reference tree), among them the reference's logits that
+``tests/test_oracle_vs_reference.py`` checks.  The neighborhood-attention core is
 external to the reference (natten, unpinned) -- see ``oracle/natten_ref.py``.
 
 Used by: tests/, __graft_entry__.smoke(), bench.py's cpu_baseline leg.  Never

@@ -1,8 +1,8 @@
 """Import the real reference ``core.LM_Net`` from /root/reference in THIS container.
 
-Used only by ``tools/make_golden.py`` (fixture generation) and by
-``tests/test_oracle_vs_reference.py`` (skipped when /root/reference is absent,
-i.e. on the GPU box).  Three third-party modules the reference imports are not
+Used only by the fixture generators ``tools/make_golden.py`` and
+``tools/make_golden_vsref.py``; the tests read the fixtures they write
+under ``tests/golden/``.  Three third-party modules the reference imports are not
 installable here (no network): ``timm``, ``torchvision.ops.*`` and ``natten``.
 They are injected as stubs:
 
