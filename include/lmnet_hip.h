@@ -459,6 +459,9 @@ int lmn_se_bwd_params(const float* dvec, const float* gsum, float inv_hw, const 
  * The reference constructs K = 3 (core/modules.py:509; the LDS-tiled kernels), its LM_Net signature also carries [3, 5]
  * (core/LM_Net.py:81-84): any other K runs the direct form, and so does K given NEGATIVE (-3: the direct form at K = 3,
  * which the tests compare with the tiled kernels).  scale = hd^-0.5.
+ * head_dim: any of 1..32.  1, 2, 4, 8, 16 run the channel-quad kernels above (C % 4 == 0, heads <= 16, K 3..13); every other head_dim
+ * (the wide LM_Net variants: filters[i] / 12 = 3, 5, 6, 7, 12, 24, ...) runs per-head kernels (csrc/na_gen.hip, K 3..9) that load the
+ * head's channels 4 / 2 / 1 at a time as hd % 4 / hd % 2 allow; env LMN_NA_GENERAL=1 sends every head_dim there (A/B runs).
  * ------------------------------------------------------------------------------------------ */
 int lmn_na_fwd(const void* qkv, const float* rpb, void* out, int B, int H, int W, int heads, int hd, int K, float scale,
                int act_dtype, lmn_stream_t stream);
@@ -470,7 +473,8 @@ int lmn_na_bwd(const void* qkv, const float* rpb, const void* dout, void* dqkv, 
 
 /* ------------------------------------------------------------------------------------------
  * Dense global attention of GFT (core/modules.py:267-279): qkv [B,N,3C] (channel = which*C +
- * head*hd + d), out [B,N,C].  Any N (streamed over key tiles; exercised up to 16384 tokens = 2048x2048 inputs), hd <= 32.
+ * head*hd + d), out [B,N,C].  Any N (streamed over key tiles; exercised up to 16384 tokens = 2048x2048 inputs), hd <= 128 (hd <= 32:
+ * matrix-core form; 33..128: VALU form at a padded width of 64 / 128 -- the wide LM_Net variants, sum(filters) / 12).
  * ------------------------------------------------------------------------------------------ */
 int lmn_gattn_fwd(const void* qkv, void* out, float* lse, int B, int N, int heads, int hd, float scale, int act_dtype,
                   lmn_stream_t stream);
@@ -479,7 +483,8 @@ int lmn_gattn_bwd(const void* qkv, const void* out, const void* dout, const floa
                   int B, int N, int heads, int hd, float scale, int act_dtype, lmn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * LayerNorm over the channel axis of NHWC rows (core/modules.py:330,333,508,511); eps = 1e-5.
+ * LayerNorm over the channel axis of NHWC rows (core/modules.py:330,333,508,511); eps = 1e-5.  C % 4 == 0, C <= 1536 (one wave per
+ * row above 512: the GFT norms of the wide LM_Net variants).
  * ------------------------------------------------------------------------------------------ */
 int lmn_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, int64_t rows, int C, int act_dtype,
                lmn_stream_t stream);

@@ -157,6 +157,38 @@ class _LMNetPlanDirectFunction(torch.autograd.Function):
         return None, None, None, None
 
 
+# Supported width envelope of the HIP path (README "Wider variants"): neighbourhood attention runs any head_dim 1..32
+# (csrc/na.hip, csrc/na_gen.hip), GFT attention head_dim <= 128 (csrc/gattn.hip), LayerNorm rows <= 1536 channels (csrc/rows.hip).
+NA_MAX_FILTER = NUM_HEADS * 32          # filters[0..3]: neighbourhood-attention head_dim <= 32
+GFT_MAX_WIDTH = NUM_HEADS * 128         # sum(filters): GFT head_dim <= 128, LayerNorm rows <= 1536
+NA_GENERAL_KERNEL_SIZES = (3, 5, 7)     # window sizes of the general-head_dim kernels (head_dim not in {1, 2, 4, 8, 16})
+NA_QUAD_HEAD_DIMS = (1, 2, 4, 8, 16)    # head dims of the channel-quad kernels (any odd window 3..13)
+
+
+def envelope_error(filters, na_kernel_size=3):
+    """None when the HIP path runs LM_Net(filters=..., na_kernel_size=...), else the message naming the limit it exceeds.
+    Host logic only (no device): LM_Net.forward raises ValueError with it before its first launch."""
+    f = [int(c) for c in filters]
+    if len(f) != 5:
+        return "filters must have 5 entries (got %d)" % len(f)
+    for i, c in enumerate(f):
+        if c <= 0 or c % NUM_HEADS:
+            return "filters[%d] = %d: every entry must be a positive multiple of %d (%d attention heads)" % (i, c, NUM_HEADS, NUM_HEADS)
+    for i, c in enumerate(f[:4]):
+        if c > NA_MAX_FILTER:
+            return ("filters[%d] = %d exceeds %d: neighbourhood-attention head_dim %d > 32 (the supported envelope is filters[0..3] <= %d)"
+                    % (i, c, NA_MAX_FILTER, c // NUM_HEADS, NA_MAX_FILTER))
+    if sum(f) > GFT_MAX_WIDTH:
+        return ("sum(filters) = %d exceeds %d: GFT attention head_dim %d > 128 and LayerNorm rows > %d channels"
+                % (sum(f), GFT_MAX_WIDTH, sum(f) // NUM_HEADS, GFT_MAX_WIDTH))
+    K = int(na_kernel_size)
+    general = [c // NUM_HEADS for c in f[:4] if c // NUM_HEADS not in NA_QUAD_HEAD_DIMS]
+    if general and K not in NA_GENERAL_KERNEL_SIZES:
+        return ("na_kernel_size = %d: neighbourhood attention at head_dim %s runs for kernel sizes %s only"
+                % (K, general, list(NA_GENERAL_KERNEL_SIZES)))
+    return None
+
+
 class LM_Net(nn.Module):
     def __init__(self, channel, n_classes=2, filters=[12, 24, 48, 96, 192], deep_supervision=False, na_kernel_size=3):
         # (na_kernel_size is not in the reference signature, core/LM_Net.py:6: its four NAT blocks are built with kernel_size 3,
@@ -237,6 +269,11 @@ class LM_Net(nn.Module):
             raise ValueError("expected input [B,%d,H,W], got %s" % (self.channel, tuple(x.shape)))
         if x.shape[2] % 16 or x.shape[3] % 16 or x.shape[2] < 32 or x.shape[3] < 32:
             raise ValueError("H and W must be multiples of 16 and >= 32 (got %dx%d)" % (x.shape[2], x.shape[3]))
+        env = self.__dict__.get("_envelope_err", False)
+        if env is False:                                      # (checked once per model: filters and window are fixed at construction)
+            env = self.__dict__["_envelope_err"] = envelope_error(self.filters, self.natt4.att1.kernel_size)
+        if env is not None:
+            raise ValueError("LM_Net(filters=%s) is outside the supported envelope: %s" % (self.filters, env))
         hip.load()
         # the step is as long as the kernel chain on the caller's stream: its conv / depthwise kernels run at a raised wave priority
         hip.set_priority_stream(torch.cuda.current_stream(x.device), self._engine.prio_main)

@@ -1,5 +1,6 @@
 // Dense multi-head self-attention of the GFT bottleneck (core/modules.py:267-279): N = (H/16)*(W/16)
-// tokens (484 at 352x352, 1024 at 512x512), 12 heads, head_dim = 31.  < 2 % of the step's FLOPs, so a
+// tokens (484 at 352x352, 1024 at 512x512), 12 heads, head_dim = 31 (up to 128 for the wide variants: the VALU form below at a
+// padded width of 64 / 128).  < 2 % of the step's FLOPs, so a
 // compact flash-style VALU kernel: four lanes per query row (each owns 8 of the 32 padded dims: q, the output
 // slice and the running max/sum in registers), keys/values streamed through LDS in 64-key chunks.  The backward
 // is the standard two-sweep form (query-owned dq; key-owned dk, dv) -- no atomics, deterministic.
@@ -10,8 +11,8 @@ namespace {
 constexpr int GA_D = 32;    // padded head_dim
 constexpr int GA_KC = 64;   // keys (or queries) per LDS chunk
 constexpr int GA_P = 4;     // lanes per row: each owns GA_D / GA_P = 8 consecutive dims
-constexpr int GA_DP = GA_D / GA_P;
 constexpr int GA_ROWS = 256 / GA_P;  // rows (queries or keys) per block
+constexpr int GA_DMAX = 128;  // widest head (VALU form at padded width 64 / 128 above GA_D)
 
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 
@@ -21,11 +22,21 @@ struct GaGeom {
   int prio;   // wave priority of the launch stream (lmn_set_priority_stream)
 };
 
-// copy rows [r0, r0+GA_KC) of one (b, head, which) slab into LDS as [GA_KC][GA_D] (zero padded)
-template <typename TA>
+// VALU form for a padded head width D = 32 (the default width's 31), 64 or 128 (wide LM_Net variants: sum(filters) / 12 up to 128):
+// P lanes per row (4, 8, 8), each owning DP = D / P consecutive dims; 256 / P rows per block; KC keys per LDS chunk (K and V: 32 KB
+// at D = 64 and 128)
+template <int D> struct GaCfg {
+  static constexpr int P = D <= 64 ? D / 8 : 8;   // (D = 128: 8 lanes of 16 dims -- half the cross-lane sums of 16 lanes of 8)
+  static constexpr int DP = D / P;
+  static constexpr int ROWS = 256 / P;
+  static constexpr int KC = D <= 64 ? 64 : 32;
+};
+
+// copy rows [r0, r0+KC) of one (b, head, which) slab into LDS as [KC][D] (zero padded)
+template <int D, int KC, typename TA>
 __device__ __forceinline__ void stage_rows(float* lds, const TA* base, int64_t row_stride, int r0, int N, int hd) {
-  for (int i = threadIdx.x; i < GA_KC * GA_D; i += blockDim.x) {
-    const int r = i / GA_D, d = i - r * GA_D;
+  for (int i = threadIdx.x; i < KC * D; i += blockDim.x) {
+    const int r = i / D, d = i - r * D;
     float v = 0.f;
     if (r0 + r < N && d < hd) v = ld1(base + (int64_t)(r0 + r) * row_stride + d);
     lds[i] = v;
@@ -38,55 +49,70 @@ __device__ __forceinline__ float quad_sum(float v) {
   v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));  // quad_perm [2,3,0,1]
   return v;
 }
-
-// this lane's 8-dim slice of LDS row r
-__device__ __forceinline__ void row_slice(const float* lds, int r, int part, float (&x)[GA_DP]) {
-  const f32x4g a = *reinterpret_cast<const f32x4g*>(lds + r * GA_D + part * GA_DP);
-  const f32x4g c = *reinterpret_cast<const f32x4g*>(lds + r * GA_D + part * GA_DP + 4);
-  x[0] = a[0]; x[1] = a[1]; x[2] = a[2]; x[3] = a[3];
-  x[4] = c[0]; x[5] = c[1]; x[6] = c[2]; x[7] = c[3];
+// sum over the P lanes of a row: the DPP quad form at P = 4, lane-pair shuffles for the wider rows
+template <int P>
+__device__ __forceinline__ float row_sum(float v) {
+  if constexpr (P == 4) return quad_sum(v);
+#pragma unroll
+  for (int m = 1; m < P; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
 }
 
-// The row (query or key) a thread works on is shared by 4 lanes that split head_dim: 4x the waves of the
+// this lane's DP-dim slice of LDS row r
+template <int D, int DP>
+__device__ __forceinline__ void row_slice(const float* lds, int r, int part, float (&x)[DP]) {
+  const f32x4g a = *reinterpret_cast<const f32x4g*>(lds + r * D + part * DP);
+  const f32x4g c = *reinterpret_cast<const f32x4g*>(lds + r * D + part * DP + 4);
+  x[0] = a[0]; x[1] = a[1]; x[2] = a[2]; x[3] = a[3];
+  x[4] = c[0]; x[5] = c[1]; x[6] = c[2]; x[7] = c[3];
+#pragma unroll
+  for (int k = 8; k < DP; k += 4) {
+    const f32x4g e = *reinterpret_cast<const f32x4g*>(lds + r * D + part * DP + k);
+    x[k] = e[0]; x[k + 1] = e[1]; x[k + 2] = e[2]; x[k + 3] = e[3];
+  }
+}
+
+// The row (query or key) a thread works on is shared by P lanes (4 at D = 32) that split head_dim: 4x the waves of the
 // one-thread-per-row form (484 tokens x 12 heads x 8 images is only 726 waves of rows -- less than one per SIMD),
 // a quarter of the registers, and the dot products close with two DPP adds.
-template <typename TA>
+template <int D, typename TA>
 __global__ __launch_bounds__(256) void gattn_fwd_kernel(const TA* __restrict__ qkv, TA* __restrict__ out,
                                                         float* __restrict__ lse, const GaGeom g) {
-  __shared__ __attribute__((aligned(16))) float Ks[GA_KC * GA_D], Vs[GA_KC * GA_D];
+  constexpr int P = GaCfg<D>::P, DP = GaCfg<D>::DP, ROWS = GaCfg<D>::ROWS, KC = GaCfg<D>::KC;
+  __shared__ __attribute__((aligned(16))) float Ks[KC * D], Vs[KC * D];
   const int h = blockIdx.y, b = blockIdx.z;
-  const int part = threadIdx.x & (GA_P - 1);
-  const int i = blockIdx.x * GA_ROWS + (threadIdx.x >> 2);
+  const int part = threadIdx.x & (P - 1);
+  const int i = blockIdx.x * ROWS + (threadIdx.x / P);
   const bool ok = i < g.N;
   const int64_t rs = 3 * g.C;
   const TA* qb = qkv + (int64_t)b * g.N * rs + h * g.hd;
-  float q[GA_DP], o[GA_DP];
+  float q[DP], o[DP];
 #pragma unroll
-  for (int d = 0; d < GA_DP; ++d) {
-    const int dd = part * GA_DP + d;
+  for (int d = 0; d < DP; ++d) {
+    const int dd = part * DP + d;
     q[d] = (ok && dd < g.hd) ? ld1(qb + (int64_t)i * rs + dd) * g.scale : 0.f;
     o[d] = 0.f;
   }
   float m = -3.0e38f, l = 0.f;
-  for (int k0 = 0; k0 < g.N; k0 += GA_KC) {
+  for (int k0 = 0; k0 < g.N; k0 += KC) {
     __syncthreads();
-    stage_rows(Ks, qb + g.C, rs, k0, g.N, g.hd);
-    stage_rows(Vs, qb + 2 * g.C, rs, k0, g.N, g.hd);
+    stage_rows<D, KC>(Ks, qb + g.C, rs, k0, g.N, g.hd);
+    stage_rows<D, KC>(Vs, qb + 2 * g.C, rs, k0, g.N, g.hd);
     __syncthreads();
-    const int kn = g.N - k0 < GA_KC ? g.N - k0 : GA_KC;
+    const int kn = g.N - k0 < KC ? g.N - k0 : KC;
     for (int j = 0; j < kn; ++j) {
-      float kk[GA_DP], vv[GA_DP];
-      row_slice(Ks, j, part, kk);
-      row_slice(Vs, j, part, vv);
+      float kk[DP], vv[DP];
+      row_slice<D, DP>(Ks, j, part, kk);
+      row_slice<D, DP>(Vs, j, part, vv);
       float s = 0.f;
 #pragma unroll
-      for (int d = 0; d < GA_DP; ++d) s += q[d] * kk[d];
-      s = quad_sum(s);
+      for (int d = 0; d < DP; ++d) s += q[d] * kk[d];
+      s = row_sum<P>(s);
       const float mn = fmaxf(m, s);
       const float corr = __expf(m - mn), pj = __expf(s - mn);
       l = l * corr + pj;
 #pragma unroll
-      for (int d = 0; d < GA_DP; ++d) o[d] = o[d] * corr + pj * vv[d];
+      for (int d = 0; d < DP; ++d) o[d] = o[d] * corr + pj * vv[d];
       m = mn;
     }
   }
@@ -94,8 +120,8 @@ __global__ __launch_bounds__(256) void gattn_fwd_kernel(const TA* __restrict__ q
     const float inv = 1.0f / l;
     TA* ob = out + ((int64_t)b * g.N + i) * g.C + h * g.hd;
 #pragma unroll
-    for (int d = 0; d < GA_DP; ++d)
-      if (part * GA_DP + d < g.hd) st1(ob + part * GA_DP + d, o[d] * inv);
+    for (int d = 0; d < DP; ++d)
+      if (part * DP + d < g.hd) st1(ob + part * DP + d, o[d] * inv);
     if (part == 0) lse[((int64_t)b * g.heads + h) * g.N + i] = m + __logf(l);
   }
 }
@@ -403,23 +429,24 @@ __global__ __launch_bounds__(256) void gattn_bwd_kv_mfma_kernel(const TA* __rest
 }
 
 // sweep A: query-owned.  delta_i = do_i . o_i ;  dq_i = scale * sum_j p_ij (dp_ij - delta_i) k_j
-template <typename TA>
+template <int D, typename TA>
 __global__ __launch_bounds__(256) void gattn_bwd_q_kernel(const TA* __restrict__ qkv, const TA* __restrict__ out,
                                                           const TA* __restrict__ dout, const float* __restrict__ lse,
                                                           TA* __restrict__ dqkv, float* __restrict__ delta,
                                                           const GaGeom g) {
-  __shared__ __attribute__((aligned(16))) float Ks[GA_KC * GA_D], Vs[GA_KC * GA_D];
+  constexpr int P = GaCfg<D>::P, DP = GaCfg<D>::DP, ROWS = GaCfg<D>::ROWS, KC = GaCfg<D>::KC;
+  __shared__ __attribute__((aligned(16))) float Ks[KC * D], Vs[KC * D];
   const int h = blockIdx.y, b = blockIdx.z;
-  const int part = threadIdx.x & (GA_P - 1);
-  const int i = blockIdx.x * GA_ROWS + (threadIdx.x >> 2);
+  const int part = threadIdx.x & (P - 1);
+  const int i = blockIdx.x * ROWS + (threadIdx.x / P);
   const bool ok = i < g.N;
   const int64_t rs = 3 * g.C;
   const TA* qb = qkv + (int64_t)b * g.N * rs + h * g.hd;
-  float q[GA_DP], dO[GA_DP], dq[GA_DP];
+  float q[DP], dO[DP], dq[DP];
   float dl = 0.f;
 #pragma unroll
-  for (int d = 0; d < GA_DP; ++d) {
-    const int dd = part * GA_DP + d;
+  for (int d = 0; d < DP; ++d) {
+    const int dd = part * DP + d;
     const bool dk = ok && dd < g.hd;
     q[d] = dk ? ld1(qb + (int64_t)i * rs + dd) * g.scale : 0.f;
     dO[d] = dk ? ld1(dout + ((int64_t)b * g.N + i) * g.C + h * g.hd + dd) : 0.f;
@@ -427,90 +454,91 @@ __global__ __launch_bounds__(256) void gattn_bwd_q_kernel(const TA* __restrict__
     dl += dO[d] * ov;
     dq[d] = 0.f;
   }
-  dl = quad_sum(dl);
+  dl = row_sum<P>(dl);
   const float L = ok ? lse[((int64_t)b * g.heads + h) * g.N + i] : 0.f;
-  for (int k0 = 0; k0 < g.N; k0 += GA_KC) {
+  for (int k0 = 0; k0 < g.N; k0 += KC) {
     __syncthreads();
-    stage_rows(Ks, qb + g.C, rs, k0, g.N, g.hd);
-    stage_rows(Vs, qb + 2 * g.C, rs, k0, g.N, g.hd);
+    stage_rows<D, KC>(Ks, qb + g.C, rs, k0, g.N, g.hd);
+    stage_rows<D, KC>(Vs, qb + 2 * g.C, rs, k0, g.N, g.hd);
     __syncthreads();
-    const int kn = g.N - k0 < GA_KC ? g.N - k0 : GA_KC;
+    const int kn = g.N - k0 < KC ? g.N - k0 : KC;
     for (int j = 0; j < kn; ++j) {
-      float kk[GA_DP], vv[GA_DP];
-      row_slice(Ks, j, part, kk);
-      row_slice(Vs, j, part, vv);
+      float kk[DP], vv[DP];
+      row_slice<D, DP>(Ks, j, part, kk);
+      row_slice<D, DP>(Vs, j, part, vv);
       float s = 0.f, dp = 0.f;
 #pragma unroll
-      for (int d = 0; d < GA_DP; ++d) {
+      for (int d = 0; d < DP; ++d) {
         s += q[d] * kk[d];
         dp += dO[d] * vv[d];
       }
-      s = quad_sum(s);
-      dp = quad_sum(dp);
+      s = row_sum<P>(s);
+      dp = row_sum<P>(dp);
       const float ds = __expf(s - L) * (dp - dl);
 #pragma unroll
-      for (int d = 0; d < GA_DP; ++d) dq[d] += ds * kk[d];
+      for (int d = 0; d < DP; ++d) dq[d] += ds * kk[d];
     }
   }
   if (ok) {
     TA* dqb = dqkv + ((int64_t)b * g.N + i) * rs + h * g.hd;
 #pragma unroll
-    for (int d = 0; d < GA_DP; ++d)
-      if (part * GA_DP + d < g.hd) st1(dqb + part * GA_DP + d, dq[d] * g.scale);
+    for (int d = 0; d < DP; ++d)
+      if (part * DP + d < g.hd) st1(dqb + part * DP + d, dq[d] * g.scale);
     if (part == 0) delta[((int64_t)b * g.heads + h) * g.N + i] = dl;
   }
 }
 
 // sweep B: key-owned.  dv_j = sum_i p_ij do_i ;  dk_j = scale * sum_i p_ij (dp_ij - delta_i) q_i
-template <typename TA>
+template <int D, typename TA>
 __global__ __launch_bounds__(256) void gattn_bwd_kv_kernel(const TA* __restrict__ qkv, const TA* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            TA* __restrict__ dqkv, const GaGeom g) {
-  __shared__ __attribute__((aligned(16))) float Qs[GA_KC * GA_D], Ds[GA_KC * GA_D];
-  __shared__ float Ls[GA_KC], Dl[GA_KC];
+  constexpr int P = GaCfg<D>::P, DP = GaCfg<D>::DP, ROWS = GaCfg<D>::ROWS, KC = GaCfg<D>::KC;
+  __shared__ __attribute__((aligned(16))) float Qs[KC * D], Ds[KC * D];
+  __shared__ float Ls[KC], Dl[KC];
   const int h = blockIdx.y, b = blockIdx.z;
-  const int part = threadIdx.x & (GA_P - 1);
-  const int j = blockIdx.x * GA_ROWS + (threadIdx.x >> 2);
+  const int part = threadIdx.x & (P - 1);
+  const int j = blockIdx.x * ROWS + (threadIdx.x / P);
   const bool ok = j < g.N;
   const int64_t rs = 3 * g.C;
   const TA* qb = qkv + (int64_t)b * g.N * rs + h * g.hd;
-  float k[GA_DP], v[GA_DP], dk[GA_DP], dv[GA_DP];
+  float k[DP], v[DP], dk[DP], dv[DP];
 #pragma unroll
-  for (int d = 0; d < GA_DP; ++d) {
-    const int dd = part * GA_DP + d;
+  for (int d = 0; d < DP; ++d) {
+    const int dd = part * DP + d;
     const bool dok = ok && dd < g.hd;
     k[d] = dok ? ld1(qb + (int64_t)j * rs + g.C + dd) : 0.f;
     v[d] = dok ? ld1(qb + (int64_t)j * rs + 2 * g.C + dd) : 0.f;
     dk[d] = dv[d] = 0.f;
   }
   const TA* dob = dout + (int64_t)b * g.N * g.C + h * g.hd;
-  for (int i0 = 0; i0 < g.N; i0 += GA_KC) {
+  for (int i0 = 0; i0 < g.N; i0 += KC) {
     __syncthreads();
-    stage_rows(Qs, qb, rs, i0, g.N, g.hd);
-    stage_rows(Ds, dob, g.C, i0, g.N, g.hd);
-    for (int t = threadIdx.x; t < GA_KC; t += 256) {
+    stage_rows<D, KC>(Qs, qb, rs, i0, g.N, g.hd);
+    stage_rows<D, KC>(Ds, dob, g.C, i0, g.N, g.hd);
+    for (int t = threadIdx.x; t < KC; t += 256) {
       const bool in = i0 + t < g.N;
       Ls[t] = in ? lse[((int64_t)b * g.heads + h) * g.N + i0 + t] : 0.f;
       Dl[t] = in ? delta[((int64_t)b * g.heads + h) * g.N + i0 + t] : 0.f;
     }
     __syncthreads();
-    const int qn = g.N - i0 < GA_KC ? g.N - i0 : GA_KC;
+    const int qn = g.N - i0 < KC ? g.N - i0 : KC;
     for (int i = 0; i < qn; ++i) {
-      float qq[GA_DP], dd[GA_DP];
-      row_slice(Qs, i, part, qq);
-      row_slice(Ds, i, part, dd);
+      float qq[DP], dd[DP];
+      row_slice<D, DP>(Qs, i, part, qq);
+      row_slice<D, DP>(Ds, i, part, dd);
       float s = 0.f, dp = 0.f;
 #pragma unroll
-      for (int d = 0; d < GA_DP; ++d) {
+      for (int d = 0; d < DP; ++d) {
         s += qq[d] * k[d];
         dp += dd[d] * v[d];
       }
-      s = quad_sum(s);
-      dp = quad_sum(dp);
+      s = row_sum<P>(s);
+      dp = row_sum<P>(dp);
       const float pij = __expf(s * g.scale - Ls[i]);
       const float ds = pij * (dp - Dl[i]);
 #pragma unroll
-      for (int d = 0; d < GA_DP; ++d) {
+      for (int d = 0; d < DP; ++d) {
         dv[d] += pij * dd[d];
         dk[d] += ds * qq[d];
       }
@@ -519,10 +547,10 @@ __global__ __launch_bounds__(256) void gattn_bwd_kv_kernel(const TA* __restrict_
   if (ok) {
     TA* db = dqkv + ((int64_t)b * g.N + j) * rs + h * g.hd;
 #pragma unroll
-    for (int d = 0; d < GA_DP; ++d)
-      if (part * GA_DP + d < g.hd) {
-        st1(db + g.C + part * GA_DP + d, dk[d] * g.scale);
-        st1(db + 2 * g.C + part * GA_DP + d, dv[d]);
+    for (int d = 0; d < DP; ++d)
+      if (part * DP + d < g.hd) {
+        st1(db + g.C + part * DP + d, dk[d] * g.scale);
+        st1(db + 2 * g.C + part * DP + d, dv[d]);
       }
   }
 }
@@ -536,15 +564,21 @@ int lmn_gattn_fwd(const void* qkv, void* out, float* lse, int B, int N, int head
   LMN_REC(lmn_gattn_fwd(qkv, out, lse, B, N, heads, hd, scale, act_dtype, stream));
   LMN_REQUIRE_DT(act_dtype, "gattn_fwd");
   LMN_REQUIRE(qkv && out && lse && B > 0 && N > 0 && heads > 0, "gattn_fwd: bad argument");
-  LMN_REQUIRE(hd >= 1 && hd <= GA_D, "gattn_fwd: head_dim %d > %d", hd, GA_D);
+  LMN_REQUIRE(hd >= 1 && hd <= GA_DMAX, "gattn_fwd: head_dim %d > %d", hd, GA_DMAX);
   GaGeom g{B, N, heads, hd, heads * hd, scale, lmn_prio_level((hipStream_t)stream)};
+  if (hd > GA_D) {   // wide variants: the VALU form at padded width 64 / 128
+#define LMN_GAW(DV) LMN_LAUNCH((gattn_fwd_kernel<DV, T>), dim3(lmn_cdiv(N, GaCfg<DV>::ROWS), heads, B), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (T*)out, lse, g)
+    LMN_ACT_DISPATCH(act_dtype, if (hd <= 64) LMN_GAW(64); else LMN_GAW(128));
+#undef LMN_GAW
+    return lmn_launch_status("gattn_fwd");
+  }
   static int mf = -1;
   if (mf < 0) { const char* e = getenv("LMN_GATTN_MFMA"); mf = e ? atoi(e) : 1; }
   if (mf) {  // MFMA form (LMN_GATTN_MFMA=0: the VALU form, A/B runs)
     LMN_ACT_DISPATCH(act_dtype, LMN_LAUNCH((gattn_fwd_mfma_kernel<T>), dim3(lmn_cdiv(N, 64), heads, B), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (T*)out, lse, g));
     return lmn_launch_status("gattn_fwd");
   }
-  LMN_ACT_DISPATCH(act_dtype, LMN_LAUNCH((gattn_fwd_kernel<T>), dim3(lmn_cdiv(N, GA_ROWS), heads, B), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (T*)out, lse, g));
+  LMN_ACT_DISPATCH(act_dtype, LMN_LAUNCH((gattn_fwd_kernel<GA_D, T>), dim3(lmn_cdiv(N, GA_ROWS), heads, B), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (T*)out, lse, g));
   return lmn_launch_status("gattn_fwd");
 }
 
@@ -553,8 +587,19 @@ int lmn_gattn_bwd(const void* qkv, const void* out, const void* dout, const floa
   LMN_REC(lmn_gattn_bwd(qkv, out, dout, lse, dqkv, delta, B, N, heads, hd, scale, act_dtype, stream));
   LMN_REQUIRE_DT(act_dtype, "gattn_bwd");
   LMN_REQUIRE(qkv && out && dout && lse && dqkv && delta && B > 0 && N > 0 && heads > 0, "gattn_bwd: bad argument");
-  LMN_REQUIRE(hd >= 1 && hd <= GA_D, "gattn_bwd: head_dim %d > %d", hd, GA_D);
+  LMN_REQUIRE(hd >= 1 && hd <= GA_DMAX, "gattn_bwd: head_dim %d > %d", hd, GA_DMAX);
   GaGeom g{B, N, heads, hd, heads * hd, scale, lmn_prio_level((hipStream_t)stream)};
+  if (hd > GA_D) {
+#define LMN_GAW(DV)                                                                                                             \
+  do {                                                                                                                          \
+    const dim3 wgrid(lmn_cdiv(N, GaCfg<DV>::ROWS), heads, B);                                                                   \
+    LMN_LAUNCH((gattn_bwd_q_kernel<DV, T>), wgrid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (const T*)out, (const T*)dout, lse, (T*)dqkv, delta, g); \
+    LMN_LAUNCH((gattn_bwd_kv_kernel<DV, T>), wgrid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (const T*)dout, lse, delta, (T*)dqkv, g); \
+  } while (0)
+    LMN_ACT_DISPATCH(act_dtype, if (hd <= 64) LMN_GAW(64); else LMN_GAW(128));
+#undef LMN_GAW
+    return lmn_launch_status("gattn_bwd");
+  }
   static int mf = -1;
   if (mf < 0) { const char* e = getenv("LMN_GATTN_MFMA"); mf = e ? atoi(e) : 1; }
   if (mf) {
@@ -564,8 +609,8 @@ int lmn_gattn_bwd(const void* qkv, const void* out, const void* dout, const floa
     return lmn_launch_status("gattn_bwd");
   }
   const dim3 grid(lmn_cdiv(N, GA_ROWS), heads, B);
-  LMN_ACT_DISPATCH(act_dtype, LMN_LAUNCH((gattn_bwd_q_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (const T*)out, (const T*)dout, lse, (T*)dqkv, delta, g);
-                   LMN_LAUNCH((gattn_bwd_kv_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (const T*)dout, lse, delta, (T*)dqkv, g));
+  LMN_ACT_DISPATCH(act_dtype, LMN_LAUNCH((gattn_bwd_q_kernel<GA_D, T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (const T*)out, (const T*)dout, lse, (T*)dqkv, delta, g);
+                   LMN_LAUNCH((gattn_bwd_kv_kernel<GA_D, T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (const T*)dout, lse, delta, (T*)dqkv, g));
   return lmn_launch_status("gattn_bwd");
 }
 

@@ -9,6 +9,7 @@
 // one lane-pair shuffle for hd = 8).  The 9x re-use of k/v between neighbouring queries is served by
 // L1/L2: HBM traffic stays at the algorithmic 4*C*4 B per pixel.
 #include "common.h"
+#include "na_gen.h"
 
 namespace {
 
@@ -1227,6 +1228,9 @@ int lmn_na_fwd(const void* qkv, const float* rpb, void* out, int B, int H, int W
   LMN_REQUIRE(qkv && rpb && out, "na_fwd: null pointer");
   const bool gen = K < 0;   // -K: the direct (run-time K) form, also for K = 3 (tests)
   if (gen) K = -K;
+  // head dims without a channel-quad kernel below (and every head dim under LMN_NA_GENERAL=1): the per-head kernels of na_gen.hip
+  if (lmn_na_force_general() || !(hd == 1 || hd == 2 || hd == 4 || hd == 8 || hd == 16))
+    return lmn_na_any_fwd(qkv, rpb, out, B, H, W, heads, hd, K, scale, act_dtype, (hipStream_t)stream);
   LMN_REQUIRE(K >= 3 && K <= 13 && (K & 1), "na_fwd: window %d (odd, 3..13)", K);
   LMN_REQUIRE(B > 0 && H >= K && W >= K, "na_fwd: feature map %dx%d smaller than the %dx%d window", H, W, K, K);
   LMN_REQUIRE(hd == 1 || hd == 2 || hd == 4 || hd == 8 || hd == 16, "na_fwd: head_dim %d not in {1,2,4,8,16}", hd);
@@ -1281,6 +1285,8 @@ int lmn_na_bwd(const void* qkv_, const float* rpb, const void* dout_, void* dqkv
   LMN_REQUIRE(qkv && rpb && dout && dqkv && drpb && stat, "na_bwd: null pointer");
   const bool gen = K < 0;
   if (gen) K = -K;
+  if (lmn_na_force_general() || !(hd == 1 || hd == 2 || hd == 4 || hd == 8 || hd == 16))
+    return lmn_na_any_bwd(qkv, rpb, dout, dqkv, drpb, stat, B, H, W, heads, hd, K, scale, act_dtype, (hipStream_t)stream);
   LMN_REQUIRE(K >= 3 && K <= 13 && (K & 1), "na_bwd: window %d (odd, 3..13)", K);
   LMN_REQUIRE(B > 0 && H >= K && W >= K, "na_bwd: feature map %dx%d smaller than the %dx%d window", H, W, K, K);
   LMN_REQUIRE(hd == 1 || hd == 2 || hd == 4 || hd == 8 || hd == 16, "na_bwd: head_dim %d not in {1,2,4,8,16}", hd);

@@ -143,6 +143,124 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ x, co
   }
 }
 
+// Rows wider than 512 channels (the GFT norms of the wide LM_Net variants: sum(filters) up to 1536): one wave per row, lane j owns
+// float4 slots j + 64 s, s < LN_WS.
+constexpr int LN_WS = 6;
+constexpr int LN_WIDE_MAXC = 64 * 4 * LN_WS;
+template <typename T>
+__global__ __launch_bounds__(256) void ln_fwd_wide_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, T* __restrict__ y, int64_t rows, int C) {
+  const int C4 = C >> 2, j = threadIdx.x & 63;
+  const float invC = 1.0f / (float)C;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (int64_t)gridDim.x * 4) {
+    const T* xr = x + row * C;
+    f32x4 v[LN_WS];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < LN_WS; ++k) {
+      v[k] = f32x4{0, 0, 0, 0};
+      if (j + 64 * k < C4) v[k] = ld4(xr + (j + 64 * k) * 4);
+      s += v[k][0] + v[k][1] + v[k][2] + v[k][3];
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    const float mean = s * invC;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < LN_WS; ++k)
+      if (j + 64 * k < C4)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q += (v[k][e] - mean) * (v[k][e] - mean);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) q += __shfl_xor(q, m, 64);
+    const float rstd = rsqrtf(q * invC + 1e-5f);
+#pragma unroll
+    for (int k = 0; k < LN_WS; ++k) {
+      const int c = (j + 64 * k) * 4;
+      if (c < C) st4(y + row * C + c, (v[k] - mean) * rstd * ld4(gamma + c) + ld4(beta + c));
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ln_bwd_wide_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
+                                                          const T* __restrict__ dy, const T* __restrict__ dres, T* __restrict__ dx,
+                                                          float* __restrict__ dgamma, float* __restrict__ dbeta, int64_t rows, int C,
+                                                          int det) {
+  extern __shared__ float red[];  // [4 waves][2][C]
+  const int C4 = C >> 2, j = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float invC = 1.0f / (float)C;
+  f32x4 ag[LN_WS], ab[LN_WS];
+#pragma unroll
+  for (int k = 0; k < LN_WS; ++k) ag[k] = ab[k] = f32x4{0, 0, 0, 0};
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wv; row < rows; row += (int64_t)gridDim.x * 4) {
+    f32x4 v[LN_WS], d[LN_WS];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < LN_WS; ++k) {
+      v[k] = d[k] = f32x4{0, 0, 0, 0};
+      if (j + 64 * k < C4) { v[k] = ld4(x + row * C + (j + 64 * k) * 4); d[k] = ld4(dy + row * C + (j + 64 * k) * 4); }
+      s += v[k][0] + v[k][1] + v[k][2] + v[k][3];
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    const float mean = s * invC;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < LN_WS; ++k)
+      if (j + 64 * k < C4)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q += (v[k][e] - mean) * (v[k][e] - mean);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) q += __shfl_xor(q, m, 64);
+    const float rstd = rsqrtf(q * invC + 1e-5f);
+    f32x4 h[LN_WS], t[LN_WS];
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < LN_WS; ++k) {
+      h[k] = (v[k] - mean) * rstd;
+      t[k] = f32x4{0, 0, 0, 0};
+      if (j + 64 * k < C4) {
+        t[k] = d[k] * ld4(gamma + (j + 64 * k) * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { m1 += t[k][e]; m2 += t[k][e] * h[k][e]; }
+      }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      m1 += __shfl_xor(m1, m, 64);
+      m2 += __shfl_xor(m2, m, 64);
+    }
+    m1 *= invC;
+    m2 *= invC;
+#pragma unroll
+    for (int k = 0; k < LN_WS; ++k) {
+      const int c = (j + 64 * k) * 4;
+      if (c < C) {
+        f32x4 o = (t[k] - m1 - h[k] * m2) * rstd;
+        if (dres) o += ld4(dres + row * C + c);
+        st4(dx + row * C + c, o);
+        ag[k] += d[k] * h[k];
+        ab[k] += d[k];
+      }
+    }
+  }
+  // dgamma / dbeta: the waves through plain LDS stores, then ONE global add per channel per block (as ln_bwd_kernel)
+  float* wred = red + wv * 2 * C;
+#pragma unroll
+  for (int k = 0; k < LN_WS; ++k) {
+    const int c = (j + 64 * k) * 4;
+    if (c < C)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { wred[c + e] = ag[k][e]; wred[C + c + e] = ab[k][e]; }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * C; i += 256) {
+    const float v = red[i] + red[2 * C + i] + red[4 * C + i] + red[6 * C + i];
+    lmn_red_add((i < C ? dgamma : dbeta - C) + (det ? (int64_t)blockIdx.x * C : 0) + i, v, det);
+  }
+}
+
 // ------------------------------------------------------------------------------------ BN(+act) tails
 template <typename T>
 __global__ __launch_bounds__(256) void bnact_fwd_kernel(const T* __restrict__ z, const float* __restrict__ a,
@@ -983,10 +1101,14 @@ int lmn_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, in
   LMN_REC(lmn_ln_fwd(x, gamma, beta, y, rows, C, act_dtype, stream));
   LMN_REQUIRE_DT(act_dtype, "ln_fwd");
   LMN_REQUIRE(x && gamma && beta && y && rows > 0, "ln_fwd: bad argument");
-  LMN_REQUIRE(C % 4 == 0 && C >= 4 && C <= 512, "ln_fwd: C=%d (need multiple of 4, <= 512)", C);
+  LMN_REQUIRE(C % 4 == 0 && C >= 4 && C <= LN_WIDE_MAXC, "ln_fwd: C=%d (need multiple of 4, <= %d)", C, LN_WIDE_MAXC);
+  hipStream_t st = (hipStream_t)stream;
+  if (C > 512) {   // one wave per row
+    LMN_ACT_DISPATCH(act_dtype, LMN_LAUNCH((ln_fwd_wide_kernel<T>), dim3(grid_for(rows, 4, 2048)), dim3(256), 0, st, (const T*)x, gamma, beta, (T*)y, rows, C));
+    return lmn_launch_status("ln_fwd");
+  }
   const int G = ln_group(C / 4);
   const int grid = grid_for(rows, 256 / G, 2048);
-  hipStream_t st = (hipStream_t)stream;
 #define LN_CASE(g) case g: LMN_LAUNCH((ln_fwd_kernel<g, T>), dim3(grid), dim3(256), 0, st, (const T*)x, gamma, beta, (T*)y, rows, C); break;
   LMN_ACT_DISPATCH(act_dtype, switch (G) { LN_CASE(1) LN_CASE(2) LN_CASE(4) LN_CASE(8) LN_CASE(16) LN_CASE(32) LN_CASE(64) });
 #undef LN_CASE
@@ -998,11 +1120,14 @@ int lmn_ln_bwd(const void* x, const float* gamma, const void* dy, const void* dr
   LMN_REC(lmn_ln_bwd(x, gamma, dy, dres, dx, dgamma, dbeta, rows, C, act_dtype, stream));
   LMN_REQUIRE_DT(act_dtype, "ln_bwd");
   LMN_REQUIRE(x && gamma && dy && dx && dgamma && dbeta && rows > 0, "ln_bwd: bad argument");
-  LMN_REQUIRE(C % 4 == 0 && C >= 4 && C <= 512, "ln_bwd: C=%d", C);
-  const int G = ln_group(C / 4);
+  LMN_REQUIRE(C % 4 == 0 && C >= 4 && C <= LN_WIDE_MAXC, "ln_bwd: C=%d (need multiple of 4, <= %d)", C, LN_WIDE_MAXC);
+  const bool wide = C > 512;   // one wave per row (ln_bwd_wide_kernel)
+  const int G = wide ? 64 : ln_group(C / 4);
   // every block ends with one global atomic per channel: ~40 ns per block on the same address, so the grid is kept to
   // what the tensor needs for bandwidth (level 0: 143 MB -> 1024 blocks; the coarser maps: 512)
-  const int grid = grid_for(rows, 256 / G, C <= 12 ? 1024 : 512);
+  // (wide rows: 2C atomics per block on the same 2C addresses dominate -- 512 blocks took 0.53 ms at 3872 x 1488, so 64 blocks of
+  //  one row per wave, ~15 rows each)
+  const int grid = grid_for(rows, 256 / G, wide ? 64 : C <= 12 ? 1024 : 512);
   hipStream_t st = (hipStream_t)stream;
   const size_t sh = 8 * C * sizeof(float);
   float *dgs = dgamma, *dbs = dbeta;
@@ -1013,7 +1138,8 @@ int lmn_ln_bwd(const void* x, const float* gamma, const void* dy, const void* dr
     dbs = dgs + (size_t)grid * C;
   }
 #define LN_CASE(g) case g: LMN_LAUNCH((ln_bwd_kernel<g, T>), dim3(grid), dim3(256), sh, st, (const T*)x, gamma, (const T*)dy, (const T*)dres, (T*)dx, dgs, dbs, rows, C, g_lmn_det); break;
-  LMN_ACT_DISPATCH(act_dtype, switch (G) { LN_CASE(1) LN_CASE(2) LN_CASE(4) LN_CASE(8) LN_CASE(16) LN_CASE(32) LN_CASE(64) });
+  if (wide) LMN_ACT_DISPATCH(act_dtype, LMN_LAUNCH((ln_bwd_wide_kernel<T>), dim3(grid), dim3(256), sh, st, (const T*)x, gamma, (const T*)dy, (const T*)dres, (T*)dx, dgs, dbs, rows, C, g_lmn_det));
+  else LMN_ACT_DISPATCH(act_dtype, switch (G) { LN_CASE(1) LN_CASE(2) LN_CASE(4) LN_CASE(8) LN_CASE(16) LN_CASE(32) LN_CASE(64) });
 #undef LN_CASE
   if (g_lmn_det) { lmn_det_sum(st, dgs, grid, C, dgamma); lmn_det_sum(st, dbs, grid, C, dbeta); }
   return lmn_launch_status("ln_bwd");
