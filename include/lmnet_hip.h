@@ -48,7 +48,7 @@ extern "C" {
 
 typedef void* lmn_stream_t; /* hipStream_t */
 
-#define LMN_ABI_VERSION 14
+#define LMN_ABI_VERSION 15
 /* arithmetic type of the matrix-core operands of a dense contraction (accumulators, epilogues, statistics: fp32) */
 #define LMN_F32 0  /* v_mfma_f32_16x16x4_f32: exact fp32 (k-ordered fma chain)                                  */
 #define LMN_BF16 1 /* v_mfma_f32_16x16x16_bf16: operands rounded to bf16 (RNE) when staged / packed -- the mixed- */
@@ -565,7 +565,9 @@ int lmn_nhwc_to_nchw(const void* x, float* y, int B, int C, int H, int W, int x_
  *        + DiceLoss(C)(logits, target, weight=w_dice)  -- softmax, one-hot, per class
  *          1 - (2*sum(p*t) + smooth)/(sum(p^2) + sum(t^2) + smooth), weighted, / C   (utils/loss.py:170-206),
  * as called in utils/train_eval_utils.py:141.  `sums` [3+3C] and `coef` [3+2C] are device workspaces the
- * backward re-uses; `loss` [1] stays on the device (no host sync).  C in {2,3,4,8}.
+ * backward re-uses; `loss` [1] stays on the device (no host sync).  C in [2, 64]: C in {2,3,4,8} run kernels templated on C,
+ * every other C the general-C kernels (logits staged in LDS per wave / per thread; no register arrays of size C).
+ * Labels must lie in [0, C).
  * lmn_segloss_bwd writes dlogits = gscale[0] * dloss/dlogits (gscale NULL = 1).                                 */
 int lmn_segloss_fwd(const float* logits, const int64_t* target, const float* w_ce, const float* w_dice, int B, int C,
                     int64_t HW, float label_smoothing, float smooth, float* sums, float* coef, float* loss,
@@ -573,7 +575,9 @@ int lmn_segloss_fwd(const float* logits, const int64_t* target, const float* w_c
 int lmn_segloss_bwd(const float* logits, const int64_t* target, const float* w_ce, const float* coef, const float* gscale,
                     int B, int C, int64_t HW, float* dlogits, lmn_stream_t stream);
 /* On-device confusion matrix (row N2): counts[t*C + p] += #pixels with label t and argmax(logits) = p.  Dice and IoU
- * follow as 2TP/(2TP+FP+FN), TP/(TP+FP+FN) (utils/train_eval_utils.py:78-95).  C in {2,3,4}.                   */
+ * follow as 2TP/(2TP+FP+FN), TP/(TP+FP+FN) (utils/train_eval_utils.py:78-95).  C in [2, 64]: C in {2,3,4} count in registers,
+ * 5..64 in a C x C int32 histogram per block in LDS.  Labels outside [0, C) are dropped (Evaluator._generate_matrix); ties of the
+ * argmax go to the first maximum (torch.argmax).  Float counts: exact up to 2^24 per cell and call.                 */
 int lmn_confusion(const float* logits, const int64_t* target, int B, int C, int64_t HW, float* counts, lmn_stream_t stream);
 /* Device-side input pipeline (row N4): uint8 HWC images [B,Hs,Ws,3] (channel order untouched, as cv2.imread hands it
  * over) and grayscale masks [B,Hs,Ws] -> normalised fp32 NCHW images [B,3,H,W] and int64 labels [B,H,W].
@@ -584,6 +588,12 @@ int lmn_confusion(const float* logits, const int64_t* target, int B, int C, int6
  * arguments, max_pixel_value 255).  Either images/out or masks/labels may be NULL.                                   */
 int lmn_preprocess_u8(const uint8_t* images, const uint8_t* masks, const uint8_t* flips, int B, int Hs, int Ws, int H,
                       int W, const double* mean, const double* std, float* out, int64_t* labels, lmn_stream_t stream);
+/* (ABI 15) lmn_preprocess_u8 for `channels` 1 (grayscale [B,Hs,Ws], out [B,1,H,W]) or 3 (as above), mean / std: HOST arrays of
+ * `channels` doubles.  mask_mode 0: cv2.threshold(127, 1) as lmn_preprocess_u8; 1: class ids passed through (INTER_NEAREST, no
+ * threshold), labels = the mask byte.                                                                               */
+int lmn_preprocess_u8_ex(const uint8_t* images, const uint8_t* masks, const uint8_t* flips, int B, int Hs, int Ws, int H, int W,
+                         int channels, int mask_mode, const double* mean, const double* std, float* out, int64_t* labels,
+                         lmn_stream_t stream);
 /* One AdamW step over flat buffers of n floats (n % 4 == 0): replaces torch.optim.AdamW.step() of
  * train.py:156 when parameters and gradients live in the flat layout of lm_net_amd.LM_Net.
  * bias_corr1 = 1 - beta1^t, bias_corr2 = 1 - beta2^t (t = step count, from the host). */

@@ -165,9 +165,17 @@ NA_GENERAL_KERNEL_SIZES = (3, 5, 7)     # window sizes of the general-head_dim k
 NA_QUAD_HEAD_DIMS = (1, 2, 4, 8, 16)    # head dims of the channel-quad kernels (any odd window 3..13)
 
 
-def envelope_error(filters, na_kernel_size=3):
-    """None when the HIP path runs LM_Net(filters=..., na_kernel_size=...), else the message naming the limit it exceeds.
-    Host logic only (no device): LM_Net.forward raises ValueError with it before its first launch."""
+MAX_CHANNEL = 16                        # input channels: the stem's padded input rows (multiple of 4)
+MAX_CLASSES = 64                        # classes: the head's padded output rows (multiple of 4)
+
+
+def envelope_error(filters, na_kernel_size=3, channel=3, n_classes=2):
+    """None when the HIP path runs LM_Net(channel, n_classes, filters=..., na_kernel_size=...), else the message naming the limit it
+    exceeds.  Host logic only (no device): LM_Net.forward raises ValueError with it before its first launch."""
+    if not 1 <= int(channel) <= MAX_CHANNEL:
+        return "channel = %d: the supported envelope is 1 <= channel <= %d input channels" % (int(channel), MAX_CHANNEL)
+    if not 1 <= int(n_classes) <= MAX_CLASSES:
+        return "n_classes = %d: the supported envelope is 1 <= n_classes <= %d classes" % (int(n_classes), MAX_CLASSES)
     f = [int(c) for c in filters]
     if len(f) != 5:
         return "filters must have 5 entries (got %d)" % len(f)
@@ -271,9 +279,10 @@ class LM_Net(nn.Module):
             raise ValueError("H and W must be multiples of 16 and >= 32 (got %dx%d)" % (x.shape[2], x.shape[3]))
         env = self.__dict__.get("_envelope_err", False)
         if env is False:                                      # (checked once per model: filters and window are fixed at construction)
-            env = self.__dict__["_envelope_err"] = envelope_error(self.filters, self.natt4.att1.kernel_size)
+            env = self.__dict__["_envelope_err"] = envelope_error(self.filters, self.natt4.att1.kernel_size, self.channel, self.n_classes)
         if env is not None:
-            raise ValueError("LM_Net(filters=%s) is outside the supported envelope: %s" % (self.filters, env))
+            raise ValueError("LM_Net(%d, %d, filters=%s) is outside the supported envelope: %s"
+                             % (self.channel, self.n_classes, self.filters, env))
         hip.load()
         # the step is as long as the kernel chain on the caller's stream: its conv / depthwise kernels run at a raised wave priority
         hip.set_priority_stream(torch.cuda.current_stream(x.device), self._engine.prio_main)

@@ -974,6 +974,147 @@ __global__ __launch_bounds__(256) void segloss_bwd_kernel(const float* __restric
   }
 }
 
+// General class count (C in [5, 64] outside {8}; the templates above keep C in {2, 3, 4, 8}).  Per-thread accumulators of all
+// 3 + 3C sums do not fit in registers at C = 64, so each wave stages the logits of its 64 pixels in LDS (tile [C][65], one global read
+// per logit) and works in two phases per tile:
+//   pixel phase  (lane = pixel): max, log-sum-exp, the three cross-entropy sums;
+//   class phase  (lane = g*C + c, G = 64/C pixel groups): the three per-class sums over the tile's pixels g, g+G, ...
+// Every partial is summed in a fixed order (per lane, then over g, over the wave's lanes by xor shuffles, over the 4 waves), so the
+// deterministic slot copies are bit-identical from run to run.
+constexpr int SG_STRIDE = 65;   // row stride of the staged tile: the class phase reads a row per lane, conflict-free at 65
+constexpr int SG_MAXC = 64;
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 1; m <= 32; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void segloss_sums_gen_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+                                                               const float* __restrict__ wce, int B, int C, int64_t hw,
+                                                               float* __restrict__ sums, int det) {
+  extern __shared__ float sg_tile[];                  // [4 waves][C][SG_STRIDE]
+  __shared__ float s_lse[4][64];
+  __shared__ int s_y[4][64];                          // label of the pixel, -2 past the end of the batch
+  __shared__ float s_part[4][3][64];
+  __shared__ float s_red[4][3 + 3 * SG_MAXC];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float* tile = sg_tile + wv * C * SG_STRIDE;
+  const int G = 64 / C, cc = lane % C, gg = lane / C;
+  float a_w = 0.f, a_nll = 0.f, a_sm = 0.f, a_pt = 0.f, a_pp = 0.f, a_t = 0.f;
+  const int64_t total = (int64_t)B * hw;
+  for (int64_t base = (int64_t)blockIdx.x * 256; base < total; base += (int64_t)gridDim.x * 256) {
+    const int64_t idx = base + threadIdx.x;
+    int y = -2;
+    float lse = 0.f;
+    if (idx < total) {
+      const int64_t b = idx / hw, i = idx - b * hw;
+      const float* lg = logits + b * C * hw + i;
+      float mx = -3.0e38f;
+#pragma unroll 8
+      for (int c = 0; c < C; ++c) {
+        const float z = lg[c * hw];
+        tile[c * SG_STRIDE + lane] = z;
+        mx = fmaxf(mx, z);
+      }
+      float den = 0.f;
+      for (int c = 0; c < C; ++c) den += __expf(tile[c * SG_STRIDE + lane] - mx);
+      lse = mx + __logf(den);
+      float sm = 0.f;
+      for (int c = 0; c < C; ++c) sm += wce[c] * (lse - tile[c * SG_STRIDE + lane]);   // sum_c w_c * (-log p_c)
+      a_sm += sm;
+      y = (int)target[idx];
+      if (y >= 0 && y < C) {
+        const float wy = wce[y];
+        a_w += wy;
+        a_nll += wy * (lse - tile[y * SG_STRIDE + lane]);
+      } else {
+        y = -1;
+      }
+    }
+    s_lse[wv][lane] = lse;
+    s_y[wv][lane] = y;
+    __syncthreads();
+    if (gg < G) {
+      for (int p = gg; p < 64; p += G) {
+        const int yp = s_y[wv][p];
+        if (yp == -2) break;                          // (pixels past the end are the tail of the tile)
+        const float pc = __expf(tile[cc * SG_STRIDE + p] - s_lse[wv][p]);
+        const float t = (yp == cc) ? 1.f : 0.f;
+        a_pt += pc * t;
+        a_pp += pc * pc;
+        a_t += t;
+      }
+    }
+    __syncthreads();
+  }
+  s_part[wv][0][lane] = a_pt;
+  s_part[wv][1][lane] = a_pp;
+  s_part[wv][2][lane] = a_t;
+  a_w = wave_sum(a_w);
+  a_nll = wave_sum(a_nll);
+  a_sm = wave_sum(a_sm);
+  if (lane == 0) { s_red[wv][0] = a_w; s_red[wv][1] = a_nll; s_red[wv][2] = a_sm; }
+  __syncthreads();
+  if (lane < C) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      float v = 0.f;
+      for (int g = 0; g < G; ++g) v += s_part[wv][k][g * C + lane];
+      s_red[wv][3 + k * C + lane] = v;
+    }
+  }
+  __syncthreads();
+  const int NS = 3 + 3 * C;
+  if (threadIdx.x < NS)   // (deterministic mode: sums addresses slot copies [blocks][NS])
+    lmn_red_add(sums + (det ? (int64_t)blockIdx.x * NS : 0) + threadIdx.x,
+                s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x], det);
+}
+
+// dlogits of the general-C loss: one pixel per thread, its C logits staged in LDS ([C][256], one global read each); three passes
+// over them (max / denominator, dice dot product gp = a_y p_y + sum_c b_c p_c^2, the write).
+__global__ __launch_bounds__(256) void segloss_bwd_gen_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+                                                              const float* __restrict__ wce, const float* __restrict__ coef,
+                                                              const float* __restrict__ gscale, int B, int C, int64_t hw,
+                                                              float* __restrict__ dlogits) {
+  extern __shared__ float sg_tile[];                  // [C][256]
+  float* z = sg_tile + threadIdx.x;
+  const float k_nll = coef[0], k_sm = coef[1], wsum = coef[2];
+  const float* a = coef + 3;
+  const float* bq = coef + 3 + C;
+  const float gs = gscale ? gscale[0] : 1.f;
+  const int64_t total = (int64_t)B * hw;
+  for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = idx / hw, i = idx - b * hw;
+    const float* lg = logits + b * C * hw + i;
+    float mx = -3.0e38f;
+#pragma unroll 8
+    for (int c = 0; c < C; ++c) {
+      const float v = lg[c * hw];
+      z[c * 256] = v;
+      mx = fmaxf(mx, v);
+    }
+    float den = 0.f;
+    for (int c = 0; c < C; ++c) den += __expf(z[c * 256] - mx);
+    const float r = 1.f / den;
+    const int y = (int)target[idx];
+    const bool in = y >= 0 && y < C;
+    const float wy = in ? wce[y] : 0.f;
+    float gp = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float p = __expf(z[c * 256] - mx) * r;
+      gp += (a[c] * ((c == y) ? 1.f : 0.f) + bq[c] * p) * p;
+    }
+    float* d = dlogits + b * C * hw + i;
+    for (int c = 0; c < C; ++c) {
+      const float p = __expf(z[c * 256] - mx) * r;
+      const float t = (c == y) ? 1.f : 0.f;
+      const float dce = k_nll * wy * (p - t) + k_sm * (p * wsum - wce[c]);
+      d[c * hw] = gs * (dce + p * (a[c] * t + bq[c] * p - gp));
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Input pipeline on the device: the validation transform of dataset/data_loading.py:203-206
 // (A.Resize -> A.Normalize -> ToTensorV2) plus the two flips of the training transform (:213-214), for a batch of
@@ -1034,6 +1175,42 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t* __res
   }
 }
 
+// lmn_preprocess_u8_ex: the same resample / normalise arithmetic for CH = 1 (grayscale [B,Hs,Ws]) or 3 channels, and a mask mode:
+// 0 = cv2.threshold(127, 1) as above, 1 = class ids passed through (nearest resize, no threshold).
+template <int CH>
+__global__ __launch_bounds__(256) void preprocess_u8_ex_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ mask,
+                                                               const uint8_t* __restrict__ flips, float* __restrict__ out,
+                                                               int64_t* __restrict__ labels, const PrepGeom g, int mask_mode) {
+  const int64_t n = (int64_t)g.B * g.H * g.W;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int x = (int)(i % g.W), y = (int)((i / g.W) % g.H), b = (int)(i / ((int64_t)g.W * g.H));
+    const int fl = flips ? flips[b] : 0;
+    const int rx = (fl & 1) ? g.W - 1 - x : x, ry = (fl & 2) ? g.H - 1 - y : y;  // pixel of the resized image
+    if (img) {
+      int x0, x1, ax0, ax1, y0, y1, ay0, ay1;
+      prep_axis(rx, g.W, g.Ws, true, x0, x1, ax0, ax1);
+      prep_axis(ry, g.H, g.Hs, false, y0, y1, ay0, ay1);
+      const uint8_t* r0 = img + ((int64_t)b * g.Hs + y0) * g.Ws * CH;
+      const uint8_t* r1 = img + ((int64_t)b * g.Hs + y1) * g.Ws * CH;
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        const int h0 = r0[x0 * CH + c] * ax0 + r0[x1 * CH + c] * ax1;  // horizontal pass, scale 2^11
+        const int h1 = r1[x0 * CH + c] * ax0 + r1[x1 * CH + c] * ax1;
+        int v = (((ay0 * (h0 >> 4)) >> 16) + ((ay1 * (h1 >> 4)) >> 16) + 2) >> 2;  // cv2 VResizeLinear<uchar>
+        v = min(max(v, 0), 255);
+        const float t = (float)((double)v - g.m255[c]);     // numpy: float32 array -= float64 mean
+        out[(((int64_t)b * CH + c) * g.H + y) * g.W + x] = (float)((double)t * g.inv[c]);
+      }
+    }
+    if (mask) {
+      const int sx = min((int)floor(rx * ((double)g.Ws / g.W)), g.Ws - 1);
+      const int sy = min((int)floor(ry * ((double)g.Hs / g.H)), g.Hs - 1);
+      const int v = mask[((int64_t)b * g.Hs + sy) * g.Ws + sx];
+      labels[i] = mask_mode ? v : (v > 127 ? 1 : 0);
+    }
+  }
+}
+
 
 // Confusion matrix of argmax(logits) against the labels: counts[t*C + p] += 1 (float counts are
 // exact up to 2^24 per launch per cell; the host accumulates in int64/double).
@@ -1071,6 +1248,32 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict_
   __syncthreads();
   for (int i = threadIdx.x; i < C * C; i += 256)
     if (sc[i] != 0.f) atomicAdd(counts + i, sc[i]);
+}
+
+// General class count (5 <= C <= 64): the block's C x C histogram lives in LDS as int32 (16 KB at C = 64) instead of C^2 registers per
+// thread; labels outside [0, C) are dropped (Evaluator._generate_matrix).
+__global__ __launch_bounds__(256) void confusion_gen_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+                                                            int B, int C, int64_t hw, float* __restrict__ counts) {
+  extern __shared__ int s_hist[];                     // [C * C]
+  for (int i = threadIdx.x; i < C * C; i += 256) s_hist[i] = 0;
+  __syncthreads();
+  const int64_t total = (int64_t)B * hw;
+  for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = idx / hw, i = idx - b * hw;
+    const float* lg = logits + b * C * hw + i;
+    int best = 0;
+    float bv = lg[0];
+#pragma unroll 8
+    for (int c = 1; c < C; ++c) {
+      const float v = lg[c * hw];
+      if (v > bv) { bv = v; best = c; }  // first maximum wins, as torch.argmax
+    }
+    const int64_t y = target[idx];
+    if (y >= 0 && y < C) atomicAdd(&s_hist[(int)y * C + best], 1);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < C * C; i += 256)
+    if (s_hist[i]) atomicAdd(counts + i, (float)s_hist[i]);
 }
 
 __global__ void copy2d_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows, int cols, int xs, int ys) {
@@ -1382,10 +1585,13 @@ int lmn_segloss_fwd(const float* logits, const int64_t* target, const float* w_c
                     int64_t HW, float label_smoothing, float smooth, float* sums, float* coef, float* loss,
                     lmn_stream_t stream) {
   LMN_REQUIRE(logits && target && w_ce && w_dice && sums && coef && loss, "segloss_fwd: null pointer");
-  LMN_REQUIRE(B > 0 && HW > 0 && (C == 2 || C == 3 || C == 4 || C == 8), "segloss_fwd: C=%d not in {2,3,4,8}", C);
+  LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= SG_MAXC, "segloss_fwd: C=%d not in [2, %d]", C, SG_MAXC);
   hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for((int64_t)B * HW) > 1024 ? 1024 : grid_for((int64_t)B * HW);
-  LMN_LAUNCH(fill_kernel, dim3(1), dim3(64), 0, st, sums, 0.f, (int64_t)(3 + 3 * C));
+  const bool gen = !(C == 2 || C == 3 || C == 4 || C == 8);
+  const int64_t tiles = ((int64_t)B * HW + 255) / 256;    // (the general form runs one 256-pixel tile per block and iteration)
+  const int grid = gen ? (int)(tiles > 1024 ? 1024 : tiles) : (grid_for((int64_t)B * HW) > 1024 ? 1024 : grid_for((int64_t)B * HW));
+  // (fill_kernel strides by 256: one block of 64 threads clears the first 64 entries, enough for C <= 20 only)
+  LMN_LAUNCH(fill_kernel, dim3(1), dim3(gen ? 256 : 64), 0, st, sums, 0.f, (int64_t)(3 + 3 * C));
   float* sd = sums;
   if (g_lmn_det) {
     lmn_det_begin(st);
@@ -1396,7 +1602,13 @@ int lmn_segloss_fwd(const float* logits, const int64_t* target, const float* w_c
     case 2: LMN_LAUNCH((segloss_sums_kernel<2>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, B, HW, sd, g_lmn_det); break;
     case 3: LMN_LAUNCH((segloss_sums_kernel<3>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, B, HW, sd, g_lmn_det); break;
     case 4: LMN_LAUNCH((segloss_sums_kernel<4>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, B, HW, sd, g_lmn_det); break;
-    default: LMN_LAUNCH((segloss_sums_kernel<8>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, B, HW, sd, g_lmn_det); break;
+    case 8: LMN_LAUNCH((segloss_sums_kernel<8>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, B, HW, sd, g_lmn_det); break;
+    default: {
+      const size_t sh = (size_t)4 * C * SG_STRIDE * sizeof(float);
+      if (sh > 64 * 1024) (void)hipFuncSetAttribute((const void*)segloss_sums_gen_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+      LMN_LAUNCH(segloss_sums_gen_kernel, dim3(grid), dim3(256), sh, st, logits, target, w_ce, B, C, HW, sd, g_lmn_det);
+      break;
+    }
   }
   if (g_lmn_det) lmn_det_sum(st, sd, grid, 3 + 3 * C, sums);
   LMN_LAUNCH(segloss_finish_kernel, dim3(1), dim3(64), 0, st, sums, w_ce, w_dice, C, label_smoothing, smooth, loss, coef);
@@ -1406,30 +1618,61 @@ int lmn_segloss_fwd(const float* logits, const int64_t* target, const float* w_c
 int lmn_segloss_bwd(const float* logits, const int64_t* target, const float* w_ce, const float* coef, const float* gscale,
                     int B, int C, int64_t HW, float* dlogits, lmn_stream_t stream) {
   LMN_REQUIRE(logits && target && w_ce && coef && dlogits, "segloss_bwd: null pointer");
-  LMN_REQUIRE(B > 0 && HW > 0 && (C == 2 || C == 3 || C == 4 || C == 8), "segloss_bwd: C=%d not in {2,3,4,8}", C);
+  LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= SG_MAXC, "segloss_bwd: C=%d not in [2, %d]", C, SG_MAXC);
   hipStream_t st = (hipStream_t)stream;
   const int grid = grid_for((int64_t)B * HW);
   switch (C) {
     case 2: LMN_LAUNCH((segloss_bwd_kernel<2>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, coef, gscale, B, HW, dlogits); break;
     case 3: LMN_LAUNCH((segloss_bwd_kernel<3>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, coef, gscale, B, HW, dlogits); break;
     case 4: LMN_LAUNCH((segloss_bwd_kernel<4>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, coef, gscale, B, HW, dlogits); break;
-    default: LMN_LAUNCH((segloss_bwd_kernel<8>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, coef, gscale, B, HW, dlogits); break;
+    case 8: LMN_LAUNCH((segloss_bwd_kernel<8>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, coef, gscale, B, HW, dlogits); break;
+    default: LMN_LAUNCH(segloss_bwd_gen_kernel, dim3(grid), dim3(256), (size_t)C * 256 * sizeof(float), st, logits, target, w_ce, coef,
+                        gscale, B, C, HW, dlogits); break;   // (<= 64 KB of LDS at C = 64)
   }
   return lmn_launch_status("segloss_bwd");
 }
 
 int lmn_confusion(const float* logits, const int64_t* target, int B, int C, int64_t HW, float* counts, lmn_stream_t stream) {
   LMN_REQUIRE(logits && target && counts, "confusion: null pointer");
-  LMN_REQUIRE(B > 0 && HW > 0 && (C == 2 || C == 3 || C == 4), "confusion: C=%d not in {2,3,4}", C);
+  LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= 64, "confusion: C=%d not in [2, 64]", C);
   LMN_REQUIRE((int64_t)B * HW < (1LL << 24) * 64, "confusion: more than 2^30 pixels per call");
   hipStream_t st = (hipStream_t)stream;
   const int grid = grid_for((int64_t)B * HW) > 512 ? 512 : grid_for((int64_t)B * HW);
   switch (C) {
     case 2: LMN_LAUNCH((confusion_kernel<2>), dim3(grid), dim3(256), 0, st, logits, target, B, HW, counts); break;
     case 3: LMN_LAUNCH((confusion_kernel<3>), dim3(grid), dim3(256), 0, st, logits, target, B, HW, counts); break;
-    default: LMN_LAUNCH((confusion_kernel<4>), dim3(grid), dim3(256), 0, st, logits, target, B, HW, counts); break;
+    case 4: LMN_LAUNCH((confusion_kernel<4>), dim3(grid), dim3(256), 0, st, logits, target, B, HW, counts); break;
+    default: LMN_LAUNCH(confusion_gen_kernel, dim3(grid), dim3(256), (size_t)C * C * sizeof(int), st, logits, target, B, C, HW, counts); break;
   }
   return lmn_launch_status("confusion");
+}
+
+int lmn_preprocess_u8_ex(const uint8_t* images, const uint8_t* masks, const uint8_t* flips, int B, int Hs, int Ws, int H, int W,
+                         int channels, int mask_mode, const double* mean, const double* std, float* out, int64_t* labels,
+                         lmn_stream_t stream) {
+  LMN_REQUIRE(channels == 1 || channels == 3, "preprocess_u8_ex: channels=%d not in {1, 3}", channels);
+  LMN_REQUIRE(mask_mode == 0 || mask_mode == 1, "preprocess_u8_ex: mask_mode=%d not in {0, 1}", mask_mode);
+  LMN_REQUIRE((images && out && mean && std) || (masks && labels), "preprocess_u8_ex: nothing to do");
+  LMN_REQUIRE(!images || (out && mean && std), "preprocess_u8_ex: images need out, mean and std");
+  LMN_REQUIRE(!masks || labels, "preprocess_u8_ex: masks need labels");
+  LMN_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "preprocess_u8_ex: empty tensor");
+  LMN_REQUIRE(Hs < 32768 && Ws < 32768 && H < 32768 && W < 32768, "preprocess_u8_ex: side above 32767");
+  PrepGeom g{B, Hs, Ws, H, W, {0, 0, 0}, {1, 1, 1}};
+  if (images) {
+    for (int c = 0; c < channels; ++c) {
+      LMN_REQUIRE(std[c] > 0.0, "preprocess_u8_ex: std[%d] must be positive", c);
+      g.m255[c] = mean[c] * 255.0;
+      g.inv[c] = 1.0 / (std[c] * 255.0);
+    }
+  }
+  const int64_t n = (int64_t)B * H * W;
+  if (channels == 1)
+    LMN_LAUNCH((preprocess_u8_ex_kernel<1>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, images ? images : nullptr,
+               masks ? masks : nullptr, flips, images ? out : nullptr, masks ? labels : nullptr, g, mask_mode);
+  else
+    LMN_LAUNCH((preprocess_u8_ex_kernel<3>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, images ? images : nullptr,
+               masks ? masks : nullptr, flips, images ? out : nullptr, masks ? labels : nullptr, g, mask_mode);
+  return lmn_launch_status("preprocess_u8_ex");
 }
 
 int lmn_preprocess_u8(const uint8_t* images, const uint8_t* masks, const uint8_t* flips, int B, int Hs, int Ws, int H,

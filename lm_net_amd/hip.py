@@ -19,7 +19,7 @@ ACT_NONE, ACT_HSWISH, ACT_GELU = 0, 1, 2
 STATS_NONE, STATS_SUM_SQ, STATS_EP = 0, 1, 2
 F32, BF16 = 0, 1            # matrix-core operand type of the dense contractions (LMN_F32 / LMN_BF16)
 _MMA = [F32]                # ... of the pass in flight (engine.begin_pass)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class SrcT(C.Structure):
@@ -139,7 +139,7 @@ SYMBOLS = [
     "lmn_se_fwd", "lmn_se_bwd", "lmn_se_bwd_dm", "lmn_se_bwd_params", "lmn_na_fwd", "lmn_na_bwd", "lmn_plan_host_profile", "lmn_set_deterministic", "lmn_get_deterministic", "lmn_gattn_fwd", "lmn_gattn_bwd",
     "lmn_ln_fwd", "lmn_ln_bwd", "lmn_bnact_fwd", "lmn_bnact_bwd_stats", "lmn_bnact_bwd",
     "lmn_bn_finalize", "lmn_bn_fold", "lmn_bn_bwd_coef", "lmn_up2_fwd", "lmn_up2_bwd", "lmn_avgpool_fwd", "lmn_avgpool_bwd",
-    "lmn_nchw_to_nhwc", "lmn_nhwc_to_nchw", "lmn_adamw_step", "lmn_segloss_fwd", "lmn_segloss_bwd", "lmn_confusion", "lmn_preprocess_u8", "lmn_fill", "lmn_add", "lmn_colsum", "lmn_copy_slice", "lmn_copy2d",
+    "lmn_nchw_to_nhwc", "lmn_nhwc_to_nchw", "lmn_adamw_step", "lmn_segloss_fwd", "lmn_segloss_bwd", "lmn_confusion", "lmn_preprocess_u8", "lmn_preprocess_u8_ex", "lmn_fill", "lmn_add", "lmn_colsum", "lmn_copy_slice", "lmn_copy2d",
     "lmn_stream_wait", "lmn_event_record", "lmn_event_wait", "lmn_set_priority_stream", "lmn_plan_create", "lmn_plan_destroy", "lmn_plan_record_begin", "lmn_plan_record_end", "lmn_plan_size",
     "lmn_plan_run", "lmn_prof_begin", "lmn_prof_end",
 ]
@@ -958,6 +958,32 @@ def preprocess_u8(images, masks, flips, out, labels, mean, std):
     m3, s3 = (C.c_double * 3)(*[float(v) for v in mean]), (C.c_double * 3)(*[float(v) for v in std])
     _check(load().lmn_preprocess_u8(raw(images, torch.uint8), raw(masks, torch.uint8), raw(flips, torch.uint8), B, Hs, Ws,
                                     H, W, m3, s3, _p(out), raw(labels, torch.int64), _stream()), "preprocess_u8")
+
+
+def preprocess_u8_ex(images, masks, flips, out, labels, mean, std, channels, mask_mode):
+    """uint8 images [B,Hs,Ws,channels] (channels 1: also [B,Hs,Ws]) / masks [B,Hs,Ws] -> fp32 NCHW `out` [B,channels,H,W] / int64
+    `labels` [B,H,W]; mask_mode 0 thresholds the mask at 127 into {0, 1}, 1 passes class ids through."""
+    def raw(t, dt):
+        if t is None:
+            return None
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError("lm_net_amd.preprocess_u8_ex: contiguous %s device tensor required" % dt)
+        return C.c_void_p(t.data_ptr())
+    ref = images if images is not None else masks
+    B, Hs, Ws = ref.shape[0], ref.shape[1], ref.shape[2]
+    dst = out if out is not None else labels
+    H, W = dst.shape[-2], dst.shape[-1]
+    if len(mean) != channels or len(std) != channels:
+        raise ValueError("lm_net_amd.preprocess_u8_ex: mean and std need %d entries" % channels)
+    if ((images is not None and (images.numel() != B * Hs * Ws * channels or out is None or out.numel() != B * channels * H * W))
+            or (masks is not None and (masks.numel() != B * Hs * Ws or labels is None or labels.numel() != B * H * W))
+            or (flips is not None and flips.numel() != B)):
+        raise ValueError("lm_net_amd.preprocess_u8_ex: tensor sizes do not match B=%d, %dx%d -> %dx%d, %d channel(s)"
+                         % (B, Hs, Ws, H, W, channels))
+    mc, sc = (C.c_double * channels)(*[float(v) for v in mean]), (C.c_double * channels)(*[float(v) for v in std])
+    _check(load().lmn_preprocess_u8_ex(raw(images, torch.uint8), raw(masks, torch.uint8), raw(flips, torch.uint8), B, Hs, Ws,
+                                       H, W, int(channels), int(mask_mode), mc, sc, _p(out), raw(labels, torch.int64), _stream()),
+           "preprocess_u8_ex")
 
 
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2):

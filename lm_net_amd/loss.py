@@ -38,17 +38,32 @@ class _SegLossFn(torch.autograd.Function):
 
 
 class SegLoss(torch.nn.Module):
-    """``CrossEntropyLoss(weight=ce_weight, label_smoothing) + DiceLoss(n_classes)(…, weight=dice_weight)``."""
+    """``CrossEntropyLoss(weight=ce_weight, label_smoothing) + DiceLoss(n_classes)(…, weight=dice_weight)``.
+
+    Any class count 2..64; labels must lie in [0, C).  ``ce_weight=None`` / ``dice_weight=None`` mean all ones, sized from the
+    logits (the reference's own defaults: ``nn.CrossEntropyLoss()``, ``DiceLoss`` with ``weight=None``)."""
+
+    MAX_CLASSES = 64
 
     def __init__(self, ce_weight=(1.0, 4.0), dice_weight=(1.0, 4.0), label_smoothing=0.0, smooth=1e-5):
         super().__init__()
-        self.register_buffer("ce_weight", torch.tensor(ce_weight, dtype=torch.float32))
-        self.register_buffer("dice_weight", torch.tensor(dice_weight, dtype=torch.float32))
+        self.register_buffer("ce_weight", None if ce_weight is None else torch.tensor(ce_weight, dtype=torch.float32))
+        self.register_buffer("dice_weight", None if dice_weight is None else torch.tensor(dice_weight, dtype=torch.float32))
         self.label_smoothing, self.smooth = float(label_smoothing), float(smooth)
 
+    def _weight(self, w, Cn, dev, what):
+        if w is None:
+            return torch.ones(Cn, device=dev, dtype=torch.float32)
+        if w.numel() != Cn:
+            raise ValueError("SegLoss: %d classes in the logits, %d %s weights" % (Cn, w.numel(), what))
+        return w
+
     def forward(self, logits, target):
-        if logits.shape[1] != self.ce_weight.numel():
-            raise ValueError("SegLoss: %d classes in the logits, %d weights" % (logits.shape[1], self.ce_weight.numel()))
+        Cn = logits.shape[1]
+        if not 2 <= Cn <= self.MAX_CLASSES:
+            raise ValueError("SegLoss: %d classes in the logits; the fused loss takes 2..%d" % (Cn, self.MAX_CLASSES))
+        w_ce = self._weight(self.ce_weight, Cn, logits.device, "ce")
+        w_dice = self._weight(self.dice_weight, Cn, logits.device, "dice")
         if target.dim() == logits.dim():          # the reference passes labels.unsqueeze(1) to the Dice term
             target = target[:, 0]
-        return _SegLossFn.apply(logits, target.long(), self.ce_weight, self.dice_weight, self.label_smoothing, self.smooth)
+        return _SegLossFn.apply(logits, target.long(), w_ce, w_dice, self.label_smoothing, self.smooth)
