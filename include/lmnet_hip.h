@@ -594,6 +594,40 @@ int lmn_preprocess_u8(const uint8_t* images, const uint8_t* masks, const uint8_t
 int lmn_preprocess_u8_ex(const uint8_t* images, const uint8_t* masks, const uint8_t* flips, int B, int Hs, int Ws, int H, int W,
                          int channels, int mask_mode, const double* mean, const double* std, float* out, int64_t* labels,
                          lmn_stream_t stream);
+/* (additive to ABI 15) Per-sample parameters of the training augmentations (lmn_augment_u8), drawn on the host
+ * (lm_net_amd.data.DeviceAugment.sample) and copied to the device once per batch as an array of B structs.          */
+typedef struct {
+  double M[6];      /* ShiftScaleRotate: FORWARD 2x3 matrix on the H x W crop-resized frame, as cv2.warpAffine takes it     */
+  double iM[6];     /* its inverse, cv2.invertAffineTransform arithmetic in double (filled by the host): what the kernel maps */
+  double cj[4];     /* ColorJitter factors: brightness, contrast, saturation (U[max(0,1-x), 1+x]) and hue (U[-h, h])        */
+  int32_t y0, x0, h, w;  /* RandomResizedCrop window in the sample's valid source area                                   */
+  int32_t apply_ssr;     /* 0: skip the warp                                                                             */
+  int32_t apply_cj;      /* 0: skip ColorJitter                                                                          */
+  int32_t flips;         /* bit 0 horizontal, bit 1 vertical                                                             */
+  int32_t order[4];      /* ColorJitter op order, a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue         */
+  int32_t _pad;
+} lmn_aug_param_t;
+int lmn_sizeof_aug_param(void);
+/* (additive to ABI 15) The per-sample part of the training transform (dataset/data_loading.py:207-216) on the device:
+ * RandomResizedCrop (:208) -> ShiftScaleRotate(BORDER_CONSTANT) (:210-211) -> HorizontalFlip / VerticalFlip (:212-213) ->
+ * ColorJitter (:214) -> Normalize + ToTensorV2 (:227-228); the OneOf block (:215-225) stays on the CPU.  Two kernels on `stream`:
+ *   1. geometry: per output pixel, undo the flips, map through iM with cv2.warpAffine's fixed-point arithmetic (AB_BITS 10,
+ *      INTER_BITS 5, border 0) and blend the four neighbours of the crop-resized frame with the 32768-scale remap weights; each
+ *      neighbour is cv2.resize INTER_LINEAR of the crop window computed straight from the raw frame (the lmn_preprocess_u8
+ *      arithmetic), so the reference's double resampling is reproduced without materialising the intermediate.  The mask takes
+ *      INTER_NEAREST both times, then mask_mode as in lmn_preprocess_u8_ex.  Writes uint8 `scratch` [B,H,W,channels], `labels`
+ *      and, for samples whose contrast factor runs, the grayscale sum of the image as contrast sees it into gray_sum [B] (uint64,
+ *      zeroed here; integer atomics).
+ *   2. colour + normalise: ColorJitter's four uint8 ops (albumentations adjust_*_torchvision) in the sample's order, then
+ *      (v - mean*255) * (1/(std*255)) into fp32 NCHW `out`.
+ * images [B,Hs,Ws,channels] / masks [B,Hs,Ws] uint8 (device; either may be NULL with its output).  params: HOST array of B
+ * structs; the entry checks every one (non-empty crop window inside src_hw[b] -- HOST int32 [B][2], the valid size of sample b
+ * inside the padded Hs x Ws frame, or NULL = Hs x Ws --, flips 0..3, order a permutation, finite factors, bounded iM) before any
+ * launch and copies them into params_dev (device, B structs) on `stream` (keep `params` alive until the stream has passed the
+ * call).  mean / std: HOST arrays of `channels` doubles.  Not recorded by plans.                                              */
+int lmn_augment_u8(const uint8_t* images, const uint8_t* masks, const lmn_aug_param_t* params, const int32_t* src_hw,
+                   lmn_aug_param_t* params_dev, int B, int Hs, int Ws, int H, int W, int channels, int mask_mode, const double* mean,
+                   const double* std, uint8_t* scratch, uint64_t* gray_sum, float* out, int64_t* labels, lmn_stream_t stream);
 /* One AdamW step over flat buffers of n floats (n % 4 == 0): replaces torch.optim.AdamW.step() of
  * train.py:156 when parameters and gradients live in the flat layout of lm_net_amd.LM_Net.
  * bias_corr1 = 1 - beta1^t, bias_corr2 = 1 - beta2^t (t = step count, from the host). */

@@ -7,6 +7,7 @@ shared library is missing the import raises, and calling any op with a non-devic
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -130,6 +131,13 @@ class ReduceJob(C.Structure):
                 ("dW", C.c_void_p), ("dW_src", C.c_void_p * 3), ("db", C.c_void_p), ("db2", C.c_void_p)]
 
 
+
+class AugParam(C.Structure):
+    """Mirror of lmn_aug_param_t: one sample's parameters of lmn_augment_u8 (lm_net_amd.data.DeviceAugment)."""
+    _fields_ = [("M", C.c_double * 6), ("iM", C.c_double * 6), ("cj", C.c_double * 4), ("y0", C.c_int32), ("x0", C.c_int32),
+                ("h", C.c_int32), ("w", C.c_int32), ("apply_ssr", C.c_int32), ("apply_cj", C.c_int32), ("flips", C.c_int32),
+                ("order", C.c_int32 * 4), ("_pad", C.c_int32)]
+
 # every symbol include/lmnet_hip.h declares (the CPU test suite checks the library exports all of them)
 SYMBOLS = [
     "lmn_abi_version", "lmn_sizeof_conv_args", "lmn_sizeof_src", "lmn_sizeof_wgrad_args", "lmn_last_error",
@@ -139,7 +147,7 @@ SYMBOLS = [
     "lmn_se_fwd", "lmn_se_bwd", "lmn_se_bwd_dm", "lmn_se_bwd_params", "lmn_na_fwd", "lmn_na_bwd", "lmn_plan_host_profile", "lmn_set_deterministic", "lmn_get_deterministic", "lmn_gattn_fwd", "lmn_gattn_bwd",
     "lmn_ln_fwd", "lmn_ln_bwd", "lmn_bnact_fwd", "lmn_bnact_bwd_stats", "lmn_bnact_bwd",
     "lmn_bn_finalize", "lmn_bn_fold", "lmn_bn_bwd_coef", "lmn_up2_fwd", "lmn_up2_bwd", "lmn_avgpool_fwd", "lmn_avgpool_bwd",
-    "lmn_nchw_to_nhwc", "lmn_nhwc_to_nchw", "lmn_adamw_step", "lmn_segloss_fwd", "lmn_segloss_bwd", "lmn_confusion", "lmn_preprocess_u8", "lmn_preprocess_u8_ex", "lmn_fill", "lmn_add", "lmn_colsum", "lmn_copy_slice", "lmn_copy2d",
+    "lmn_nchw_to_nhwc", "lmn_nhwc_to_nchw", "lmn_adamw_step", "lmn_segloss_fwd", "lmn_segloss_bwd", "lmn_confusion", "lmn_preprocess_u8", "lmn_preprocess_u8_ex", "lmn_sizeof_aug_param", "lmn_augment_u8", "lmn_fill", "lmn_add", "lmn_colsum", "lmn_copy_slice", "lmn_copy2d",
     "lmn_stream_wait", "lmn_event_record", "lmn_event_wait", "lmn_set_priority_stream", "lmn_plan_create", "lmn_plan_destroy", "lmn_plan_record_begin", "lmn_plan_record_end", "lmn_plan_size",
     "lmn_plan_run", "lmn_prof_begin", "lmn_prof_end",
 ]
@@ -170,7 +178,8 @@ def load():
     if lib.lmn_abi_version() != ABI_VERSION:
         raise RuntimeError("lm_net_amd: ABI version mismatch")
     if (lib.lmn_sizeof_conv_args() != C.sizeof(ConvArgs) or lib.lmn_sizeof_src() != C.sizeof(SrcT)
-            or lib.lmn_sizeof_wgrad_args() != C.sizeof(WgradArgs) or lib.lmn_sizeof_reduce_job() != C.sizeof(ReduceJob)):
+            or lib.lmn_sizeof_wgrad_args() != C.sizeof(WgradArgs) or lib.lmn_sizeof_reduce_job() != C.sizeof(ReduceJob)
+            or lib.lmn_sizeof_aug_param() != C.sizeof(AugParam)):
         raise RuntimeError("lm_net_amd: argument struct layout differs between hip.py and lmnet_hip.h")
     _lib = lib
     return lib
@@ -985,6 +994,45 @@ def preprocess_u8_ex(images, masks, flips, out, labels, mean, std, channels, mas
                                        H, W, int(channels), int(mask_mode), mc, sc, _p(out), raw(labels, torch.int64), _stream()),
            "preprocess_u8_ex")
 
+
+
+def augment_u8(images, masks, params, src_hw, params_dev, scratch, gray_sum, out, labels, mean, std, channels, mask_mode):
+    """uint8 images [B,Hs,Ws,channels] (channels 1: also [B,Hs,Ws]) / masks [B,Hs,Ws] -> fp32 NCHW `out` [B,channels,H,W] / int64
+    `labels` [B,H,W] through lmn_augment_u8.  params: host ctypes array of B AugParam (checked and copied into the device buffer
+    params_dev, uint8 [B * sizeof(AugParam)]); src_hw: host int32 numpy array [B,2] or None; scratch: uint8 [B,H,W,channels];
+    gray_sum: int64 [B] (the kernels' uint64 sums)."""
+    def raw(t, dt):
+        if t is None:
+            return None
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError("lm_net_amd.augment_u8: contiguous %s device tensor required" % dt)
+        return C.c_void_p(t.data_ptr())
+    ref = images if images is not None else masks
+    if ref is None:
+        raise ValueError("lm_net_amd.augment_u8: images or masks required")
+    B, Hs, Ws = ref.shape[0], ref.shape[1], ref.shape[2]
+    dst = out if out is not None else labels
+    if dst is None:
+        raise ValueError("lm_net_amd.augment_u8: out or labels required")
+    H, W = dst.shape[-2], dst.shape[-1]
+    if channels not in (1, 3) or mask_mode not in (0, 1):
+        raise ValueError("lm_net_amd.augment_u8: channels %r / mask_mode %r" % (channels, mask_mode))
+    if len(mean) != channels or len(std) != channels:
+        raise ValueError("lm_net_amd.augment_u8: mean and std need %d entries" % channels)
+    if ((images is not None and (images.numel() != B * Hs * Ws * channels or out is None or out.numel() != B * channels * H * W
+                                 or scratch is None or scratch.numel() != B * H * W * channels
+                                 or gray_sum is None or gray_sum.numel() != B))
+            or (masks is not None and (masks.numel() != B * Hs * Ws or labels is None or labels.numel() != B * H * W))
+            or len(params) != B or params_dev.numel() != B * C.sizeof(AugParam)
+            or (src_hw is not None and tuple(src_hw.shape) != (B, 2))):
+        raise ValueError("lm_net_amd.augment_u8: tensor sizes do not match B=%d, %dx%d -> %dx%d, %d channel(s)"
+                         % (B, Hs, Ws, H, W, channels))
+    hw_arr = None if src_hw is None else np.ascontiguousarray(src_hw, dtype=np.int32)   # (kept alive across the call)
+    hw = None if hw_arr is None else hw_arr.ctypes.data_as(C.POINTER(C.c_int32))
+    mc, sc = (C.c_double * channels)(*[float(v) for v in mean]), (C.c_double * channels)(*[float(v) for v in std])
+    _check(load().lmn_augment_u8(raw(images, torch.uint8), raw(masks, torch.uint8), params, hw, raw(params_dev, torch.uint8), B, Hs,
+                                 Ws, H, W, int(channels), int(mask_mode), mc, sc, raw(scratch, torch.uint8),
+                                 raw(gray_sum, torch.int64), _p(out), raw(labels, torch.int64), _stream()), "augment_u8")
 
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2):
     _check(load().lmn_adamw_step(_p(p), _p(g), _p(m), _p(v), _i64(p.numel()), _f(lr), _f(beta1), _f(beta2), _f(eps),
