@@ -3,6 +3,11 @@
     python bench.py --gpus 1 --steps 20 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --full      (also the roofline, the other configurations, deterministic mode and the CPU baseline)
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line.  --full adds, after the
+timed steps and outside them, what takes runs of its own: the `roofline` block (row and serial-step kernel timings),
+`other_configs`, `deterministic_mode` and `cpu_baseline`.  The timed steps are the same in both.
 
 A step = one full training step of BASELINE.json configs[1] ("LM-Net fp32 training, batch 8, 352x352
 synthetic masks") per GPU: forward, CE(weight [1,4], label_smoothing 1e-3) + Dice(weight [1,4]) loss
@@ -561,9 +566,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8, help="images per GPU")
     ap.add_argument("--size", type=int, default=352)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline block (extra untimed steps with kernel timers), the "
+                         "other BASELINE configurations, deterministic mode and the CPU baseline; the timed steps are unchanged")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the extra lines for BASELINE configs[2] (bf16, batch 64) and configs[4] at one GPU (512x512, batch 32)")
+                    help="with --full: skip the extra lines for BASELINE configs[2] (bf16, batch 64) and configs[4] at one GPU "
+                         "(512x512, batch 32), and the deterministic-mode check")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="arithmetic of the dense contractions: f32 (BASELINE configs[1], the headline) or bf16 matrix-core operands "
                          "with fp32 accumulation / statistics / master weights (BASELINE configs[2]; run with --batch 64)")
@@ -646,6 +655,8 @@ def main():
     # ---- timed region: ONLY the dominant kernel is timed live (HIP events around its launches: the `roofline` contract).  Timing
     # the A2 / A7 kernels there as well (~90 launches, two events each) cost the step 0.45 ms (15.2 -> 15.65 ms, LMN_BENCH_NOLIVE=1
     # for the figure without any timer): they are timed over the same number of steps right after, outside the headline.
+    # The survey and these live events are part of every run, --full or not, so the timed steps and ms_per_step are the same in
+    # both; the steps after the timed region that feed `roofline` run only with --full.
     torch.cuda.synchronize()
     nolive = os.environ.get("LMN_BENCH_NOLIVE") == "1"      # (measurement of the timers' own cost: no kernel timed in the region)
     head = [dominant] + [k for k in survey if "wgrad_reduce" in k and "wgrad" in dominant]
@@ -658,7 +669,7 @@ def main():
         dumped = dump_outputs(run, loss, args.dump_outputs)
         print("bench.py: wrote %s to %s" % (", ".join(dumped), args.dump_outputs), file=sys.stderr)
         run.keep_out, run.out = False, None
-    if not net.use_graphs:
+    if args.full and not net.use_graphs:
         rows = [k for k in watch if k.split("<")[0] not in set(h.split("<")[0] for h in head)] if not nolive else watch
         if rows:
             torch.cuda.synchronize()
@@ -666,7 +677,7 @@ def main():
             for _ in range(args.steps):
                 step()
             live = {**hip.prof_end(), **live}
-    if net.use_graphs:      # replays run no host code: time the same kernels over 5 host-launched steps right after
+    if args.full and net.use_graphs:      # replays run no host code: time the same kernels over 5 host-launched steps right after
         net.use_graphs = False
         hip.prof_begin("|".join(sorted(set(w.split("<")[0] for w in watch))))
         for _ in range(5):
@@ -680,17 +691,18 @@ def main():
                 "buckets_per_step": len(red.launched), "launched_before_finish": red.launched_before_finish,
                 "bucket_bounds_floats": [list(b) for b in red.launched],
                 "gradient_MB": round(net._grad_flat.numel() * 4 / 1e6, 2) if net._grad_flat is not None else None}
-    # the same kernels with nothing else on the GPU: 3 more steps launched from the host with the branch / weight-gradient
-    # streams switched off (inside the timed region a kernel shares the CUs with the other streams of the step)
-    saved = (eng.branch_overlap, eng.overlap_wgrad, net.use_graphs, net.use_plans)
-    eng.branch_overlap, eng.overlap_wgrad, net.use_graphs, net.use_plans = False, False, False, False
-    for _ in range(2):
-        step()
-    hip.prof_begin("|".join(sorted(set(w.split("<")[0] for w in watch))))
-    for _ in range(3):
-        step()
-    alone = hip.prof_end()
-    eng.branch_overlap, eng.overlap_wgrad, net.use_graphs, net.use_plans = saved
+    if args.full:
+        # the same kernels with nothing else on the GPU: 3 more steps launched from the host with the branch / weight-gradient
+        # streams switched off (inside the timed region a kernel shares the CUs with the other streams of the step)
+        saved = (eng.branch_overlap, eng.overlap_wgrad, net.use_graphs, net.use_plans)
+        eng.branch_overlap, eng.overlap_wgrad, net.use_graphs, net.use_plans = False, False, False, False
+        for _ in range(2):
+            step()
+        hip.prof_begin("|".join(sorted(set(w.split("<")[0] for w in watch))))
+        for _ in range(3):
+            step()
+        alone = hip.prof_end()
+        eng.branch_overlap, eng.overlap_wgrad, net.use_graphs, net.use_plans = saved
     if rank == 0:
         step_s = dt / args.steps
         cfg_idx = 1 if args.dtype == "f32" else 2
@@ -708,17 +720,18 @@ def main():
                                  ("lmn_plan_run (recorded C-side schedule, one crossing per pass)" if args.plans else "host"),
                        "kernel_launches_per_step": launches_per_step,
                        "final_loss": round(float(loss.detach()), 5)},
-            "roofline": dict(roofline_block(dominant, live, survey, tot_us, B, H, W, step_s, alone, esz),
-                             largest_share_without_algorithmic_cost=(None if zero_cost_top is None else
-                                                                     {"kernel": zero_cost_top, "share_of_gpu_time": round(survey[zero_cost_top]["total_us"] / tot_us, 4),
-                                                                      "avg_us": round(survey[zero_cost_top]["total_us"] / max(survey[zero_cost_top]["launches"], 1), 1)})),
         }
+        if args.full:
+            res["roofline"] = dict(roofline_block(dominant, live, survey, tot_us, B, H, W, step_s, alone, esz),
+                                   largest_share_without_algorithmic_cost=(None if zero_cost_top is None else
+                                                                           {"kernel": zero_cost_top, "share_of_gpu_time": round(survey[zero_cost_top]["total_us"] / tot_us, 4),
+                                                                            "avg_us": round(survey[zero_cost_top]["total_us"] / max(survey[zero_cost_top]["launches"], 1), 1)}))
         if comm is not None:
             res["allreduce"] = comm
     run = net = step = None
     if rank == 0:
         default_headline = world == 1 and (args.dtype, B, H) == ("f32", 8, 352)
-        if default_headline and not args.no_other_configs:
+        if args.full and default_headline and not args.no_other_configs:
             torch.cuda.empty_cache()
             # the two other single-GPU BASELINE configurations, timed in this process AFTER the headline (value / config / dtype of
             # the line stay configs[1]): configs[2] = bf16 storage + bf16 MFMA operands at batch 64; configs[4] at one GPU =
@@ -726,7 +739,7 @@ def main():
             res["other_configs"] = {"configs[2] bf16 mixed precision, batch 64, 352x352": other_config(dev, "bf16", 64, 352),
                                     "configs[4] on 1 GPU: fp32, 512x512, batch 32": other_config(dev, "f32", 32, 512)}
             res["deterministic_mode"] = deterministic_check(dev, 8, 352)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(H, W)
         print(json.dumps(res))
     if world > 1:

@@ -5,7 +5,7 @@ showed only at this size -- at the 2 x 96 x 128 of test_model_gpu.py the kernels
 All comparisons run in deterministic mode (fixed-order reductions, lmn_set_deterministic), where a different stream interleaving or
 launch path must not change one bit; the A/B switches of INTEGRATION.md section 5 change the arithmetic's grouping, so they are held
 to the gradient tolerance of the oracle tests instead.  Also here: `bench.py --gpus 2` through its own launcher (two ranks on the one
-test GPU over gloo) and its refusal (exit 2) of a rank count the box cannot hold."""
+test GPU over gloo), the headline-only line of a plain run, and the refusal (exit 2) of a rank count the box cannot hold."""
 import json
 import os
 import subprocess
@@ -171,8 +171,9 @@ def _bench(args, env_extra, timeout=600):
 def test_bench_two_ranks_through_its_own_launcher():
     """`python bench.py --gpus 2` starts its ranks itself (torch.distributed.run, 127.0.0.1) before anything touches the GPU; with
     LMNET_BENCH_BACKEND=gloo both ranks share the one test GPU.  The line must say two ranks, carry the all-reduce record, and show
-    gradient buckets launched while the backward was still running."""
-    p = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs"], dict(LMNET_BENCH_BACKEND="gloo"))
+    gradient buckets launched while the backward was still running.  --full: the line carries the `roofline` block as well."""
+    p = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs"],
+               dict(LMNET_BENCH_BACKEND="gloo"))
     assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -189,6 +190,20 @@ def test_bench_two_ranks_through_its_own_launcher():
     assert abs(bounds[-1][1] * 4 / 1e6 - r["allreduce"]["gradient_MB"]) < 0.01 and 15.8 < r["allreduce"]["gradient_MB"] < 15.95, r["allreduce"]
     assert r["value"] > 0 and abs(r["value"] - 16 * 2 / (r["ms_per_step"] * 2e-3)) < 1e-2 * r["value"]
     assert "cpu_baseline" not in r and r["roofline"]["kernel"]
+
+
+def test_bench_plain_run_prints_the_headline_only():
+    """Without --full the line is the headline: value over the timed steps, ms_per_step and the run's configuration, and none of
+    the blocks that take runs of their own."""
+    p = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1"], {})
+    assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["n_gpus"] == 1 and r["steps"] == 2 and r["warmup"] == 1 and r["dtype"] == "f32" and r["higher_is_better"] is True, r
+    assert r["unit"] == "images/sec" and r["metric"].startswith("train images/sec at 352x352"), r
+    assert r["value"] > 0 and abs(r["value"] - 8 * 2 / (r["ms_per_step"] * 2e-3)) < 1e-2 * r["value"]
+    assert not {"roofline", "other_configs", "deterministic_mode", "cpu_baseline", "allreduce"} & set(r), sorted(r)
 
 
 def test_bench_refuses_more_rccl_ranks_than_gpus():

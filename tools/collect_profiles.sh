@@ -3,7 +3,8 @@
 # back in the container: `python tools/refresh_profiles.py r02a` copies the summaries into profiles/.
 D=${1:-r02x}
 shift
-EXTRA="$@"
+# every run is the full benchmark: the bench line carries `roofline` etc., and the profiled runs hold its row and serial steps
+EXTRA="--full $@"
 R=$GRAFT_REPO_ROOT
 rm -rf $R/gpurun_out/$D; mkdir -p $R/gpurun_out/$D
 cd $R
