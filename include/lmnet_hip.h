@@ -628,6 +628,28 @@ int lmn_sizeof_aug_param(void);
 int lmn_augment_u8(const uint8_t* images, const uint8_t* masks, const lmn_aug_param_t* params, const int32_t* src_hw,
                    lmn_aug_param_t* params_dev, int B, int Hs, int Ws, int H, int W, int channels, int mask_mode, const double* mean,
                    const double* std, uint8_t* scratch, uint64_t* gray_sum, float* out, int64_t* labels, lmn_stream_t stream);
+/* (additive to ABI 15: new symbols only, no struct or signature touched) Surface-distance statistics of a batch, the device half of
+ * lm_net_amd.metrics.SurfaceDistanceMeter: HD, HD95, ASSD and RVD in the medpy.metric.binary conventions (hd, hd95, assd, ravd),
+ * the boundary metrics the reference's evaluate() prepares for and never computes (utils/train_eval_utils.py:7 imports
+ * skimage.metrics.hausdorff_distance, :178-179 set up hausdorff_distance_list and rvd_list, :14-52 ravd / RVDEvaluator).
+ * lmn_surface_workspace: bytes of scratch lmn_surface_dist needs for B samples x nk classes of H x W pixels (host arithmetic:
+ * two uint8 label maps per sample; a uint16 column distance and an int32 squared distance per pixel, map and pair; an int32 count
+ * per row, map and pair); -1 and
+ * lmn_last_error when B < 1, nk outside [1, 64], B * nk > 65535 or a side outside [2, 1024].
+ * lmn_surface_dist: the prediction is EITHER pred_logits [B,C,H,W] fp32 (arg-max over C, first maximum wins as lmn_confusion) OR
+ * pred_labels [B,H,W] int64 (the other NULL); target [B,H,W] int64; values outside [0, C) belong to no class.  classes: HOST array
+ * of nk class ids in [0, C).  For pair (b, k) = sample b, class classes[k], with P = (pred == class), T = (target == class), the
+ * border of a mask = its pixels with a 4-neighbour outside it (outside the image counts as outside) and D2(A -> B) = the squared
+ * Euclidean pixel distance of every border pixel of A to the nearest border pixel of B (exact int32):
+ *   stats_i [B][nk][8] int64: |P|, |T|, border count of P, of T, max D2(P -> T), max D2(T -> P), and D2[lo], D2[hi] of the pooled
+ *     multiset D2(P -> T) U D2(T -> P) sorted ascending, lo = 95 (n - 1) / 100 (integer), hi = min(lo + 1, n - 1), n = its size;
+ *   stats_f [B][nk][2] float64: sum sqrt(D2(P -> T)), sum sqrt(D2(T -> P)), each summed in a fixed order.
+ * A pair with |P| = 0 or |T| = 0 keeps its counts and gets 0 in the six other fields.  No float atomics: the statistics of two calls
+ * on one input are bit-identical.  Four kernels on `stream`; stats_i is zeroed here.  Not recorded by plans.                  */
+int64_t lmn_surface_workspace(int B, int nk, int H, int W);
+int lmn_surface_dist(const float* pred_logits, const int64_t* pred_labels, const int64_t* target, int B, int C, int H, int W,
+                     const int32_t* classes, int nk, void* workspace, int64_t ws_bytes, int64_t* stats_i, double* stats_f,
+                     lmn_stream_t stream);
 /* One AdamW step over flat buffers of n floats (n % 4 == 0): replaces torch.optim.AdamW.step() of
  * train.py:156 when parameters and gradients live in the flat layout of lm_net_amd.LM_Net.
  * bias_corr1 = 1 - beta1^t, bias_corr2 = 1 - beta2^t (t = step count, from the host). */

@@ -147,7 +147,7 @@ SYMBOLS = [
     "lmn_se_fwd", "lmn_se_bwd", "lmn_se_bwd_dm", "lmn_se_bwd_params", "lmn_na_fwd", "lmn_na_bwd", "lmn_plan_host_profile", "lmn_set_deterministic", "lmn_get_deterministic", "lmn_gattn_fwd", "lmn_gattn_bwd",
     "lmn_ln_fwd", "lmn_ln_bwd", "lmn_bnact_fwd", "lmn_bnact_bwd_stats", "lmn_bnact_bwd",
     "lmn_bn_finalize", "lmn_bn_fold", "lmn_bn_bwd_coef", "lmn_up2_fwd", "lmn_up2_bwd", "lmn_avgpool_fwd", "lmn_avgpool_bwd",
-    "lmn_nchw_to_nhwc", "lmn_nhwc_to_nchw", "lmn_adamw_step", "lmn_segloss_fwd", "lmn_segloss_bwd", "lmn_confusion", "lmn_preprocess_u8", "lmn_preprocess_u8_ex", "lmn_sizeof_aug_param", "lmn_augment_u8", "lmn_fill", "lmn_add", "lmn_colsum", "lmn_copy_slice", "lmn_copy2d",
+    "lmn_nchw_to_nhwc", "lmn_nhwc_to_nchw", "lmn_adamw_step", "lmn_segloss_fwd", "lmn_segloss_bwd", "lmn_confusion", "lmn_preprocess_u8", "lmn_preprocess_u8_ex", "lmn_sizeof_aug_param", "lmn_augment_u8", "lmn_surface_workspace", "lmn_surface_dist", "lmn_fill", "lmn_add", "lmn_colsum", "lmn_copy_slice", "lmn_copy2d",
     "lmn_stream_wait", "lmn_event_record", "lmn_event_wait", "lmn_set_priority_stream", "lmn_plan_create", "lmn_plan_destroy", "lmn_plan_record_begin", "lmn_plan_record_end", "lmn_plan_size",
     "lmn_plan_run", "lmn_prof_begin", "lmn_prof_end",
 ]
@@ -171,6 +171,7 @@ def load():
     lib.lmn_last_error.restype = C.c_char_p
     lib.lmn_conv_pack_size.restype = C.c_int64
     lib.lmn_conv_wgrad_workspace.restype = C.c_int64
+    lib.lmn_surface_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -950,6 +951,37 @@ def confusion(logits, target, counts):
     B, Cn = logits.shape[0], logits.shape[1]
     hw = logits.numel() // (B * Cn)
     _check(load().lmn_confusion(_p(logits), _pl(target), B, Cn, _i64(hw), _p(counts), _stream()), "confusion")
+
+
+def surface_workspace(B, nk, H, W):
+    """Bytes of scratch lmn_surface_dist needs for B samples x nk classes of H x W pixels (host arithmetic, no GPU)."""
+    n = int(load().lmn_surface_workspace(int(B), int(nk), int(H), int(W)))
+    if n < 0:
+        raise ValueError("lm_net_amd.surface_workspace: " + load().lmn_last_error().decode())
+    return n
+
+
+def surface_dist(pred, target, n_classes, classes, workspace, stats_i, stats_f):
+    """Raw surface-distance statistics of one batch (lmn_surface_dist).  pred: fp32 logits [B,C,H,W] or int64 labels [B,H,W];
+    target int64 [B,H,W]; classes: the class ids scored (host list); workspace: uint8 device tensor of at least
+    surface_workspace(B, len(classes), H, W) bytes; stats_i int64 [B,nk,8] and stats_f float64 [B,nk,2] device tensors."""
+    nk = len(classes)
+    B, H, W = target.shape
+    for t, dt in ((workspace, torch.uint8), (stats_i, torch.int64), (stats_f, torch.float64)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError("lm_net_amd.surface_dist: contiguous %s device tensor required" % dt)
+    if stats_i.numel() != B * nk * 8 or stats_f.numel() != B * nk * 2:
+        raise ValueError("lm_net_amd.surface_dist: statistics buffers do not match B=%d, %d classes" % (B, nk))
+    logits = pred if pred.dim() == 4 else None
+    labels = pred if pred.dim() == 3 else None
+    if (logits is None) == (labels is None) or tuple(pred.shape[-2:]) != (H, W) or pred.shape[0] != B:
+        raise ValueError("lm_net_amd.surface_dist: pred %s does not match target %s" % (tuple(pred.shape), tuple(target.shape)))
+    if logits is not None and (logits.shape[1] != n_classes or not logits.is_contiguous()):
+        raise ValueError("lm_net_amd.surface_dist: contiguous logits with %d channels required" % n_classes)
+    ids = (C.c_int32 * nk)(*[int(k) for k in classes])
+    _check(load().lmn_surface_dist(_p(logits), _pl(labels), _pl(target), B, int(n_classes), H, W, ids, nk,
+                                   C.c_void_p(workspace.data_ptr()), _i64(workspace.numel()), C.c_void_p(stats_i.data_ptr()),
+                                   C.c_void_p(stats_f.data_ptr()), _stream()), "surface_dist")
 
 
 def preprocess_u8(images, masks, flips, out, labels, mean, std):

@@ -5,6 +5,12 @@ The reference moves every batch to the CPU and updates a torchmetrics collection
 GPU (one kernel per batch, no sync) and derives Dice ``2TP/(2TP+FP+FN)`` and IoU ``TP/(TP+FP+FN)`` per class
 (``train_eval_utils.py:78-95``) when ``compute()`` is called, plus the reference ``Evaluator``'s other metrics
 (``train_eval_utils.py:55-118``) under its method names.  Any class count 2..64 (labels outside [0, C) are not counted).
+
+``SurfaceDistanceMeter`` adds the boundary metrics that go with them in a results table -- HD, HD95, ASSD and RVD in the
+``medpy.metric.binary`` conventions -- which the reference's ``evaluate()`` prepares for (``train_eval_utils.py:7`` imports
+``hausdorff_distance``, ``:178-179`` set up ``hausdorff_distance_list`` / ``rvd_list``, ``:14-52`` ``ravd`` / ``RVDEvaluator``) and
+never computes.  The device produces ten exact raw statistics per (sample, class) pair (``lmn_surface_dist``); ``compute()`` turns
+them into the metrics in float64 on the host.
 """
 import numpy as np
 import torch
@@ -41,6 +47,144 @@ class ConfusionMeter:
         out = dict(dice=dice, iou=iou, accuracy=float(tp.sum() / m.sum().clamp_min(1)), confusion=m.long().tolist())
         out.update(evaluator_metrics(m.numpy()))
         return out
+
+
+class SurfaceDistanceMeter:
+    """HD, HD95, ASSD and RVD per class, accumulated on the device.
+
+    For one sample and class k, P = (pred == k), T = (target == k).  The border of a mask is its pixels with a 4-neighbour outside
+    it (outside the image counts as outside); D2(A -> B) is the squared pixel distance of every border pixel of A to the nearest
+    border pixel of B.  HD = sqrt(max D2), HD95 = numpy's 95th percentile (linear) of the pooled sqrt(D2(P -> T)) U sqrt(D2(T -> P)),
+    ASSD = the mean of the two directed means, RVD = (|P| - |T|) / |T| (0 when |T| = 0).  A pair is valid for HD / HD95 / ASSD when
+    P and T are both non-empty; the others are counted as empty_pred / empty_target / empty_both and not scored.  ``spacing``: one
+    isotropic pixel size that scales HD, HD95 and ASSD.
+
+    update(pred, target): pred = fp32 logits [B, C, H, W] (arg-max, first maximum wins) or an integer label map [B, H, W]; target
+    [B, H, W] integer; 2 <= H, W <= 1024; no host synchronisation.  Batches whose pairs need more than ``workspace_mb`` of scratch
+    run in chunks of samples (and of classes, if one sample is too much); the statistics do not depend on the chunking."""
+
+    RAW_I = ("n_pred", "n_target", "border_pred", "border_target", "max_d2_pt", "max_d2_tp", "d2_lo", "d2_hi")
+
+    def __init__(self, n_classes, classes=None, spacing=1.0, device="cuda", workspace_mb=256):
+        if not 2 <= n_classes <= 64:
+            raise ValueError("SurfaceDistanceMeter: n_classes = %d outside [2, 64]" % n_classes)
+        classes = list(range(1, n_classes)) if classes is None else [int(k) for k in classes]
+        if not classes or len(set(classes)) != len(classes) or min(classes) < 0 or max(classes) >= n_classes:
+            raise ValueError("SurfaceDistanceMeter: classes %r must be distinct ids in [0, %d)" % (classes, n_classes))
+        if not spacing > 0 or not workspace_mb > 0:
+            raise ValueError("SurfaceDistanceMeter: spacing and workspace_mb must be positive")
+        self.n, self.classes, self.spacing, self.device = n_classes, classes, float(spacing), torch.device(device)
+        self.workspace_bytes = int(workspace_mb * (1 << 20))
+        self._si, self._sf = [], []
+
+    def reset(self):
+        self._si, self._sf = [], []
+
+    def chunking(self, B, H, W):
+        """(samples, classes) per lmn_surface_dist call: the largest chunk whose scratch fits workspace_mb."""
+        nk = len(self.classes)
+        need = lambda b, k: hip.surface_workspace(b, k, H, W)
+        if need(1, 1) > self.workspace_bytes:
+            raise ValueError("SurfaceDistanceMeter: one %dx%d pair needs %d bytes of scratch, workspace_mb allows %d"
+                             % (H, W, need(1, 1), self.workspace_bytes))
+        if need(1, nk) > self.workspace_bytes:
+            return 1, max(k for k in range(1, nk) if need(1, k) <= self.workspace_bytes)
+        cap = min(B, 65535 // nk)
+        return max(b for b in range(1, cap + 1) if need(b, nk) <= self.workspace_bytes), nk
+
+    @torch.no_grad()
+    def update(self, pred, target):
+        if not pred.is_cuda or not target.is_cuda:
+            raise RuntimeError("lm_net_amd.SurfaceDistanceMeter: device tensors required (the HIP path has no CPU fallback)")
+        if pred.dim() == 4:
+            if pred.shape[1] != self.n:
+                raise ValueError("SurfaceDistanceMeter: logits with %d channels, n_classes = %d" % (pred.shape[1], self.n))
+            pred = pred.contiguous().float()
+        elif pred.dim() == 3 and not pred.is_floating_point():
+            pred = pred.contiguous().long()
+        else:
+            raise ValueError("SurfaceDistanceMeter: pred must be logits [B, C, H, W] or an integer label map [B, H, W]")
+        target = target.contiguous().long()
+        if target.dim() != 3 or target.shape[0] != pred.shape[0] or target.shape[-2:] != pred.shape[-2:]:
+            raise ValueError("SurfaceDistanceMeter: target %s does not match pred %s" % (tuple(target.shape), tuple(pred.shape)))
+        B, H, W = target.shape
+        nk = len(self.classes)
+        bs, ks = self.chunking(B, H, W)
+        ws = torch.empty(hip.surface_workspace(bs, ks, H, W), device=pred.device, dtype=torch.uint8)
+        si = torch.empty(B, nk, 8, device=pred.device, dtype=torch.int64)
+        sf = torch.empty(B, nk, 2, device=pred.device, dtype=torch.float64)
+        for b0 in range(0, B, bs):
+            b1 = min(b0 + bs, B)
+            for k0 in range(0, nk, ks):
+                k1 = min(k0 + ks, nk)
+                whole = k0 == 0 and k1 == nk                     # (a chunk of whole samples is a contiguous slice: written in place)
+                ci = si[b0:b1] if whole else torch.empty(b1 - b0, k1 - k0, 8, device=pred.device, dtype=torch.int64)
+                cf = sf[b0:b1] if whole else torch.empty(b1 - b0, k1 - k0, 2, device=pred.device, dtype=torch.float64)
+                hip.surface_dist(pred[b0:b1], target[b0:b1], self.n, self.classes[k0:k1], ws, ci, cf)
+                if not whole:
+                    si[b0:b1, k0:k1], sf[b0:b1, k0:k1] = ci, cf
+        self._si.append(si)
+        self._sf.append(sf)
+
+    def add_raw(self, stats_i, stats_f):
+        """Append raw statistics ([N, len(classes), 8] int64, [N, len(classes), 2] float64), e.g. another rank's raw()."""
+        nk = len(self.classes)
+        if tuple(stats_i.shape[1:]) != (nk, 8) or tuple(stats_f.shape[1:]) != (nk, 2) or stats_i.shape[0] != stats_f.shape[0]:
+            raise ValueError("SurfaceDistanceMeter.add_raw: shapes %s, %s" % (tuple(stats_i.shape), tuple(stats_f.shape)))
+        self._si.append(stats_i.to(self.device, torch.int64))
+        self._sf.append(stats_f.to(self.device, torch.float64))
+
+    def raw(self):
+        """The raw statistics so far, in update order: int64 [N, len(classes), 8] (fields RAW_I) and float64 [N, len(classes), 2]
+        (the sums of sqrt(D2(P -> T)) and sqrt(D2(T -> P))), on the meter's device."""
+        nk = len(self.classes)
+        if not self._si:
+            return (torch.zeros(0, nk, 8, device=self.device, dtype=torch.int64),
+                    torch.zeros(0, nk, 2, device=self.device, dtype=torch.float64))
+        return torch.cat(self._si), torch.cat(self._sf)
+
+    def compute(self):
+        """{'classes', 'hd', 'hd95', 'assd', 'rvd', 'rvd_total', 'valid', 'empty_pred', 'empty_target', 'empty_both': per class;
+        'mean_hd', 'mean_hd95', 'mean_assd': nanmean over classes; 'per_sample': {'hd', 'hd95', 'assd', 'rvd'} as float64
+        [N, len(classes)] arrays, nan on pairs that are not scored}."""
+        si, sf = self.raw()
+        return surface_metrics(si.cpu().numpy(), sf.cpu().numpy(), self.classes, self.spacing)
+
+
+def surface_metrics(si, sf, classes, spacing=1.0):
+    """SurfaceDistanceMeter.compute() of raw statistics si [N, nk, 8] int64, sf [N, nk, 2] float64 (numpy, float64 throughout)."""
+    si, sf = np.asarray(si, dtype=np.int64), np.asarray(sf, dtype=np.float64)
+    n_p, n_t, b_p, b_t, m_pt, m_tp, d_lo, d_hi = (si[..., i] for i in range(8))
+    valid = (n_p > 0) & (n_t > 0)
+    nan = np.full(valid.shape, np.nan)
+    n = np.where(valid, b_p + b_t, 1)
+    rem = (95 * (n - 1)) % 100                                   # the rank arithmetic is integer: lo = 95 (n - 1) // 100
+    v_lo, v_hi = np.sqrt(d_lo.astype(np.float64)), np.sqrt(d_hi.astype(np.float64))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        hd = np.where(valid, np.sqrt(np.maximum(m_pt, m_tp).astype(np.float64)), nan) * spacing
+        hd95 = np.where(valid, v_lo + (v_hi - v_lo) * rem / 100, nan) * spacing
+        assd = np.where(valid, (sf[..., 0] / b_p + sf[..., 1] / b_t) / 2, nan) * spacing
+        rvd = np.where(n_t > 0, (n_p - n_t) / n_t.astype(np.float64), 0.0)
+        sp, st = n_p.sum(0), n_t.sum(0)
+        rvd_total = np.where(st > 0, (sp - st) / st.astype(np.float64), 0.0)
+
+    def mean0(a):                                                # nanmean over samples, nan (and no warning) for an empty column
+        ok = ~np.isnan(a)
+        cnt = ok.sum(0)
+        return np.where(cnt > 0, np.where(ok, a, 0.0).sum(0) / np.maximum(cnt, 1), np.nan)
+
+    def mean_all(v):
+        v = np.asarray(v, dtype=np.float64)
+        return float(v[~np.isnan(v)].mean()) if (~np.isnan(v)).any() else float("nan")
+
+    out = {"classes": list(classes), "hd": mean0(hd).tolist(), "hd95": mean0(hd95).tolist(), "assd": mean0(assd).tolist(),
+           "rvd": mean0(rvd).tolist(), "rvd_total": rvd_total.tolist(), "valid": valid.sum(0).tolist(),
+           "empty_pred": ((n_p == 0) & (n_t > 0)).sum(0).tolist(), "empty_target": ((n_p > 0) & (n_t == 0)).sum(0).tolist(),
+           "empty_both": ((n_p == 0) & (n_t == 0)).sum(0).tolist(),
+           "per_sample": {"hd": hd, "hd95": hd95, "assd": assd, "rvd": rvd}}
+    for k in ("hd", "hd95", "assd"):
+        out["mean_" + k] = mean_all(out[k])
+    return out
 
 
 def evaluator_metrics(cm):
