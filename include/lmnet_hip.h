@@ -650,6 +650,60 @@ int64_t lmn_surface_workspace(int B, int nk, int H, int W);
 int lmn_surface_dist(const float* pred_logits, const int64_t* pred_labels, const int64_t* target, int B, int C, int H, int W,
                      const int32_t* classes, int nk, void* workspace, int64_t ws_bytes, int64_t* stats_i, double* stats_f,
                      lmn_stream_t stream);
+/* (additive to ABI 15: new symbols only) Post-processing of predictions, the device half of lm_net_amd.post.DevicePostprocess: what
+ * the reference's --test and --visualization modes do on the host after .cpu() (train.py:139-145, 182-197; arg-max, numpy and the
+ * np.where painting of utils/train_eval_utils.py:203-221), plus the connected-component cleaning every user adds behind it.
+ * Integer arithmetic only; two calls on one input give bit-identical outputs.  None of these entries is recorded by plans.
+ * lmn_post_workspace: bytes of scratch lmn_post_clean needs for B samples of H x W pixels (host arithmetic: two uint8 label maps,
+ * an int32 root and an int32 area per pixel, one 64-bit slot per sample and class); -1 and lmn_last_error when B is outside
+ * [1, 65535] or a side outside [2, 1024].
+ * lmn_cc_label: connected components of uint8 label maps [B,H,W] (device), connectivity 4 or 8, every label value partitioned
+ * (0 included).  roots [B,H,W] int32: the smallest row-major index y * W + x of the pixel's component; areas [B,H,W] int32: the
+ * component's pixel count at its root pixel, 0 elsewhere.  The labelling runs inside roots and areas themselves: workspace is not
+ * used at present and may be NULL.  One memset and three kernels on `stream` (tile pass in LDS, seam pass, flatten pass).    */
+int64_t lmn_post_workspace(int B, int H, int W);
+int lmn_cc_label(const uint8_t* labels, int B, int H, int W, int connectivity, void* workspace, int64_t ws_bytes, int32_t* roots,
+                 int32_t* areas, lmn_stream_t stream);
+/* Cleaning parameters of lmn_post_clean, read on the HOST at the call and passed to the kernels by value (no device copy).     */
+typedef struct {
+  int32_t connectivity;        /* 4 or 8: of the class components; holes use the dual (8 or 4)                                   */
+  int32_t hole_limit;          /* 0: no hole filling; otherwise the largest hole area that is filled (INT32_MAX: every hole)    */
+  uint64_t class_mask;         /* bit k: class k is cleaned (bit 0 must be clear: background is never removed)                  */
+  uint64_t keep_largest_mask;  /* bit k: only the largest component of class k survives (ties: the smallest root); a subset     */
+  int32_t min_area[64];        /* class k: components with fewer pixels do not survive                                          */
+} lmn_post_param_t;
+int lmn_sizeof_post_param(void);
+/* lmn_post_clean: the prediction is EXACTLY ONE of logits [B,C,H,W] fp32 (arg-max over C, first maximum wins as lmn_confusion),
+ * labels_u8 [B,H,W] uint8 or labels_i64 [B,H,W] int64 (device; values outside [0, C) count as background 0) -> L0.
+ *   L1 = L0 without the components (params->connectivity) of the cleaned classes that fail keep_largest or min_area;
+ *   L2 = L1 with its holes filled: a hole is a component of label 0 under the dual connectivity with no pixel on the image frame
+ *        and at most hole_limit pixels; its pixels take the label of the pixel left of its root pixel.
+ * labels_out [B,H,W] uint8 = L2.  stats [B][C][4] int32 (zeroed here): components of class k in L0, components of class k that
+ * survive, pixels of class k in L2, and for k = 0 the number of holes filled (0 for k > 0).  Two labellings when hole_limit > 0.
+ * With class_mask = 0 and hole_limit = 0 stats (and workspace) may be NULL: the entry then only writes L0 into labels_out (one
+ * kernel, no labelling), which is what lmn_cc_label takes.                                                                       */
+int lmn_post_clean(const float* logits, const uint8_t* labels_u8, const int64_t* labels_i64, int B, int C, int H, int W,
+                   const lmn_post_param_t* params, void* workspace, int64_t ws_bytes, uint8_t* labels_out, int32_t* stats,
+                   lmn_stream_t stream);
+/* lmn_post_render: label maps at network size back to the frames they came from, and painted over them (one kernel per 64
+ * samples, no frame-size intermediate).  src_hw: HOST int32 [B][2], the valid size (h, w) of sample b inside the padded Hs x Ws
+ * frame (the lmn_augment_u8 convention), or NULL = Hs x Ws; Hs, Ws < 32768.  For y < h, x < w:
+ *   labels_out[b][y][x] = labels_net[b][min(floor(y * (H / h)), H - 1)][min(floor(x * (W / w)), W - 1)], quotient and product in
+ *   double: the INTER_NEAREST arithmetic of lmn_preprocess_u8 with source and destination exchanged; 0 outside the valid area.
+ * overlay [B,Hs,Ws,3] uint8 from frames [B,Hs,Ws,channels] uint8 (channels 3, or 1 replicated): a painted pixel of class k becomes
+ *   ((256 - alpha256) * pixel + alpha256 * palette[k] + 128) >> 8 per channel (alpha256 = 256: the colour itself, the np.where of
+ *   train_eval_utils.py:217-219), every other valid pixel is the frame's, outside the valid area 0.  Class 0 is never painted.
+ *   mode 0 paints every pixel of a class, mode 1 only those with a 4-neighbour of another label at frame resolution (outside the
+ *   valid area counts as another label).  palette: HOST uint8 [C][3].  labels_out or overlay may be NULL (frames and palette are
+ *   needed only with overlay).  frames, labels_out and overlay must be 16-byte aligned.                                          */
+int lmn_post_render(const uint8_t* labels_net, int B, int H, int W, const int32_t* src_hw, int Hs, int Ws, const uint8_t* frames,
+                    int channels, const uint8_t* palette, int C, int alpha256, int mode, uint8_t* labels_out, uint8_t* overlay,
+                    lmn_stream_t stream);
+/* lmn_confusion with the arg-max already taken: pred_labels [B,HW] uint8 (e.g. a cleaned label map), counts[t*C + p] += #pixels
+ * with label t and prediction p (train_eval_utils.py:78-95 on a label map); pixels whose label or prediction is outside [0, C)
+ * are dropped.  Float counts: exact up to 2^24 per cell and call.                                                                */
+int lmn_confusion_labels(const uint8_t* pred_labels, const int64_t* target, int B, int C, int64_t HW, float* counts,
+                         lmn_stream_t stream);
 /* One AdamW step over flat buffers of n floats (n % 4 == 0): replaces torch.optim.AdamW.step() of
  * train.py:156 when parameters and gradients live in the flat layout of lm_net_amd.LM_Net.
  * bias_corr1 = 1 - beta1^t, bias_corr2 = 1 - beta2^t (t = step count, from the host). */

@@ -5,6 +5,7 @@
 Around the path (SURVEY.md section 8f "next" rows): ``lm_net_amd.loss.SegLoss`` (fused CE + Dice),
 ``lm_net_amd.optim.FusedAdamW`` (one-launch AdamW), ``lm_net_amd.metrics.ConfusionMeter`` (on-device Dice / IoU),
 ``lm_net_amd.metrics.SurfaceDistanceMeter`` (on-device HD / HD95 / ASSD / RVD),
+``lm_net_amd.post.DevicePostprocess`` (on-device arg-max, connected-component cleaning, resize back to the frame, overlay),
 ``lm_net_amd.ddp.DistributedLMNet`` (bucketed RCCL gradient all-reduce).
 """
 from .LM_Net import LM_Net  # noqa: F401

@@ -138,6 +138,12 @@ class AugParam(C.Structure):
                 ("h", C.c_int32), ("w", C.c_int32), ("apply_ssr", C.c_int32), ("apply_cj", C.c_int32), ("flips", C.c_int32),
                 ("order", C.c_int32 * 4), ("_pad", C.c_int32)]
 
+
+class PostParam(C.Structure):
+    """Mirror of lmn_post_param_t: the cleaning parameters of lmn_post_clean (lm_net_amd.post.DevicePostprocess)."""
+    _fields_ = [("connectivity", C.c_int32), ("hole_limit", C.c_int32), ("class_mask", C.c_uint64), ("keep_largest_mask", C.c_uint64),
+                ("min_area", C.c_int32 * 64)]
+
 # every symbol include/lmnet_hip.h declares (the CPU test suite checks the library exports all of them)
 SYMBOLS = [
     "lmn_abi_version", "lmn_sizeof_conv_args", "lmn_sizeof_src", "lmn_sizeof_wgrad_args", "lmn_last_error",
@@ -147,7 +153,7 @@ SYMBOLS = [
     "lmn_se_fwd", "lmn_se_bwd", "lmn_se_bwd_dm", "lmn_se_bwd_params", "lmn_na_fwd", "lmn_na_bwd", "lmn_plan_host_profile", "lmn_set_deterministic", "lmn_get_deterministic", "lmn_gattn_fwd", "lmn_gattn_bwd",
     "lmn_ln_fwd", "lmn_ln_bwd", "lmn_bnact_fwd", "lmn_bnact_bwd_stats", "lmn_bnact_bwd",
     "lmn_bn_finalize", "lmn_bn_fold", "lmn_bn_bwd_coef", "lmn_up2_fwd", "lmn_up2_bwd", "lmn_avgpool_fwd", "lmn_avgpool_bwd",
-    "lmn_nchw_to_nhwc", "lmn_nhwc_to_nchw", "lmn_adamw_step", "lmn_segloss_fwd", "lmn_segloss_bwd", "lmn_confusion", "lmn_preprocess_u8", "lmn_preprocess_u8_ex", "lmn_sizeof_aug_param", "lmn_augment_u8", "lmn_surface_workspace", "lmn_surface_dist", "lmn_fill", "lmn_add", "lmn_colsum", "lmn_copy_slice", "lmn_copy2d",
+    "lmn_nchw_to_nhwc", "lmn_nhwc_to_nchw", "lmn_adamw_step", "lmn_segloss_fwd", "lmn_segloss_bwd", "lmn_confusion", "lmn_preprocess_u8", "lmn_preprocess_u8_ex", "lmn_sizeof_aug_param", "lmn_augment_u8", "lmn_surface_workspace", "lmn_surface_dist", "lmn_post_workspace", "lmn_cc_label", "lmn_sizeof_post_param", "lmn_post_clean", "lmn_post_render", "lmn_confusion_labels", "lmn_fill", "lmn_add", "lmn_colsum", "lmn_copy_slice", "lmn_copy2d",
     "lmn_stream_wait", "lmn_event_record", "lmn_event_wait", "lmn_set_priority_stream", "lmn_plan_create", "lmn_plan_destroy", "lmn_plan_record_begin", "lmn_plan_record_end", "lmn_plan_size",
     "lmn_plan_run", "lmn_prof_begin", "lmn_prof_end",
 ]
@@ -172,6 +178,7 @@ def load():
     lib.lmn_conv_pack_size.restype = C.c_int64
     lib.lmn_conv_wgrad_workspace.restype = C.c_int64
     lib.lmn_surface_workspace.restype = C.c_int64
+    lib.lmn_post_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -180,7 +187,7 @@ def load():
         raise RuntimeError("lm_net_amd: ABI version mismatch")
     if (lib.lmn_sizeof_conv_args() != C.sizeof(ConvArgs) or lib.lmn_sizeof_src() != C.sizeof(SrcT)
             or lib.lmn_sizeof_wgrad_args() != C.sizeof(WgradArgs) or lib.lmn_sizeof_reduce_job() != C.sizeof(ReduceJob)
-            or lib.lmn_sizeof_aug_param() != C.sizeof(AugParam)):
+            or lib.lmn_sizeof_aug_param() != C.sizeof(AugParam) or lib.lmn_sizeof_post_param() != C.sizeof(PostParam)):
         raise RuntimeError("lm_net_amd: argument struct layout differs between hip.py and lmnet_hip.h")
     _lib = lib
     return lib
@@ -982,6 +989,90 @@ def surface_dist(pred, target, n_classes, classes, workspace, stats_i, stats_f):
     _check(load().lmn_surface_dist(_p(logits), _pl(labels), _pl(target), B, int(n_classes), H, W, ids, nk,
                                    C.c_void_p(workspace.data_ptr()), _i64(workspace.numel()), C.c_void_p(stats_i.data_ptr()),
                                    C.c_void_p(stats_f.data_ptr()), _stream()), "surface_dist")
+
+
+def _raw(t, dt, what):
+    """device pointer of a contiguous tensor of dtype dt (None passes through)"""
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+        raise RuntimeError("lm_net_amd.%s: contiguous %s device tensor required" % (what, dt))
+    return C.c_void_p(t.data_ptr())
+
+
+def confusion_labels(pred, target, counts):
+    """counts[t*C + p] += pixels with label t and prediction p, for a uint8 label-map prediction [B,H,W] (lmn_confusion_labels)."""
+    B = pred.shape[0]
+    hw = pred.numel() // B
+    if target.numel() != pred.numel():
+        raise ValueError("lm_net_amd.confusion_labels: pred %s does not match target %s" % (tuple(pred.shape), tuple(target.shape)))
+    n = int(counts.shape[0])
+    _check(load().lmn_confusion_labels(_raw(pred, torch.uint8, "confusion_labels"), _pl(target), B, n, _i64(hw), _p(counts), _stream()),
+           "confusion_labels")
+
+
+def post_workspace(B, H, W):
+    """Bytes of scratch lmn_post_clean needs for B samples of H x W pixels (host arithmetic, no GPU)."""
+    n = int(load().lmn_post_workspace(int(B), int(H), int(W)))
+    if n < 0:
+        raise ValueError("lm_net_amd.post_workspace: " + load().lmn_last_error().decode())
+    return n
+
+
+def cc_label(labels, connectivity, roots, areas):
+    """Connected components of uint8 label maps [B,H,W] into int32 roots / areas [B,H,W] (lmn_cc_label)."""
+    B, H, W = labels.shape
+    if roots.numel() != labels.numel() or areas.numel() != labels.numel():
+        raise ValueError("lm_net_amd.cc_label: roots / areas do not match labels %s" % (tuple(labels.shape),))
+    _check(load().lmn_cc_label(_raw(labels, torch.uint8, "cc_label"), B, H, W, int(connectivity), None, _i64(0),
+                               _raw(roots, torch.int32, "cc_label"), _raw(areas, torch.int32, "cc_label"), _stream()), "cc_label")
+
+
+def post_clean(pred, n_classes, params, workspace, labels_out, stats):
+    """lmn_post_clean: pred = fp32 logits [B,C,H,W] or a uint8 / int64 label map [B,H,W]; params: PostParam (host); workspace uint8
+    of at least post_workspace(B, H, W) bytes; labels_out uint8 [B,H,W]; stats int32 [B,C,4].  With nothing cleaned or filled in params,
+    workspace and stats may be None: labels_out is then the arg-max / clamped map L0 alone (one kernel)."""
+    B, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]
+    logits = l8 = l64 = None
+    if pred.dim() == 4 and pred.dtype == torch.float32:
+        if pred.shape[1] != n_classes:
+            raise ValueError("lm_net_amd.post_clean: logits with %d channels, n_classes = %d" % (pred.shape[1], n_classes))
+        logits = _raw(pred, torch.float32, "post_clean")
+    elif pred.dim() == 3 and pred.dtype == torch.uint8:
+        l8 = _raw(pred, torch.uint8, "post_clean")
+    elif pred.dim() == 3 and pred.dtype == torch.int64:
+        l64 = _raw(pred, torch.int64, "post_clean")
+    else:
+        raise ValueError("lm_net_amd.post_clean: pred must be fp32 logits [B,C,H,W] or a uint8 / int64 label map [B,H,W]")
+    if labels_out.numel() != B * H * W or (stats is not None and stats.numel() != B * n_classes * 4):
+        raise ValueError("lm_net_amd.post_clean: output buffers do not match B=%d, C=%d, %dx%d" % (B, n_classes, H, W))
+    _check(load().lmn_post_clean(logits, l8, l64, B, int(n_classes), H, W, C.byref(params), _raw(workspace, torch.uint8, "post_clean"),
+                                 _i64(0 if workspace is None else workspace.numel()), _raw(labels_out, torch.uint8, "post_clean"),
+                                 _raw(stats, torch.int32, "post_clean"), _stream()), "post_clean")
+
+
+def post_render(labels_net, src_hw, Hs, Ws, frames, palette, n_classes, alpha256, mode, labels_out, overlay):
+    """lmn_post_render: labels_net uint8 [B,H,W] -> labels_out uint8 [B,Hs,Ws] and / or overlay uint8 [B,Hs,Ws,3] over frames uint8
+    [B,Hs,Ws,3] or [B,Hs,Ws(,1)].  src_hw: host int32 numpy [B,2] or None; palette: host uint8 numpy [C,3]."""
+    B, H, W = labels_net.shape
+    channels = 3
+    if frames is not None:
+        channels = 1 if frames.dim() == 3 else int(frames.shape[3])
+        if tuple(frames.shape[:3]) != (B, Hs, Ws) or channels not in (1, 3):
+            raise ValueError("lm_net_amd.post_render: frames %s do not match B=%d, %dx%d with 1 or 3 channels"
+                             % (tuple(frames.shape), B, Hs, Ws))
+    if ((labels_out is not None and labels_out.numel() != B * Hs * Ws) or (overlay is not None and overlay.numel() != B * Hs * Ws * 3)
+            or (src_hw is not None and tuple(src_hw.shape) != (B, 2))):
+        raise ValueError("lm_net_amd.post_render: buffers do not match B=%d, frame %dx%d" % (B, Hs, Ws))
+    hw_arr = None if src_hw is None else np.ascontiguousarray(src_hw, dtype=np.int32)
+    hw = None if hw_arr is None else hw_arr.ctypes.data_as(C.POINTER(C.c_int32))
+    pal = np.ascontiguousarray(palette, dtype=np.uint8)
+    if tuple(pal.shape) != (n_classes, 3):
+        raise ValueError("lm_net_amd.post_render: palette %s is not [%d, 3]" % (tuple(pal.shape), n_classes))
+    _check(load().lmn_post_render(_raw(labels_net, torch.uint8, "post_render"), B, H, W, hw, int(Hs), int(Ws),
+                                  _raw(frames, torch.uint8, "post_render"), channels, pal.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                  int(n_classes), int(alpha256), int(mode), _raw(labels_out, torch.uint8, "post_render"),
+                                  _raw(overlay, torch.uint8, "post_render"), _stream()), "post_render")
 
 
 def preprocess_u8(images, masks, flips, out, labels, mean, std):

@@ -30,10 +30,22 @@ class ConfusionMeter:
 
     @torch.no_grad()
     def update(self, logits, target):
+        """logits [B, C, H, W] (arg-max, first maximum wins) or an integer label map [B, H, W] (e.g. DevicePostprocess's labels_net;
+        predictions outside [0, C) are not counted)."""
         if not logits.is_cuda:
             raise RuntimeError("lm_net_amd.ConfusionMeter: device tensors required (the HIP path has no CPU fallback)")
         counts = torch.zeros(self.n, self.n, device=logits.device)      # exact: < 2^24 per cell and launch
-        hip.confusion(logits.contiguous().float(), target.contiguous().long(), counts)
+        if logits.dim() == 3 and logits.is_floating_point():
+            raise ValueError("ConfusionMeter: pred must be logits [B, C, H, W] or an INTEGER label map [B, H, W], got a 3-D %s tensor"
+                             % logits.dtype)
+        if logits.dim() == 3:
+            if logits.dtype in (torch.uint8, torch.bool):
+                pred = logits.to(torch.uint8)
+            else:
+                pred = logits.clamp(-1, 255).to(torch.uint8)      # (-1 -> 255: no class)
+            hip.confusion_labels(pred.contiguous(), target.contiguous().long(), counts)
+        else:
+            hip.confusion(logits.contiguous().float(), target.contiguous().long(), counts)
         self.total += counts.double()
 
     def compute(self):

@@ -1,0 +1,193 @@
+"""Post-processing of predictions on the device (the users of the deploy path).
+
+The reference's ``--test`` and ``--visualization`` modes take the arg-max, move it to the CPU and go on in numpy / cv2
+(``train.py:139-145, 182-197``, ``utils/train_eval_utils.py:203-221``).  ``DevicePostprocess`` keeps the whole output side on the
+GPU: arg-max -> connected-component cleaning (keep the largest component, drop small ones, fill holes) -> nearest resize back to the
+frame the input came from -> overlay.  Every quantity is an integer; two calls on one input give bit-identical outputs.
+
+Semantics, per sample, with L0 the uint8 label map after arg-max (first maximum wins) / clamping (values outside [0, C) -> 0):
+
+1. Components: pixels joined by a path of ``connectivity``-neighbour steps (4 or 8) through pixels of equal label; every label, 0
+   included, is partitioned.  A component's root is the smallest row-major index ``y * W + x`` of its pixels.
+2. Cleaning, for each class k in ``classes``: with ``keep_largest`` only the class-k component of largest area survives (equal
+   areas: the smallest root); a component of area < ``min_area`` does not survive.  Pixels of the others become 0 -> L1.
+3. Hole filling on L1: a component of label 0 under the DUAL connectivity (4 for 8, 8 for 4) with no pixel on the image frame and an
+   area within the limit is a hole; its pixels take the label of the pixel left of its root pixel -> L2 = ``labels_net``.
+4. ``stats[b, k]`` = (components of class k in L0, components of class k that survive, pixels of class k in L2, holes filled for
+   k = 0 and 0 otherwise).
+5. ``labels[b, y, x] = L2[b, min(floor(y * (H / hs)), H - 1), min(floor(x * (W / ws)), W - 1)]`` for y < hs, x < ws, in double:
+   the INTER_NEAREST arithmetic of ``lmn_preprocess_u8`` with source and destination exchanged; 0 outside the valid area.
+6. Overlay: ``a = round(alpha * 256)``; a painted pixel of class k becomes ``((256 - a) * pixel + a * palette[k] + 128) >> 8`` per
+   channel.  Class 0 is never painted.  ``"fill"`` paints every pixel of a class, ``"contour"`` only pixels of the frame-resolution
+   label map with a 4-neighbour of another label (outside the valid area counts as another label).
+
+Default palette (in the frame's channel order, as the reference applies its colours to the array it has): classes 1, 2, 3 =
+(0, 0, 255), (0, 255, 0), (255, 0, 0), the reference's three; every other class k the PASCAL-VOC colour-map rule: bit j of the
+red / green / blue byte, counted from the top, is bit 3j / 3j + 1 / 3j + 2 of k.
+"""
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import hip
+
+PostOutput = namedtuple("PostOutput", ["labels_net", "labels", "overlay", "stats"])
+
+_INT32_MAX = 2 ** 31 - 1
+
+
+def alpha256(alpha):
+    """round(alpha * 256), halves up, for alpha in [0, 1]."""
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("DevicePostprocess: alpha = %r outside [0, 1]" % alpha)
+    return int(math.floor(alpha * 256.0 + 0.5))
+
+
+def default_palette(n_classes):
+    """uint8 [n_classes, 3]: the module docstring's rule."""
+    pal = np.zeros((n_classes, 3), np.uint8)
+    for k in range(n_classes):
+        v, rgb = k, [0, 0, 0]
+        for j in range(8):
+            for c in range(3):
+                rgb[c] |= ((v >> c) & 1) << (7 - j)
+            v >>= 3
+        pal[k] = rgb
+    for k, colour in ((1, (0, 0, 255)), (2, (0, 255, 0)), (3, (255, 0, 0))):
+        if k < n_classes:
+            pal[k] = colour
+    return pal
+
+
+class DevicePostprocess:
+    """post(pred, src_hw=None, frames=None) -> PostOutput(labels_net, labels, overlay, stats); see the module docstring.
+
+    pred: fp32 logits [B, C, H, W] or an integer label map [B, H, W] (uint8 or int64), 2 <= H, W <= 1024, on the device.
+    src_hw: host [B, 2] or (h, w): each sample's valid size inside the padded [B, Hs, Ws, ...] frame buffer (the DeviceAugment
+    convention); without frames, Hs, Ws = the largest h and w.  frames: uint8 [B, Hs, Ws, 3] or [B, Hs, Ws(, 1)] (replicated), Hs, Ws
+    < 32768 (a view that is not contiguous or not 16-byte aligned is copied first).  labels is None without src_hw and frames, overlay
+    is None without frames.
+
+    No host synchronisation; every launch goes to the caller's current stream.  The cleaning parameters, src_hw and the palette are
+    read on the host at the call and travel as kernel arguments (no host-to-device copy), so a call may be captured into a
+    torch.cuda.graph; the capture then holds the parameters and src_hw of the captured call.  Not recorded by plans."""
+
+    def __init__(self, n_classes, connectivity=8, classes=None, keep_largest=False, min_area=0, fill_holes=False, palette=None,
+                 alpha=1.0, overlay="fill"):
+        if not 2 <= n_classes <= 64:
+            raise ValueError("DevicePostprocess: n_classes = %d outside [2, 64]" % n_classes)
+        if connectivity not in (4, 8):
+            raise ValueError("DevicePostprocess: connectivity %r is neither 4 nor 8" % (connectivity,))
+        classes = list(range(1, n_classes)) if classes is None else [int(k) for k in classes]
+        if len(set(classes)) != len(classes) or any(not 1 <= k < n_classes for k in classes):
+            raise ValueError("DevicePostprocess: classes %r must be distinct ids in [1, %d) (background is never removed)"
+                             % (classes, n_classes))
+        if isinstance(keep_largest, (bool, np.bool_)):
+            largest = list(classes) if keep_largest else []
+        else:
+            largest = [int(k) for k in keep_largest]
+            if any(k not in classes for k in largest):
+                raise ValueError("DevicePostprocess: keep_largest %r names a class outside classes %r" % (largest, classes))
+        if isinstance(min_area, (int, np.integer)):
+            areas = {k: int(min_area) for k in classes}
+        else:
+            if len(min_area) != len(classes):
+                raise ValueError("DevicePostprocess: min_area needs one entry per class in classes (%d)" % len(classes))
+            areas = {k: int(a) for k, a in zip(classes, min_area)}
+        if any(a < 0 or a > _INT32_MAX for a in areas.values()):
+            raise ValueError("DevicePostprocess: min_area must be in [0, 2^31)")
+        if isinstance(fill_holes, (bool, np.bool_)):
+            hole_limit = _INT32_MAX if fill_holes else 0
+        else:
+            hole_limit = int(fill_holes)
+            if not 0 <= hole_limit <= _INT32_MAX:
+                raise ValueError("DevicePostprocess: fill_holes = %r: a bool or a maximal hole area in [0, 2^31)" % (fill_holes,))
+        if overlay not in ("fill", "contour"):
+            raise ValueError("DevicePostprocess: overlay %r is neither 'fill' nor 'contour'" % (overlay,))
+        pal = default_palette(n_classes) if palette is None else np.asarray(palette)
+        if pal.shape != (n_classes, 3) or (palette is not None and (pal.min() < 0 or pal.max() > 255)):
+            raise ValueError("DevicePostprocess: palette of shape %s, [%d, 3] values in [0, 255] required" % (pal.shape, n_classes))
+        self.n, self.connectivity, self.classes, self.keep_largest = n_classes, connectivity, classes, largest
+        self.min_area, self.hole_limit = areas, hole_limit
+        self.palette = np.ascontiguousarray(pal, dtype=np.uint8)
+        self.alpha256, self.mode = alpha256(alpha), 0 if overlay == "fill" else 1
+        self.params = hip.PostParam()
+        self.params.connectivity, self.params.hole_limit = connectivity, hole_limit
+        self.params.class_mask = sum(1 << k for k in classes)
+        self.params.keep_largest_mask = sum(1 << k for k in largest)
+        for k, a in areas.items():
+            self.params.min_area[k] = a
+
+    def _pred(self, pred, what):
+        if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+            raise RuntimeError("lm_net_amd.DevicePostprocess%s: device tensors required (the HIP path has no CPU path)" % what)
+        if pred.dim() == 4 and pred.is_floating_point():
+            if pred.shape[1] != self.n:
+                raise ValueError("DevicePostprocess: logits with %d channels, n_classes = %d" % (pred.shape[1], self.n))
+            pred = pred.contiguous().float()
+        elif pred.dim() == 3 and pred.dtype in (torch.uint8, torch.int64):
+            pred = pred.contiguous()
+        else:
+            raise ValueError("DevicePostprocess: pred must be logits [B, C, H, W] or a uint8 / int64 label map [B, H, W]")
+        B, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]
+        if B < 1 or not (2 <= H <= 1024 and 2 <= W <= 1024):
+            raise ValueError("DevicePostprocess: B=%d, %dx%d outside B >= 1, sides in [2, 1024]" % (B, H, W))
+        return pred, B, H, W
+
+    @torch.no_grad()
+    def components(self, pred):
+        """(roots, areas), int32 [B, H, W] each: the labelling of L0 under ``connectivity``.  roots = the root of the pixel's
+        component, areas = the component's pixel count at its root pixel and 0 elsewhere."""
+        pred, B, H, W = self._pred(pred, ".components")
+        dev = pred.device
+        prm = hip.PostParam()                                   # L0 alone: arg-max / clamping, one kernel, nothing cleaned
+        prm.connectivity = self.connectivity
+        lab = torch.empty(B, H, W, device=dev, dtype=torch.uint8)
+        hip.post_clean(pred, self.n, prm, None, lab, None)
+        roots = torch.empty(B, H, W, device=dev, dtype=torch.int32)
+        areas = torch.empty(B, H, W, device=dev, dtype=torch.int32)
+        hip.cc_label(lab, self.connectivity, roots, areas)
+        return roots, areas
+
+    @torch.no_grad()
+    def __call__(self, pred, src_hw=None, frames=None):
+        pred, B, H, W = self._pred(pred, "")
+        dev = pred.device
+        hw = None
+        if src_hw is not None:
+            hw = np.asarray(src_hw.cpu() if isinstance(src_hw, torch.Tensor) else src_hw, dtype=np.int64)
+            if hw.shape == (2,):
+                hw = np.broadcast_to(hw, (B, 2))
+            if hw.shape != (B, 2) or hw.min() < 1 or hw.max() >= 32768:
+                raise ValueError("DevicePostprocess: src_hw must be (h, w) or [B=%d, 2] with 1 <= h, w < 32768" % B)
+            hw = np.ascontiguousarray(hw, dtype=np.int32)
+        if frames is not None:
+            if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+                raise RuntimeError("lm_net_amd.DevicePostprocess: device tensors required (the HIP path has no CPU path)")
+            if (frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[0] != B
+                    or (frames.dim() == 4 and frames.shape[3] not in (1, 3))):
+                raise ValueError("DevicePostprocess: frames must be uint8 [B=%d, Hs, Ws, 3] or [B, Hs, Ws(, 1)]" % B)
+            frames = frames.contiguous()
+            if frames.data_ptr() % 16:                          # (a view with a storage offset: the render kernel loads 16 bytes)
+                frames = frames.clone()
+            Hs, Ws = int(frames.shape[1]), int(frames.shape[2])
+            if not (1 <= Hs < 32768 and 1 <= Ws < 32768):
+                raise ValueError("DevicePostprocess: frame size %dx%d outside [1, 32767]" % (Hs, Ws))
+            if hw is not None and (hw[:, 0].max() > Hs or hw[:, 1].max() > Ws):
+                raise ValueError("DevicePostprocess: src_hw exceeds the %dx%d frames" % (Hs, Ws))
+        elif hw is not None:
+            Hs, Ws = int(hw[:, 0].max()), int(hw[:, 1].max())
+        labels_net = torch.empty(B, H, W, device=dev, dtype=torch.uint8)
+        stats = torch.empty(B, self.n, 4, device=dev, dtype=torch.int32)
+        ws = torch.empty(hip.post_workspace(B, H, W), device=dev, dtype=torch.uint8)
+        hip.post_clean(pred, self.n, self.params, ws, labels_net, stats)
+        labels = overlay = None
+        if frames is not None or hw is not None:
+            labels = torch.empty(B, Hs, Ws, device=dev, dtype=torch.uint8)
+            if frames is not None:
+                overlay = torch.empty(B, Hs, Ws, 3, device=dev, dtype=torch.uint8)
+            hip.post_render(labels_net, hw, Hs, Ws, frames, self.palette, self.n, self.alpha256, self.mode, labels, overlay)
+        return PostOutput(labels_net, labels, overlay, stats)
