@@ -29,6 +29,10 @@ def dev(t):
     return t.to(torch.float32).to(DEV).contiguous()
 
 
+def bf(t):  # fp32 device tensor -> its bf16-storage form
+    return t.to(torch.bfloat16)
+
+
 def rel(got, ref):
     got = got.detach().double().cpu()
     ref = ref.detach().double().cpu()
@@ -829,7 +833,6 @@ def check_fused_sources_modes():
     against the UNFUSED kernels of the same mode at tight tolerances (the model-level bf16 tolerances cannot see a 1 % single-block
     error), plus LayerNorm rows whose channel 0 is far from the row mean (the M-split pre-pass sums about channel 0)."""
     rows = []
-    bf = lambda t: t.to(torch.bfloat16)
     # ---- LayerNorm rows with an outlier in channel 0 (fp32): N-split (12, 24), M-split pre-pass (48, 96, 372)
     for Cn, Co, n in ((12, 36, 77), (24, 48, 130), (48, 96, 257), (96, 192, 64), (372, 744, 50)):
         x = R(n, Cn, seed=161) * 0.7 + 0.2
@@ -1602,7 +1605,6 @@ def check_bf16_storage_rows():
     element; statistics, weight and bias-table gradients stay fp32: 2e-4 / float-atomic noise) -- a wrong element size in an address
     computation or a mis-paired half cannot hide behind the model-level bf16 tolerances."""
     rows = []
-    bf = lambda t: t.to(torch.bfloat16)
     # ---- depthwise passes (row-planar tensors)
     for (B, H, W, E) in [(2, 20, 19, 24), (1, 33, 61, 8), (1, 9, 130, 16)]:
         x1 = R(B, E, H, W, seed=301).to(torch.bfloat16).double()
