@@ -610,7 +610,7 @@ typedef struct {
 int lmn_sizeof_aug_param(void);
 /* (additive to ABI 15) The per-sample part of the training transform (dataset/data_loading.py:207-216) on the device:
  * RandomResizedCrop (:208) -> ShiftScaleRotate(BORDER_CONSTANT) (:210-211) -> HorizontalFlip / VerticalFlip (:212-213) ->
- * ColorJitter (:214) -> Normalize + ToTensorV2 (:227-228); the OneOf block (:215-225) stays on the CPU.  Two kernels on `stream`:
+ * ColorJitter (:214) -> Normalize + ToTensorV2 (:227-228); the OneOf block (:215-225): lmnet_oneof.h.  Two kernels on `stream`:
  *   1. geometry: per output pixel, undo the flips, map through iM with cv2.warpAffine's fixed-point arithmetic (AB_BITS 10,
  *      INTER_BITS 5, border 0) and blend the four neighbours of the crop-resized frame with the 32768-scale remap weights; each
  *      neighbour is cv2.resize INTER_LINEAR of the crop window computed straight from the raw frame (the lmn_preprocess_u8

@@ -1,0 +1,81 @@
+/* The OneOf block of the training augmentations (dataset/data_loading.py:215-225) on the device: the entries of liblmnet_hip.so
+ * behind lm_net_amd.data.DeviceAugment(one_of=...).  Kept apart from lmnet_hip.h, whose declarations are frozen at ABI 15 by the
+ * export and guard-manifest checks; these symbols are additive, listed in lm_net_amd.hip.SYMBOLS_ONEOF and guarded by
+ * tests/test_guard_oneof_gpu.py.                                                                                              */
+#ifndef LMNET_ONEOF_H
+#define LMNET_ONEOF_H
+#include "lmnet_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* members of the block (lmn_oneof_param_t.op); NONE: the block did not fire for this sample */
+#define LMN_ONEOF_NONE 0
+#define LMN_ONEOF_TO_GRAY 1          /* channels 3 */
+#define LMN_ONEOF_GRID_DISTORTION 2
+#define LMN_ONEOF_ELASTIC 3
+#define LMN_ONEOF_CLAHE 4
+#define LMN_ONEOF_HSV 5              /* channels 3 */
+#define LMN_ONEOF_CHANNEL_SHUFFLE 6  /* channels 3 */
+#define LMN_ONEOF_GRID_DROPOUT 7
+#define LMN_ONEOF_RGB_SHIFT 8        /* channels 3 */
+#define LMN_ONEOF_GAUSSIAN_BLUR 9
+#define LMN_ONEOF_NOPS 10
+
+#define LMN_ONEOF_MAX_RADIUS 4096    /* elastic: taps on each side of the Gaussian */
+/* 8-bit LAB tables (lm_net_amd.data.lab_tables builds them once, in double): offsets into one int32 array */
+#define LMN_LAB_GAMMA 0       /* [256]  sRGB byte -> linear, scale 2040                                                    */
+#define LMN_LAB_CBRT 256      /* [3072] f(t / 2040) of CIE LAB, scale 2^15                                                  */
+#define LMN_LAB_FY 3328       /* [256]  L8 -> fy, scale 2^15                                                                */
+#define LMN_LAB_DA 3584       /* [256]  a8 -> fx - fy, scale 2^15                                                           */
+#define LMN_LAB_DB 3840       /* [256]  b8 -> fy - fz, scale 2^15                                                           */
+#define LMN_LAB_FWD 4096      /* [9]    RGB -> XYZ / white, scale 2^12, every row sums to 4096                              */
+#define LMN_LAB_INV 4105      /* [9]    XYZ / white -> RGB, scale 2^12                                                      */
+#define LMN_LAB_INVGAMMA 4128 /* [16385] linear, scale 2^14 -> sRGB byte                                                    */
+#define LMN_LAB_TABLE_INTS 20513
+
+/* One sample's member and its drawn values.  `tables` offsets count floats from the start of the host table array.       */
+typedef struct {
+  int32_t op;        /* LMN_ONEOF_*                                                                                          */
+  int32_t k;         /* gaussian_blur: kernel size 3, 5 or 7                                                                 */
+  int32_t perm[3];   /* channel_shuffle: out[c] = in[perm[c]]                                                                */
+  int32_t unit;      /* grid_dropout: cell size (both axes), >= 2                                                            */
+  int32_t hole;      /* grid_dropout: x % unit < hole && y % unit < hole -> 0; 1 <= hole < unit                               */
+  int32_t radius;    /* elastic: taps on each side, 0..LMN_ONEOF_MAX_RADIUS                                                    */
+  int32_t slot;      /* elastic: index of this sample among the batch's elastic samples, 0..n_elastic-1, each used once      */
+  int32_t _pad;
+  int64_t tab_off;   /* grid_distortion: xx[W] then yy[H]; elastic: weights[2 radius + 1] then noise[2][H][W]                 */
+  double v[3];       /* rgb_shift: (r, g, b) shift; hsv: (hue, sat, val) shift; clahe: v[0] clip; elastic: v[0] alpha, v[1] sigma */
+} lmn_oneof_param_t;
+int lmn_sizeof_oneof_param(void);
+
+/* Bytes of `workspace` for a batch with n_elastic elastic samples (host arithmetic only): the CLAHE look-up tables of every
+ * sample (64 tiles x 256 bytes) and 4 H W floats per elastic sample (the row-blurred and the finished displacement fields). */
+int64_t lmn_oneof_workspace(int B, int H, int W, int channels, int n_elastic);
+
+/* lmn_augment_u8 with the OneOf block between ColorJitter and Normalize.  The arguments of lmn_augment_u8 keep their meaning;
+ * in addition:
+ *   oneof [B] HOST, checked before any launch (op id, members that need channels 3, k, permutation, grid, radius, sigma > 0,
+ *     table offsets inside n_tables, slots) and copied to oneof_dev (device, B structs) on `stream`;
+ *   tables HOST float [n_tables] (may be NULL when n_tables is 0), copied to tables_dev (device, n_tables floats) on `stream`;
+ *   lab_tables DEVICE int32 [LMN_LAB_TABLE_INTS]: required when a sample draws clahe with channels 3;
+ *   scratch2 [B,H,W,channels] uint8: the colour-jittered bytes (needed with images);
+ *   labels_tmp [B,H,W] int64: needed with masks when a sample draws grid_distortion or elastic;
+ *   workspace: at least lmn_oneof_workspace(B, H, W, channels, n_elastic) bytes, 256-byte aligned.
+ * Kernels: geometry -> ColorJitter (uint8 out) -> [gaussian_blur] [clahe: tables, apply] [elastic: row blur, column blur]
+ * [grid_distortion / elastic remap, label copy] -> pointwise members + Normalize: at most 10 launches whatever B.  A sample with op NONE
+ * comes out bit-identical to lmn_augment_u8.  No stream synchronisation, no device allocation (the copies from pageable host
+ * memory hold the host for their staging); not recorded by plans; keep `params`, `oneof` and `tables` alive until the stream
+ * has passed the call.                                                 */
+int lmn_augment_oneof_u8(const uint8_t* images, const uint8_t* masks, const lmn_aug_param_t* params, const int32_t* src_hw,
+                         lmn_aug_param_t* params_dev, int B, int Hs, int Ws, int H, int W, int channels, int mask_mode,
+                         const double* mean, const double* std, uint8_t* scratch, uint64_t* gray_sum, float* out, int64_t* labels,
+                         const lmn_oneof_param_t* oneof, lmn_oneof_param_t* oneof_dev, const float* tables, int64_t n_tables,
+                         float* tables_dev, const int32_t* lab_tables, uint8_t* scratch2, int64_t* labels_tmp, void* workspace,
+                         int64_t workspace_bytes, lmn_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -8,8 +8,9 @@ layout change for a whole batch of raw uint8 frames already in HBM as ONE kernel
 frames can go to the GPU as bytes (3 B/pixel over PCIe instead of 12) and an 8-GPU loop is not fed by a CPU
 albumentations pool.  `DeviceAugment` runs the per-sample part of the training transform (`:207-214`, `:227-228`):
 RandomResizedCrop -> ShiftScaleRotate -> HorizontalFlip -> VerticalFlip -> ColorJitter -> Normalize, as two kernels
-(`lmn_augment_u8`) on parameters drawn on the host.  Only the `A.OneOf([...9 ops], p=0.4)` block (`:215-225`) stays on the
-CPU side (out of scope).
+(`lmn_augment_u8`) on parameters drawn on the host.  `DeviceAugment(one_of="reference")` adds the `A.OneOf([...9 ops], p=0.4)`
+block (`:215-225`) between ColorJitter and Normalize (`lmn_augment_oneof_u8`, include/lmnet_oneof.h): ToGray, GridDistortion,
+ElasticTransform, CLAHE, HueSaturationValue, ChannelShuffle, GridDropout, RGBShift and GaussianBlur, all on the device.
 """
 import ctypes
 import math
@@ -111,9 +112,203 @@ def pack_params(samples):
     return arr
 
 
+# ---------------------------------------------------------------- the OneOf block (dataset/data_loading.py:215-225)
+# member -> its settings and their albumentations defaults
+ONEOF_MEMBERS = {
+    "to_gray": {}, "grid_distortion": {"num_steps": 5, "distort_limit": 0.3}, "elastic": {"alpha": 1.0, "sigma": 50.0},
+    "clahe": {"clip_limit": (1.0, 4.0), "tile_grid": (8, 8)}, "hsv": {"hue": 20.0, "sat": 30.0, "val": 20.0}, "channel_shuffle": {},
+    "grid_dropout": {"ratio": 0.5}, "rgb_shift": {"r": 20.0, "g": 20.0, "b": 20.0}, "gaussian_blur": {"blur_limit": (3, 7)},
+}
+ONEOF_REFERENCE = ("to_gray", "grid_distortion", "elastic", "clahe", "hsv", "channel_shuffle", "grid_dropout", "rgb_shift",
+                   "gaussian_blur")                      # data_loading.py:216-224, in that order
+ONEOF_COLOUR = ("to_gray", "hsv", "channel_shuffle", "rgb_shift")      # need channels == 3
+
+
+def _oneof_check(name, cfg):
+    """Range checks of one member's settings; raises ValueError."""
+    def bad(what):
+        raise ValueError("DeviceAugment: one_of member %r: %s" % (name, what))
+    if name == "grid_distortion" and not (1 <= int(cfg["num_steps"]) <= 64 and cfg["num_steps"] == int(cfg["num_steps"])
+                                          and 0 <= cfg["distort_limit"] < 1):
+        bad("num_steps in 1..64 and 0 <= distort_limit < 1")
+    if name == "elastic" and not (cfg["sigma"] > 0 and int(4.0 * cfg["sigma"] + 0.5) <= hip.ONEOF_MAX_RADIUS and abs(cfg["alpha"]) <= 1e6):
+        bad("sigma in (0, %d] and |alpha| <= 1e6" % (hip.ONEOF_MAX_RADIUS // 4))
+    if name == "clahe" and not (len(cfg["clip_limit"]) == 2 and 1 <= cfg["clip_limit"][0] <= cfg["clip_limit"][1] <= 1e6
+                                and tuple(cfg["tile_grid"]) == (8, 8)):
+        bad("1 <= clip_limit[0] <= clip_limit[1] and tile_grid (8, 8)")
+    if name == "hsv" and not all(0 <= cfg[k] <= 255 for k in ("hue", "sat", "val")):
+        bad("hue, sat, val limits in 0..255")
+    if name == "rgb_shift" and not all(0 <= cfg[k] <= 255 for k in ("r", "g", "b")):
+        bad("r, g, b limits in 0..255")
+    if name == "grid_dropout" and not 0 < cfg["ratio"] <= 1:
+        bad("0 < ratio <= 1")
+    if name == "gaussian_blur":
+        lo, hi = cfg["blur_limit"]
+        if not (lo in (3, 5, 7) and hi in (3, 5, 7) and lo <= hi):
+            bad("blur_limit: odd sizes 3..7, increasing")
+
+
+def parse_one_of(one_of, channels):
+    """`one_of` of DeviceAugment -> [(member, settings)]; raises ValueError (unknown member or setting, empty list, a colour member
+    on one channel, a setting out of range)."""
+    if isinstance(one_of, str):
+        if one_of != "reference":
+            raise ValueError("DeviceAugment: one_of = %r, must be None, 'reference' or a list of members" % (one_of,))
+        one_of = list(ONEOF_REFERENCE)
+    members = []
+    for m in one_of:
+        name, over = (m, {}) if isinstance(m, str) else (m[0], dict(m[1]))
+        if name not in ONEOF_MEMBERS:
+            raise ValueError("DeviceAugment: unknown one_of member %r (known: %s)" % (name, ", ".join(ONEOF_MEMBERS)))
+        unknown = [k for k in over if k not in ONEOF_MEMBERS[name]]
+        if unknown:
+            raise ValueError("DeviceAugment: one_of member %r has no setting %s" % (name, unknown))
+        cfg = dict(ONEOF_MEMBERS[name], **over)
+        _oneof_check(name, cfg)
+        members.append((name, cfg))
+    if not members:
+        raise ValueError("DeviceAugment: one_of is empty")
+    colour = [n for n, _ in members if n in ONEOF_COLOUR]
+    if channels != 3 and colour:
+        raise ValueError("DeviceAugment: one_of members %s need channels == 3" % ", ".join(colour))
+    return members
+
+
+_LAB = []
+
+
+def lab_tables():
+    """The int32 tables of the 8-bit LAB conversion CLAHE uses on 3-channel frames (offsets hip.LAB_*), built once in double and
+    shared by the kernels and their numpy restatement, so that both index CLAHE's LUT with the same L8.  sRGB primaries, D65
+    white; forward: gamma table (scale 2040) -> XYZ / white in 2^12 fixed point -> f() table (scale 2^15) -> L8 = (116 fY - 16) *
+    2.55, a8 = 500 (fX - fY) + 128, b8 = 200 (fY - fZ) + 128; inverse: fy, fx - fy, fy - fz tables -> f^-1 in integers -> RGB in
+    2^12 fixed point -> inverse-gamma table of 2^14 + 1 entries."""
+    if _LAB:
+        return _LAB[0]
+    T = np.zeros(hip.LAB_TABLE_INTS, dtype=np.int64)
+    v = np.arange(256) / 255.0
+    T[hip.LAB_GAMMA:hip.LAB_GAMMA + 256] = np.rint(2040.0 * np.where(v <= 0.04045, v / 12.92, ((v + 0.055) / 1.055) ** 2.4))
+    t = np.arange(3072) / 2040.0
+    T[hip.LAB_CBRT:hip.LAB_CBRT + 3072] = np.rint(32768.0 * np.where(t < 0.008856, t * 7.787 + 16.0 / 116.0, np.cbrt(t)))
+    k = np.arange(256)
+    T[hip.LAB_FY:hip.LAB_FY + 256] = np.rint(32768.0 * ((k * 100.0 / 255.0 + 16.0) / 116.0))
+    T[hip.LAB_DA:hip.LAB_DA + 256] = np.rint(32768.0 * (k - 128.0) / 500.0)
+    T[hip.LAB_DB:hip.LAB_DB + 256] = np.rint(32768.0 * (k - 128.0) / 200.0)
+    M = np.array([[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169], [0.019334, 0.119193, 0.950227]])
+    white = M.sum(axis=1)                                       # D65: (0.950456, 1, 1.088754)
+    fwd = np.rint(4096.0 * M / white[:, None]).astype(np.int64)
+    fwd[:, 1] += 4096 - fwd.sum(axis=1)                         # white maps to exactly 1.0 on every row
+    T[hip.LAB_FWD:hip.LAB_FWD + 9] = fwd.reshape(-1)
+    T[hip.LAB_INV:hip.LAB_INV + 9] = np.rint(4096.0 * np.linalg.inv(M) * white[None, :]).reshape(-1)
+    u = np.arange(16385) / 16384.0
+    T[hip.LAB_INVGAMMA:] = np.rint(255.0 * np.where(u <= 0.0031308, u * 12.92, 1.055 * u ** (1.0 / 2.4) - 0.055))
+    _LAB.append(T.astype(np.int32))
+    return _LAB[0]
+
+
+def grid_distortion_map(n, num_steps, steps):
+    """albumentations' grid_distortion map of one axis of n pixels: piecewise `np.linspace` over `num_steps` cells of n //
+    num_steps pixels (and the rest), cell k stretched by steps[k]; float32 [n].  The cells are sampled WITHOUT their end point, so
+    that factors of 1 give the identity map (albumentations includes the end point, which stretches a cell of c pixels by
+    c / (c - 1) even at distort_limit 0)."""
+    step = n // num_steps
+    xx = np.zeros(n, dtype=np.float32)
+    prev = 0.0
+    for idx in range(num_steps + 1):
+        start = idx * step
+        end = start + step
+        if end > n:
+            end, cur = n, float(n)
+        else:
+            cur = prev + step * float(steps[idx])
+        xx[start:end] = np.linspace(prev, cur, end - start, endpoint=False)
+        prev = cur
+    return xx
+
+
+def gaussian_weights(sigma):
+    """Taps -r..r of scipy.ndimage.gaussian_filter(sigma, truncate=4): r = int(4 sigma + 0.5), exp(-x^2 / 2 sigma^2) normalised in
+    double, then float32."""
+    r = int(4.0 * float(sigma) + 0.5)
+    x = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-0.5 / (float(sigma) * float(sigma)) * x * x)
+    return (w / w.sum()).astype(np.float32)
+
+
+def elastic_noise(seed, H, W):
+    """The two noise fields (dx, dy) of an elastic sample: U[-1, 1) float32 [2,H,W] from the sample's seed."""
+    return np.random.default_rng(int(seed)).random((2, H, W), dtype=np.float32) * np.float32(2) - np.float32(1)
+
+
+def pack_oneof(samples, size):
+    """List of per-sample dicts (the `"oneof"` entry of each: None, or {"op": member, ...drawn values}) -> (ctypes array of
+    hip.OneOfParam, float32 host tables or None, number of elastic samples).  Keys per member: rgb_shift "shift" (r, g, b); hsv
+    "shift" (hue, sat, val); channel_shuffle "perm"; gaussian_blur "k"; clahe "clip"; grid_dropout "ratio"; grid_distortion
+    "num_steps", "xsteps", "ysteps" (num_steps + 1 factors each); elastic "seed", "alpha", "sigma".  The tables hold, per
+    grid_distortion sample, its maps xx[W], yy[H], and per elastic sample the Gaussian taps and the two noise fields."""
+    H, W = int(size[0]), int(size[1])
+    arr = (hip.OneOfParam * len(samples))()
+    tabs, off, n_el = [], 0, 0
+
+    def push(a):
+        nonlocal off
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        tabs.append(a)
+        off += a.size
+
+    for q, s in zip(arr, samples):
+        d = s.get("oneof")
+        if d is None:
+            continue
+        name = d.get("op")
+        if name not in ONEOF_MEMBERS:
+            raise ValueError("DeviceAugment: unknown one_of member %r" % (name,))
+        q.op = hip.ONEOF_OPS[name]
+        if name in ("rgb_shift", "hsv"):
+            sh = [float(v) for v in d["shift"]]
+            if len(sh) != 3 or not all(abs(v) <= 255 for v in sh):
+                raise ValueError("DeviceAugment: %s shift %r: three values within +-255" % (name, sh))
+            q.v[:] = sh
+        elif name == "channel_shuffle":
+            perm = [int(v) for v in d["perm"]]
+            if sorted(perm) != [0, 1, 2]:
+                raise ValueError("DeviceAugment: channel_shuffle perm %r is not a permutation of 0..2" % (perm,))
+            q.perm[:] = perm
+        elif name == "gaussian_blur":
+            if d["k"] not in (3, 5, 7):
+                raise ValueError("DeviceAugment: gaussian_blur k = %r, must be 3, 5 or 7" % (d["k"],))
+            q.k = int(d["k"])
+        elif name == "clahe":
+            if not 1 <= float(d["clip"]) <= 1e6:
+                raise ValueError("DeviceAugment: clahe clip = %r, must be in [1, 1e6]" % (d["clip"],))
+            q.v[0] = float(d["clip"])
+        elif name == "grid_dropout":
+            ratio = float(d.get("ratio", 0.5))
+            unit = max(2, min(H, W) // 10)
+            q.unit, q.hole = unit, min(max(int(unit * ratio), 1), unit - 1)
+        elif name == "grid_distortion":
+            n = int(d["num_steps"])
+            if len(d["xsteps"]) != n + 1 or len(d["ysteps"]) != n + 1 or n < 1:
+                raise ValueError("DeviceAugment: grid_distortion needs num_steps + 1 factors per axis")
+            q.tab_off = off
+            push(grid_distortion_map(W, n, d["xsteps"]))
+            push(grid_distortion_map(H, n, d["ysteps"]))
+        elif name == "elastic":
+            sigma, alpha = float(d["sigma"]), float(d["alpha"])
+            if not (sigma > 0 and int(4.0 * sigma + 0.5) <= hip.ONEOF_MAX_RADIUS and abs(alpha) <= 1e6):
+                raise ValueError("DeviceAugment: elastic sigma = %r / alpha = %r" % (sigma, alpha))
+            w = gaussian_weights(sigma)
+            q.radius, q.slot, q.tab_off = (w.size - 1) // 2, n_el, off
+            q.v[0], q.v[1] = alpha, sigma
+            push(w)
+            push(elastic_noise(d["seed"], H, W))
+            n_el += 1
+    return arr, (np.concatenate(tabs) if tabs else None), n_el
+
+
 class DeviceAugment:
     """`x, y = DeviceAugment((256, 256))(images_u8, masks_u8, params=None, src_hw=None)`: the reference's training augmentations on
-    the device (`dataset/data_loading.py:207-214`, then Normalize), OneOf block excluded.
+    the device (`dataset/data_loading.py:207-225`, then Normalize); the OneOf block with `one_of="reference"`.
 
     images_u8: uint8 [B,Hs,Ws,channels] on the GPU (channels=1: also [B,Hs,Ws]); masks_u8: uint8 [B,Hs,Ws] or None.  Returns fp32
     [B,channels,H,W] and int64 [B,H,W] labels (mask_mode as in `DevicePreprocess`), what `LM_Net.forward` and `SegLoss` take.
@@ -128,6 +323,16 @@ class DeviceAugment:
         `ssr_matrix` (centre (W/2, H/2): the albumentations 1.3 convention; later releases moved it by half a pixel);
       - HorizontalFlip(p_hflip), VerticalFlip(p_vflip);
       - ColorJitter(*cj) with probability p_cj: factors U[max(0, 1 - x), 1 + x], hue U[-h, h], the op order shuffled.
+      - one_of (None = no OneOf block: same draws, same two kernels as before; "reference" = the nine members of
+        `data_loading.py:216-224` with equal weight; or a list of member names / (name, {settings}) pairs from ONEOF_MEMBERS) with
+        probability p_oneof, after ColorJitter and before Normalize.  One member is drawn per sample; its values follow the sample's
+        other draws: to_gray; grid_distortion (num_steps + 1 factors 1 + U[-distort_limit, distort_limit] per axis, reflect-101
+        border, labels remapped by nearest pixel); elastic (a seed for the two noise fields, blurred with sigma, times alpha; at the
+        defaults alpha = 1, sigma = 50 the displacement stays below 1/64 pixel and the 1/32-pixel remap returns its input); clahe
+        (clip U[clip_limit], 8 x 8 tiles; on L of an integer 8-bit LAB for 3 channels); hsv (shifts U[-limit, limit]);
+        channel_shuffle (a permutation); grid_dropout (unit = max(2, min(H, W) // 10), mask untouched); rgb_shift (shifts U[-limit,
+        limit]); gaussian_blur (k from the odd sizes of blur_limit, cv2's fixed kernels).  to_gray, hsv, channel_shuffle and
+        rgb_shift need channels == 3.  `last_oneof` keeps (OneOfParam array, host tables) of the last call.
     generator: None, an int seed, a numpy Generator or a torch.Generator: a seed gives the same parameters every time.  The
     stream is not albumentations' own (matching its RNG is not a goal)."""
 
@@ -135,7 +340,7 @@ class DeviceAugment:
 
     def __init__(self, size=(256, 256), mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), channels=3, mask_mode="binary",
                  scale=(0.8, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), shift_limit=0.1, scale_limit=0.1, rotate_limit=30, p_ssr=0.5,
-                 p_hflip=0.5, p_vflip=0.5, cj=(0.2, 0.2, 0.2, 0.2), p_cj=0.4, generator=None):
+                 p_hflip=0.5, p_vflip=0.5, cj=(0.2, 0.2, 0.2, 0.2), p_cj=0.4, generator=None, one_of=None, p_oneof=0.4):
         if channels not in (1, 3):
             raise ValueError("DeviceAugment: channels = %r, must be 1 or 3" % (channels,))
         if mask_mode not in self.MASK_MODES:
@@ -160,6 +365,12 @@ class DeviceAugment:
         self.shift_limit, self.scale_limit, self.rotate_limit = float(shift_limit), float(scale_limit), float(rotate_limit)
         self.p_ssr, self.p_hflip, self.p_vflip, self.p_cj = float(p_ssr), float(p_hflip), float(p_vflip), float(p_cj)
         self.cj = tuple(float(v) for v in cj)
+        if not 0.0 <= p_oneof <= 1.0:
+            raise ValueError("DeviceAugment: p_oneof = %r outside [0, 1]" % (p_oneof,))
+        self.one_of = None if one_of is None else parse_one_of(one_of, int(channels))
+        self.p_oneof = float(p_oneof)
+        if self.one_of is not None and any(n == "grid_distortion" and min(self.size) < c["num_steps"] for n, c in self.one_of):
+            raise ValueError("DeviceAugment: grid_distortion num_steps above the output size %r" % (self.size,))
         if generator is None or isinstance(generator, (int, np.integer)):
             self._rng = np.random.default_rng(generator)
         elif isinstance(generator, np.random.Generator):
@@ -171,6 +382,8 @@ class DeviceAugment:
         self._torch_gen = generator if self._rng is None else None
         self.last_params = None        # the parameters of the last call (kept alive until its H2D copy has run)
         self.last_gray_sum = None      # int64 [B] device tensor: the contrast op's gray sums of the last call (0 where it did not run)
+        self.last_oneof = None         # (OneOfParam array, host tables or None) of the last call with one_of set
+        self._lab_dev = {}             # device -> the LAB tables, uploaded with the first call that needs them
 
     def _generator(self):
         if self._rng is not None:
@@ -226,7 +439,38 @@ class DeviceAugment:
             out.append({"crop": crop, "M": ssr_matrix(H, W, angle, scale, dx, dy) if ssr else None, "flips": flips,
                         "cj": fac if cj else None, "order": order,
                         "angle": angle, "scale": scale, "dx": dx, "dy": dy})
+            if self.one_of is not None:
+                out[-1]["oneof"] = self._draw_oneof(rng)
         return out
+
+    def _draw_oneof(self, rng):
+        """One sample's draw of the OneOf block: None (probability 1 - p_oneof) or {"op": member, ...its values}."""
+        fire = rng.random() < self.p_oneof
+        name, cfg = self.one_of[int(rng.integers(len(self.one_of)))]
+        if not fire:
+            return None
+        d = {"op": name}
+        if name == "rgb_shift":
+            d["shift"] = [rng.uniform(-cfg[k], cfg[k]) for k in ("r", "g", "b")]
+        elif name == "hsv":
+            d["shift"] = [rng.uniform(-cfg[k], cfg[k]) for k in ("hue", "sat", "val")]
+        elif name == "channel_shuffle":
+            d["perm"] = [int(v) for v in rng.permutation(3)]
+        elif name == "gaussian_blur":
+            lo, hi = cfg["blur_limit"]
+            d["k"] = int(lo) + 2 * int(rng.integers((int(hi) - int(lo)) // 2 + 1))
+        elif name == "clahe":
+            d["clip"] = rng.uniform(*cfg["clip_limit"])
+        elif name == "grid_dropout":
+            d["ratio"] = cfg["ratio"]
+        elif name == "grid_distortion":
+            n, lim = int(cfg["num_steps"]), cfg["distort_limit"]
+            d["num_steps"] = n
+            d["xsteps"] = [1.0 + rng.uniform(-lim, lim) for _ in range(n + 1)]
+            d["ysteps"] = [1.0 + rng.uniform(-lim, lim) for _ in range(n + 1)]
+        elif name == "elastic":
+            d["seed"], d["alpha"], d["sigma"] = int(rng.integers(0, 2 ** 32)), cfg["alpha"], cfg["sigma"]
+        return d
 
     def sample(self, B, src_hw):
         """A batch of parameters: ctypes array of B `hip.AugParam` (lmn_aug_param_t)."""
@@ -243,7 +487,9 @@ class DeviceAugment:
                 raise ValueError("DeviceAugment: crop window %d (y0 %d, x0 %d, %dx%d) outside its %dx%d source"
                                  % (b, p.y0, p.x0, p.h, p.w, hs, ws))
 
-    def __call__(self, images, masks=None, params=None, src_hw=None):
+    def __call__(self, images, masks=None, params=None, src_hw=None, oneof=None):
+        """params: None (draw), a list of sample dicts, or a packed AugParam array.  With one_of set, the OneOf draws come from the
+        dicts' "oneof" entries; with a packed array give `oneof` = what `pack_oneof` returned (default: no member fires)."""
         ref = images if images is not None else masks
         if ref is None:
             raise ValueError("DeviceAugment: images or masks required")
@@ -257,11 +503,23 @@ class DeviceAugment:
         hw = self._src_hw(B, src_hw if src_hw is not None else (Hs, Ws))
         if hw[:, 0].max() > Hs or hw[:, 1].max() > Ws:
             raise ValueError("DeviceAugment: src_hw exceeds the %dx%d frame" % (Hs, Ws))
-        if params is None:
+        if self.one_of is None and oneof is not None:
+            raise ValueError("DeviceAugment: oneof parameters given, but one_of is not set")
+        if self.one_of is not None and not isinstance(params, ctypes.Array):
+            dicts = self.sample_dicts(B, hw) if params is None else params
+            params, oneof = pack_params(dicts), pack_oneof(dicts, self.size)
+        elif params is None:
             params = self.sample(B, hw)
         elif not isinstance(params, ctypes.Array):
             params = pack_params(params)
         self.validate(params, hw)
+        if self.one_of is not None:
+            if oneof is None:
+                oneof = pack_oneof([{}] * B, self.size)
+            if len(oneof[0]) != B:
+                raise ValueError("DeviceAugment: %d OneOf parameter sets for a batch of %d" % (len(oneof[0]), B))
+            if self.channels != 3 and any(q.op in [hip.ONEOF_OPS[n] for n in ONEOF_COLOUR] for q in oneof[0]):
+                raise ValueError("DeviceAugment: one_of members %s need channels == 3" % ", ".join(ONEOF_COLOUR))
         if not ref.is_cuda:
             raise RuntimeError("DeviceAugment runs on the HIP device only (got %s); there is no CPU path" % ref.device)
         self.last_params = params
@@ -271,8 +529,36 @@ class DeviceAugment:
         scratch = torch.empty(B, H, W, C, device=dev, dtype=torch.uint8) if images is not None else None
         gray = torch.empty(B, device=dev, dtype=torch.int64) if images is not None else None
         pdev = torch.empty(B * ctypes.sizeof(hip.AugParam), device=dev, dtype=torch.uint8)
+        if self.one_of is not None:
+            self._call_oneof(images, masks, params, hw if src_hw is not None else None, oneof, pdev, scratch, gray, x, y)
+            self.last_gray_sum = gray
+            return x, y
         hip.augment_u8(images.contiguous() if images is not None else None, masks.contiguous() if masks is not None else None, params,
                        hw.astype(np.int32) if src_hw is not None else None, pdev, scratch, gray, x, y, self.mean, self.std, C,
                        self.MASK_MODES[self.mask_mode])
         self.last_gray_sum = gray
         return x, y
+
+    def _call_oneof(self, images, masks, params, hw, oneof, pdev, scratch, gray, x, y):
+        """The call through lmn_augment_oneof_u8: the buffers of the plain call plus the second scratch, the label copy (when a
+        geometric member fired), the device copies of the OneOf parameters and tables, and the workspace."""
+        arr, tables, n_el = oneof
+        self.last_oneof = (arr, tables)
+        ref = images if images is not None else masks
+        dev, (H, W), C, B = ref.device, self.size, self.channels, ref.shape[0]
+        ops = [q.op for q in arr]
+        geo = any(o in (hip.ONEOF_OPS["grid_distortion"], hip.ONEOF_OPS["elastic"]) for o in ops)
+        lab = None
+        if images is not None and C == 3 and hip.ONEOF_OPS["clahe"] in ops:
+            lab = self._lab_dev.get(dev)
+            if lab is None:
+                lab = self._lab_dev[dev] = torch.empty(hip.LAB_TABLE_INTS, device=dev, dtype=torch.int32)
+                lab.copy_(torch.from_numpy(lab_tables()))
+        scratch2 = torch.empty(B, H, W, C, device=dev, dtype=torch.uint8) if images is not None else None
+        ytmp = torch.empty(B, H, W, device=dev, dtype=torch.int64) if masks is not None and geo else None
+        odev = torch.empty(B * ctypes.sizeof(hip.OneOfParam), device=dev, dtype=torch.uint8)
+        tdev = torch.empty(tables.size, device=dev, dtype=torch.float32) if tables is not None else None
+        ws = torch.empty(hip.oneof_workspace(B, H, W, C, n_el), device=dev, dtype=torch.uint8)
+        hip.augment_oneof_u8(images.contiguous() if images is not None else None, masks.contiguous() if masks is not None else None,
+                             params, hw.astype(np.int32) if hw is not None else None, pdev, scratch, gray, x, y, self.mean, self.std,
+                             C, self.MASK_MODES[self.mask_mode], arr, odev, tables, tdev, lab, scratch2, ytmp, ws)

@@ -139,6 +139,20 @@ class AugParam(C.Structure):
                 ("order", C.c_int32 * 4), ("_pad", C.c_int32)]
 
 
+class OneOfParam(C.Structure):
+    """Mirror of lmn_oneof_param_t (include/lmnet_oneof.h): one sample's member of the OneOf block and its drawn values."""
+    _fields_ = [("op", C.c_int32), ("k", C.c_int32), ("perm", C.c_int32 * 3), ("unit", C.c_int32), ("hole", C.c_int32),
+                ("radius", C.c_int32), ("slot", C.c_int32), ("_pad", C.c_int32), ("tab_off", C.c_int64), ("v", C.c_double * 3)]
+
+
+# LMN_ONEOF_* of include/lmnet_oneof.h
+ONEOF_OPS = {"none": 0, "to_gray": 1, "grid_distortion": 2, "elastic": 3, "clahe": 4, "hsv": 5, "channel_shuffle": 6,
+             "grid_dropout": 7, "rgb_shift": 8, "gaussian_blur": 9}
+ONEOF_MAX_RADIUS = 4096
+# offsets into the int32 array of 8-bit LAB tables (LMN_LAB_* of include/lmnet_oneof.h; built by lm_net_amd.data.lab_tables)
+LAB_GAMMA, LAB_CBRT, LAB_FY, LAB_DA, LAB_DB, LAB_FWD, LAB_INV, LAB_INVGAMMA, LAB_TABLE_INTS = 0, 256, 3328, 3584, 3840, 4096, 4105, 4128, 20513
+
+
 class PostParam(C.Structure):
     """Mirror of lmn_post_param_t: the cleaning parameters of lmn_post_clean (lm_net_amd.post.DevicePostprocess)."""
     _fields_ = [("connectivity", C.c_int32), ("hole_limit", C.c_int32), ("class_mask", C.c_uint64), ("keep_largest_mask", C.c_uint64),
@@ -158,6 +172,11 @@ SYMBOLS = [
     "lmn_plan_run", "lmn_prof_begin", "lmn_prof_end",
 ]
 
+# every symbol include/lmnet_oneof.h declares (the OneOf block of the training augmentations).  Kept apart from SYMBOLS because the
+# guard manifest (tests/guard.py) partitions SYMBOLS and is frozen; tests/test_guard_oneof_gpu.py guards these until a later change
+# folds them into the manifest.
+SYMBOLS_ONEOF = ["lmn_sizeof_oneof_param", "lmn_oneof_workspace", "lmn_augment_oneof_u8"]
+
 _lib = None
 
 
@@ -171,7 +190,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in SYMBOLS:
+    for name in SYMBOLS + SYMBOLS_ONEOF:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -179,6 +198,7 @@ def load():
     lib.lmn_conv_wgrad_workspace.restype = C.c_int64
     lib.lmn_surface_workspace.restype = C.c_int64
     lib.lmn_post_workspace.restype = C.c_int64
+    lib.lmn_oneof_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -187,7 +207,8 @@ def load():
         raise RuntimeError("lm_net_amd: ABI version mismatch")
     if (lib.lmn_sizeof_conv_args() != C.sizeof(ConvArgs) or lib.lmn_sizeof_src() != C.sizeof(SrcT)
             or lib.lmn_sizeof_wgrad_args() != C.sizeof(WgradArgs) or lib.lmn_sizeof_reduce_job() != C.sizeof(ReduceJob)
-            or lib.lmn_sizeof_aug_param() != C.sizeof(AugParam) or lib.lmn_sizeof_post_param() != C.sizeof(PostParam)):
+            or lib.lmn_sizeof_aug_param() != C.sizeof(AugParam) or lib.lmn_sizeof_post_param() != C.sizeof(PostParam)
+            or lib.lmn_sizeof_oneof_param() != C.sizeof(OneOfParam)):
         raise RuntimeError("lm_net_amd: argument struct layout differs between hip.py and lmnet_hip.h")
     _lib = lib
     return lib
@@ -1156,6 +1177,62 @@ def augment_u8(images, masks, params, src_hw, params_dev, scratch, gray_sum, out
     _check(load().lmn_augment_u8(raw(images, torch.uint8), raw(masks, torch.uint8), params, hw, raw(params_dev, torch.uint8), B, Hs,
                                  Ws, H, W, int(channels), int(mask_mode), mc, sc, raw(scratch, torch.uint8),
                                  raw(gray_sum, torch.int64), _p(out), raw(labels, torch.int64), _stream()), "augment_u8")
+
+
+def oneof_workspace(B, H, W, channels, n_elastic):
+    """Bytes of the workspace lmn_augment_oneof_u8 needs (lmn_oneof_workspace)."""
+    n = int(load().lmn_oneof_workspace(int(B), int(H), int(W), int(channels), int(n_elastic)))
+    if n < 0:
+        raise ValueError("lm_net_amd.oneof_workspace: B=%r, %rx%r, %r channel(s), %r elastic" % (B, H, W, channels, n_elastic))
+    return n
+
+
+def augment_oneof_u8(images, masks, params, src_hw, params_dev, scratch, gray_sum, out, labels, mean, std, channels, mask_mode,
+                     oneof, oneof_dev, tables, tables_dev, lab_tables, scratch2, labels_tmp, workspace):
+    """augment_u8 with the OneOf block between ColorJitter and Normalize (lmn_augment_oneof_u8, include/lmnet_oneof.h).  The first
+    thirteen arguments are augment_u8's.  oneof: host ctypes array of B OneOfParam (checked, copied into oneof_dev, uint8 [B *
+    sizeof(OneOfParam)]); tables: host float32 numpy array (grid-distortion maps, elastic weights and noise) or None, copied into
+    tables_dev (fp32, same length); lab_tables: int32 [LAB_TABLE_INTS] device tensor or None; scratch2: uint8 like scratch;
+    labels_tmp: int64 like labels or None; workspace: uint8, at least oneof_workspace(...) bytes."""
+    def raw(t, dt):
+        if t is None:
+            return None
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError("lm_net_amd.augment_oneof_u8: contiguous %s device tensor required" % dt)
+        return C.c_void_p(t.data_ptr())
+    ref = images if images is not None else masks
+    dst = out if out is not None else labels
+    if ref is None or dst is None:
+        raise ValueError("lm_net_amd.augment_oneof_u8: images or masks, and out or labels, required")
+    B, Hs, Ws = ref.shape[0], ref.shape[1], ref.shape[2]
+    H, W = dst.shape[-2], dst.shape[-1]
+    if channels not in (1, 3) or mask_mode not in (0, 1) or len(mean) != channels or len(std) != channels:
+        raise ValueError("lm_net_amd.augment_oneof_u8: channels %r / mask_mode %r / mean, std" % (channels, mask_mode))
+    nt = 0 if tables is None else int(tables.size)
+    if ((images is not None and (images.numel() != B * Hs * Ws * channels or out is None or out.numel() != B * channels * H * W
+                                 or scratch is None or scratch.numel() != B * H * W * channels or scratch2 is None
+                                 or scratch2.numel() != B * H * W * channels or gray_sum is None or gray_sum.numel() != B))
+            or (masks is not None and (masks.numel() != B * Hs * Ws or labels is None or labels.numel() != B * H * W
+                                       or (labels_tmp is not None and labels_tmp.numel() != B * H * W)))
+            or len(params) != B or params_dev.numel() != B * C.sizeof(AugParam)
+            or len(oneof) != B or oneof_dev.numel() != B * C.sizeof(OneOfParam)
+            or (nt and (tables.dtype != np.float32 or tables_dev is None or tables_dev.numel() != nt))
+            or (lab_tables is not None and lab_tables.numel() != LAB_TABLE_INTS)
+            or (src_hw is not None and tuple(src_hw.shape) != (B, 2))):
+        raise ValueError("lm_net_amd.augment_oneof_u8: tensor sizes do not match B=%d, %dx%d -> %dx%d, %d channel(s)"
+                         % (B, Hs, Ws, H, W, channels))
+    hw_arr = None if src_hw is None else np.ascontiguousarray(src_hw, dtype=np.int32)   # (kept alive across the call)
+    hw = None if hw_arr is None else hw_arr.ctypes.data_as(C.POINTER(C.c_int32))
+    tab_arr = None if not nt else np.ascontiguousarray(tables)                           # (kept alive across the call)
+    tab = None if not nt else tab_arr.ctypes.data_as(C.POINTER(C.c_float))
+    mc, sc = (C.c_double * channels)(*[float(v) for v in mean]), (C.c_double * channels)(*[float(v) for v in std])
+    _check(load().lmn_augment_oneof_u8(
+        raw(images, torch.uint8), raw(masks, torch.uint8), params, hw, raw(params_dev, torch.uint8), B, Hs, Ws, H, W, int(channels),
+        int(mask_mode), mc, sc, raw(scratch, torch.uint8), raw(gray_sum, torch.int64), _p(out), raw(labels, torch.int64), oneof,
+        raw(oneof_dev, torch.uint8), tab, C.c_int64(nt), _p(tables_dev) if nt else None, raw(lab_tables, torch.int32),
+        raw(scratch2, torch.uint8), raw(labels_tmp, torch.int64), raw(workspace, torch.uint8), C.c_int64(workspace.numel()), _stream()),
+        "augment_oneof_u8")
+
 
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2):
     _check(load().lmn_adamw_step(_p(p), _p(g), _p(m), _p(v), _i64(p.numel()), _f(lr), _f(beta1), _f(beta2), _f(eps),
