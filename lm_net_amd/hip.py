@@ -153,6 +153,23 @@ ONEOF_MAX_RADIUS = 4096
 LAB_GAMMA, LAB_CBRT, LAB_FY, LAB_DA, LAB_DB, LAB_FWD, LAB_INV, LAB_INVGAMMA, LAB_TABLE_INTS = 0, 256, 3328, 3584, 3840, 4096, 4105, 4128, 20513
 
 
+class LossParam(C.Structure):
+    """Mirror of lmn_loss_param_t (include/lmnet_loss.h): the scalar parameters of lmn_segloss_ex_fwd / _bwd."""
+    _fields_ = [("ignore_index", C.c_int64), ("has_ignore", C.c_int32), ("label_smoothing", C.c_float), ("smooth", C.c_float),
+                ("ce_scale", C.c_float), ("dice_scale", C.c_float), ("focal_scale", C.c_float), ("focal_gamma", C.c_float),
+                ("focal_alpha", C.c_float), ("_pad", C.c_int32 * 6)]
+
+
+def loss_sums_floats(n_classes):
+    """LMN_LOSS_SUMS_FLOATS of include/lmnet_loss.h: floats of the `sums` workspace of segloss_ex_fwd."""
+    return 4 + 3 * int(n_classes)
+
+
+def loss_coef_floats(n_classes):
+    """LMN_LOSS_COEF_FLOATS of include/lmnet_loss.h: floats of the `coef` workspace shared by segloss_ex_fwd / _bwd."""
+    return 4 + 2 * int(n_classes)
+
+
 class PostParam(C.Structure):
     """Mirror of lmn_post_param_t: the cleaning parameters of lmn_post_clean (lm_net_amd.post.DevicePostprocess)."""
     _fields_ = [("connectivity", C.c_int32), ("hole_limit", C.c_int32), ("class_mask", C.c_uint64), ("keep_largest_mask", C.c_uint64),
@@ -177,6 +194,10 @@ SYMBOLS = [
 # folds them into the manifest.
 SYMBOLS_ONEOF = ["lmn_sizeof_oneof_param", "lmn_oneof_workspace", "lmn_augment_oneof_u8"]
 
+# every symbol include/lmnet_loss.h declares (void labels and the focal term of the loss, per-image statistics); apart from SYMBOLS for
+# the same reason, guarded by tests/test_guard_loss_gpu.py.
+SYMBOLS_LOSS = ["lmn_sizeof_loss_param", "lmn_segloss_ex_fwd", "lmn_segloss_ex_bwd", "lmn_image_stats"]
+
 _lib = None
 
 
@@ -190,7 +211,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in SYMBOLS + SYMBOLS_ONEOF:
+    for name in SYMBOLS + SYMBOLS_ONEOF + SYMBOLS_LOSS:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -208,7 +229,7 @@ def load():
     if (lib.lmn_sizeof_conv_args() != C.sizeof(ConvArgs) or lib.lmn_sizeof_src() != C.sizeof(SrcT)
             or lib.lmn_sizeof_wgrad_args() != C.sizeof(WgradArgs) or lib.lmn_sizeof_reduce_job() != C.sizeof(ReduceJob)
             or lib.lmn_sizeof_aug_param() != C.sizeof(AugParam) or lib.lmn_sizeof_post_param() != C.sizeof(PostParam)
-            or lib.lmn_sizeof_oneof_param() != C.sizeof(OneOfParam)):
+            or lib.lmn_sizeof_oneof_param() != C.sizeof(OneOfParam) or lib.lmn_sizeof_loss_param() != C.sizeof(LossParam)):
         raise RuntimeError("lm_net_amd: argument struct layout differs between hip.py and lmnet_hip.h")
     _lib = lib
     return lib
@@ -979,6 +1000,57 @@ def confusion(logits, target, counts):
     B, Cn = logits.shape[0], logits.shape[1]
     hw = logits.numel() // (B * Cn)
     _check(load().lmn_confusion(_p(logits), _pl(target), B, Cn, _i64(hw), _p(counts), _stream()), "confusion")
+
+
+def loss_param(ignore_index=None, label_smoothing=0.0, smooth=1e-5, ce_scale=1.0, dice_scale=1.0, focal_scale=0.0, focal_gamma=2.0,
+               focal_alpha=0.25):
+    """A LossParam (lmn_loss_param_t) from Python values; ignore_index None: no ignore label."""
+    p = LossParam()
+    p.has_ignore, p.ignore_index = (0, 0) if ignore_index is None else (1, int(ignore_index))
+    p.label_smoothing, p.smooth = float(label_smoothing), float(smooth)
+    p.ce_scale, p.dice_scale, p.focal_scale = float(ce_scale), float(dice_scale), float(focal_scale)
+    p.focal_gamma, p.focal_alpha = float(focal_gamma), float(focal_alpha)
+    return p
+
+
+def segloss_ex_fwd(logits, target, w_ce, w_dice, param, sums, coef, loss4):
+    """loss4 = [total, ce, dice, focal] with void labels and the focal term (lmn_segloss_ex_fwd); param: a LossParam; sums / coef:
+    fp32 workspaces of at least loss_sums_floats(C) / loss_coef_floats(C)."""
+    B, Cn = logits.shape[0], logits.shape[1]
+    hw = logits.numel() // (B * Cn)
+    if sums.numel() < loss_sums_floats(Cn) or coef.numel() < loss_coef_floats(Cn) or loss4.numel() < 4:
+        raise ValueError("lm_net_amd.segloss_ex_fwd: workspace too small for %d classes" % Cn)
+    _check(load().lmn_segloss_ex_fwd(_p(logits), _pl(target), _p(w_ce), _p(w_dice), B, Cn, _i64(hw), C.byref(param), _p(sums), _p(coef),
+                                     _p(loss4), _stream()), "segloss_ex_fwd")
+
+
+def segloss_ex_bwd(logits, target, w_ce, coef, gscale, param, dlogits):
+    """dlogits = gscale[0] * d total / d logits (gscale None: 1) from the coef of segloss_ex_fwd (lmn_segloss_ex_bwd)."""
+    B, Cn = logits.shape[0], logits.shape[1]
+    hw = logits.numel() // (B * Cn)
+    if coef.numel() < loss_coef_floats(Cn) or dlogits.numel() != logits.numel():
+        raise ValueError("lm_net_amd.segloss_ex_bwd: coef or dlogits does not match %d classes" % Cn)
+    _check(load().lmn_segloss_ex_bwd(_p(logits), _pl(target), _p(w_ce), _p(coef), _p(gscale), B, Cn, _i64(hw), C.byref(param), _p(dlogits),
+                                     _stream()), "segloss_ex_bwd")
+
+
+def image_stats(pred, target, n_classes, ignore_index, stats):
+    """stats [B, C, 4] int64 = tp, fp, fn, tn per image and class (lmn_image_stats).  pred: fp32 logits [B, C, H, W] or a uint8 label
+    map [B, H, W] (values >= C: no class); target int64 [B, H, W]; labels outside [0, C) are void."""
+    B = target.shape[0]
+    hw = target.numel() // B
+    logits = pred if pred.dim() == 4 else None
+    labels = pred if pred.dim() == 3 else None
+    if (logits is None) == (labels is None) or pred.shape[0] != B or pred.numel() != target.numel() * (n_classes if labels is None else 1):
+        raise ValueError("lm_net_amd.image_stats: pred %s does not match target %s with %d classes"
+                         % (tuple(pred.shape), tuple(target.shape), n_classes))
+    if logits is not None and not logits.is_contiguous():
+        raise ValueError("lm_net_amd.image_stats: contiguous logits required")
+    if stats.numel() != B * n_classes * 4:
+        raise ValueError("lm_net_amd.image_stats: stats must hold [%d, %d, 4] int64" % (B, n_classes))
+    _check(load().lmn_image_stats(_p(logits), _raw(labels, torch.uint8, "image_stats"), _pl(target), B, int(n_classes), _i64(hw),
+                                  0 if ignore_index is None else 1, _i64(0 if ignore_index is None else ignore_index),
+                                  _raw(stats, torch.int64, "image_stats"), _stream()), "image_stats")
 
 
 def surface_workspace(B, nk, H, W):

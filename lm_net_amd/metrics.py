@@ -11,7 +11,14 @@ GPU (one kernel per batch, no sync) and derives Dice ``2TP/(2TP+FP+FN)`` and IoU
 ``hausdorff_distance``, ``:178-179`` set up ``hausdorff_distance_list`` / ``rvd_list``, ``:14-52`` ``ravd`` / ``RVDEvaluator``) and
 never computes.  The device produces ten exact raw statistics per (sample, class) pair (``lmn_surface_dist``); ``compute()`` turns
 them into the metrics in float64 on the host.
+
+``ImageStatsMeter`` keeps tp / fp / fn / tn per IMAGE and class (``get_stats`` of ``utils/functional.py:61-201`` in mode
+"multiclass", with ``ignore_index``) and scores them with the metric set and the reductions of that file (``:237-358``), among them
+the ``*-imagewise`` ones; ``per_image`` gives the per-case scores behind a "mean +/- std over cases" column, which a pooled
+confusion matrix cannot.
 """
+import warnings
+
 import numpy as np
 import torch
 
@@ -59,6 +66,153 @@ class ConfusionMeter:
         out = dict(dice=dice, iou=iou, accuracy=float(tp.sum() / m.sum().clamp_min(1)), confusion=m.long().tolist())
         out.update(evaluator_metrics(m.numpy()))
         return out
+
+
+def _m_fbeta(tp, fp, fn, tn, beta=1.0):
+    return (1 + beta ** 2) * tp / ((1 + beta ** 2) * tp + beta ** 2 * fn + fp)
+
+
+def _m_sens(tp, fp, fn, tn):
+    return tp / (tp + fn)
+
+
+def _m_spec(tp, fp, fn, tn):
+    return tn / (tn + fp)
+
+
+def _m_fnr(tp, fp, fn, tn):
+    return fn / (fn + tp)
+
+
+def _m_fpr(tp, fp, fn, tn):
+    return fp / (fp + tn)
+
+
+# the metric functions of utils/functional.py:302-358 under its public names (and the short forms of a results table)
+STATS_METRICS = {
+    "fbeta": _m_fbeta, "f1": _m_fbeta, "iou": lambda tp, fp, fn, tn: tp / (tp + fp + fn),
+    "accuracy": lambda tp, fp, fn, tn: (tp + tn) / (tp + fp + fn + tn),
+    "precision": lambda tp, fp, fn, tn: tp / (tp + fp), "recall": _m_sens, "sensitivity": _m_sens, "specificity": _m_spec,
+    "balanced_accuracy": lambda tp, fp, fn, tn: (_m_sens(tp, fp, fn, tn) + _m_spec(tp, fp, fn, tn)) / 2,
+    "npv": lambda tp, fp, fn, tn: tn / (tn + fn), "fnr": _m_fnr, "fpr": _m_fpr,
+    "fdr": lambda tp, fp, fn, tn: 1 - tp / (tp + fp), "for": lambda tp, fp, fn, tn: 1 - tn / (tn + fn),
+    "positive_likelihood_ratio": lambda tp, fp, fn, tn: _m_sens(tp, fp, fn, tn) / _m_fpr(tp, fp, fn, tn),
+    "negative_likelihood_ratio": lambda tp, fp, fn, tn: _m_fnr(tp, fp, fn, tn) / _m_spec(tp, fp, fn, tn),
+}
+_ALIASES = {"f1_score": "f1", "fbeta_score": "fbeta", "iou_score": "iou", "positive_predictive_value": "precision",
+            "negative_predictive_value": "npv", "false_negative_rate": "fnr", "false_positive_rate": "fpr",
+            "false_discovery_rate": "fdr", "false_omission_rate": "for"}
+STATS_REDUCTIONS = ("micro", "macro", "weighted", "micro-imagewise", "macro-imagewise", "weighted-imagewise", "none")
+
+
+def _metric_fn(metric, beta):
+    name = _ALIASES.get(metric, metric)
+    if name not in STATS_METRICS:
+        raise ValueError("unknown metric %r (known: %s)" % (metric, ", ".join(sorted(STATS_METRICS))))
+    fn = STATS_METRICS[name]
+    return (lambda *a: fn(*a, beta=float(beta))) if name == "fbeta" else fn
+
+
+def _zero_div(x, zero_division):
+    nans = np.isnan(x)
+    if nans.any() and zero_division == "warn":
+        warnings.warn("Zero division in metric calculation!")
+    return np.where(nans, 0.0 if zero_division == "warn" else float(zero_division), x)
+
+
+def stats_score(tp, fp, fn, tn, metric, reduction="micro", class_weights=None, zero_division=1.0, beta=1.0):
+    """One metric of per-image statistics ([N, C] each) under one reduction, in float64: ``_compute_metric`` of
+    ``utils/functional.py:237-296`` as it stands there -- "micro" leaves a 0/0 as NaN, the class weights are normalised to sum 1 and
+    the weighted class scores are then AVERAGED (so "weighted" is 1/C of a weighted mean), and "none" returns the sum over images of
+    the class-mean score.  Only a 0/0 is replaced by ``zero_division``; x/0 stays inf."""
+    fnc = _metric_fn(metric, beta)
+    tp, fp, fn, tn = (np.asarray(a, dtype=np.float64) for a in (tp, fp, fn, tn))
+    if reduction not in STATS_REDUCTIONS and reduction is not None:
+        raise ValueError("reduction %r not in %s" % (reduction, STATS_REDUCTIONS))
+    if class_weights is None and reduction is not None and "weighted" in reduction:
+        raise ValueError("Class weights should be provided for `%s` reduction" % reduction)
+    cw = np.asarray(1.0 if class_weights is None else class_weights, dtype=np.float64)
+    cw = cw / cw.sum()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if reduction == "micro":
+            return float(fnc(tp.sum(), fp.sum(), fn.sum(), tn.sum()))
+        if reduction in ("macro", "weighted"):
+            return float((_zero_div(fnc(tp.sum(0), fp.sum(0), fn.sum(0), tn.sum(0)), zero_division) * cw).mean())
+        if reduction == "micro-imagewise":
+            return float(_zero_div(fnc(tp.sum(1), fp.sum(1), fn.sum(1), tn.sum(1)), zero_division).mean())
+        score = _zero_div(fnc(tp, fp, fn, tn), zero_division)
+        if reduction in ("macro-imagewise", "weighted-imagewise"):
+            return float((score.mean(0) * cw).mean())
+        return float(score.mean(1).sum())
+
+
+class ImageStatsMeter:
+    """tp, fp, fn, tn per image and class, accumulated on the device (``lmn_image_stats``: integer arithmetic, exact).
+
+    A pixel whose label lies outside [0, C) is void -- ``ignore_index`` (which must lie outside [0, C)) and any other out-of-range
+    value alike, as ``ConfusionMeter`` drops them (the reference's ``get_stats`` counts a stray label that is not ``ignore_index`` as a
+    false positive of the predicted class) -- and adds to none of the four, so tp + fp + fn + tn is the image's valid-pixel count for
+    every class.  update(pred, target): pred = fp32 logits [B, C, H, W] (arg-max, first maximum wins) or an integer label map
+    [B, H, W] (e.g. DevicePostprocess's labels_net; values outside [0, C) mean "no class"); the [B, C, 4] int64 result stays on the
+    device and nothing synchronises."""
+
+    def __init__(self, n_classes, ignore_index=None, device="cuda"):
+        if not 2 <= n_classes <= 64:
+            raise ValueError("ImageStatsMeter: n_classes = %d outside [2, 64]" % n_classes)
+        if ignore_index is not None and 0 <= int(ignore_index) < n_classes:
+            raise ValueError("ImageStatsMeter: ignore_index = %d lies inside [0, %d)" % (ignore_index, n_classes))
+        self.n, self.ignore_index, self.device = n_classes, None if ignore_index is None else int(ignore_index), torch.device(device)
+        self._stats = []
+
+    def reset(self):
+        self._stats = []
+
+    @torch.no_grad()
+    def update(self, pred, target):
+        if not pred.is_cuda or not target.is_cuda:
+            raise RuntimeError("lm_net_amd.ImageStatsMeter: device tensors required (the HIP path has no CPU fallback)")
+        if pred.dim() == 4:
+            if pred.shape[1] != self.n:
+                raise ValueError("ImageStatsMeter: logits with %d channels, n_classes = %d" % (pred.shape[1], self.n))
+            pred = pred.contiguous().float()
+        elif pred.dim() == 3 and not pred.is_floating_point():
+            if pred.dtype not in (torch.uint8, torch.bool):
+                pred = pred.clamp(-1, 255)                       # (-1 -> 255: no class)
+            pred = pred.to(torch.uint8).contiguous()
+        else:
+            raise ValueError("ImageStatsMeter: pred must be logits [B, C, H, W] or an integer label map [B, H, W]")
+        target = target.contiguous().long()
+        if target.dim() != 3 or target.shape[0] != pred.shape[0] or target.shape[-2:] != pred.shape[-2:]:
+            raise ValueError("ImageStatsMeter: target %s does not match pred %s" % (tuple(target.shape), tuple(pred.shape)))
+        stats = torch.empty(target.shape[0], self.n, 4, device=pred.device, dtype=torch.int64)
+        hip.image_stats(pred, target, self.n, self.ignore_index, stats)
+        self._stats.append(stats)
+
+    def add_raw(self, stats):
+        """Append raw statistics [N, C, 4] int64 (tp, fp, fn, tn), e.g. another rank's raw()."""
+        if stats.dim() != 3 or tuple(stats.shape[1:]) != (self.n, 4):
+            raise ValueError("ImageStatsMeter.add_raw: shape %s" % (tuple(stats.shape),))
+        self._stats.append(stats.to(self.device, torch.int64))
+
+    def raw(self):
+        """The statistics so far, in update order: int64 [N, C, 4] on the device."""
+        return torch.cat(self._stats) if self._stats else torch.zeros(0, self.n, 4, device=self.device, dtype=torch.int64)
+
+    def stats(self):
+        """tp, fp, fn, tn as four [N, C] int64 host tensors (synchronises)."""
+        r = self.raw().cpu()
+        return r[..., 0], r[..., 1], r[..., 2], r[..., 3]
+
+    def score(self, metric, reduction="micro", class_weights=None, zero_division=1.0, beta=1.0):
+        """stats_score of everything seen so far: float64 on the host."""
+        tp, fp, fn, tn = (a.numpy() for a in self.stats())
+        return stats_score(tp, fp, fn, tn, metric, reduction, class_weights, zero_division, beta)
+
+    def per_image(self, metric, zero_division=1.0, beta=1.0):
+        """The [N, C] float64 scores of one metric per image and class (0/0 -> zero_division): mean +/- std over cases from these."""
+        tp, fp, fn, tn = (a.numpy().astype(np.float64) for a in self.stats())
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _zero_div(_metric_fn(metric, beta)(tp, fp, fn, tn), zero_division)
 
 
 class SurfaceDistanceMeter:
