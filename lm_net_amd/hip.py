@@ -170,6 +170,25 @@ def loss_coef_floats(n_classes):
     return 4 + 2 * int(n_classes)
 
 
+class SigParam(C.Structure):
+    """Mirror of lmn_sig_param_t (include/lmnet_sigmoid.h): the scalar parameters of lmn_sigloss_fwd / _bwd."""
+    _fields_ = [("smooth", C.c_float), ("bce_scale", C.c_float), ("dice_scale", C.c_float), ("focal_scale", C.c_float),
+                ("focal_gamma", C.c_float), ("focal_alpha", C.c_float), ("target_kind", C.c_int32), ("_pad", C.c_int32 * 9)]
+
+
+SIG_T_U8, SIG_T_I64 = 0, 1      # LMN_SIG_T_* of include/lmnet_sigmoid.h
+
+
+def sig_sums_words(n_classes):
+    """LMN_SIG_SUMS_WORDS of include/lmnet_sigmoid.h: 4-byte words of the `sums` workspace of sigloss_fwd."""
+    return 6 * int(n_classes)
+
+
+def sig_coef_floats(n_classes):
+    """LMN_SIG_COEF_FLOATS of include/lmnet_sigmoid.h: floats of the `coef` workspace shared by sigloss_fwd / _bwd."""
+    return 4 * int(n_classes)
+
+
 class PostParam(C.Structure):
     """Mirror of lmn_post_param_t: the cleaning parameters of lmn_post_clean (lm_net_amd.post.DevicePostprocess)."""
     _fields_ = [("connectivity", C.c_int32), ("hole_limit", C.c_int32), ("class_mask", C.c_uint64), ("keep_largest_mask", C.c_uint64),
@@ -198,6 +217,10 @@ SYMBOLS_ONEOF = ["lmn_sizeof_oneof_param", "lmn_oneof_workspace", "lmn_augment_o
 # the same reason, guarded by tests/test_guard_loss_gpu.py.
 SYMBOLS_LOSS = ["lmn_sizeof_loss_param", "lmn_segloss_ex_fwd", "lmn_segloss_ex_bwd", "lmn_image_stats"]
 
+# every symbol include/lmnet_sigmoid.h declares (the loss and the statistics of sigmoid heads); apart from SYMBOLS for the same reason,
+# guarded by tests/test_guard_sigmoid_gpu.py.
+SYMBOLS_SIGMOID = ["lmn_sizeof_sig_param", "lmn_sigloss_fwd", "lmn_sigloss_bwd", "lmn_sigmoid_stats"]
+
 _lib = None
 
 
@@ -211,7 +234,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in SYMBOLS + SYMBOLS_ONEOF + SYMBOLS_LOSS:
+    for name in SYMBOLS + SYMBOLS_ONEOF + SYMBOLS_LOSS + SYMBOLS_SIGMOID:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -229,7 +252,8 @@ def load():
     if (lib.lmn_sizeof_conv_args() != C.sizeof(ConvArgs) or lib.lmn_sizeof_src() != C.sizeof(SrcT)
             or lib.lmn_sizeof_wgrad_args() != C.sizeof(WgradArgs) or lib.lmn_sizeof_reduce_job() != C.sizeof(ReduceJob)
             or lib.lmn_sizeof_aug_param() != C.sizeof(AugParam) or lib.lmn_sizeof_post_param() != C.sizeof(PostParam)
-            or lib.lmn_sizeof_oneof_param() != C.sizeof(OneOfParam) or lib.lmn_sizeof_loss_param() != C.sizeof(LossParam)):
+            or lib.lmn_sizeof_oneof_param() != C.sizeof(OneOfParam) or lib.lmn_sizeof_loss_param() != C.sizeof(LossParam)
+            or lib.lmn_sizeof_sig_param() != C.sizeof(SigParam)):
         raise RuntimeError("lm_net_amd: argument struct layout differs between hip.py and lmnet_hip.h")
     _lib = lib
     return lib
@@ -1051,6 +1075,85 @@ def image_stats(pred, target, n_classes, ignore_index, stats):
     _check(load().lmn_image_stats(_p(logits), _raw(labels, torch.uint8, "image_stats"), _pl(target), B, int(n_classes), _i64(hw),
                                   0 if ignore_index is None else 1, _i64(0 if ignore_index is None else ignore_index),
                                   _raw(stats, torch.int64, "image_stats"), _stream()), "image_stats")
+
+
+def sig_param(smooth=1e-5, bce_scale=1.0, dice_scale=1.0, focal_scale=0.0, focal_gamma=2.0, focal_alpha=0.25, target_kind=SIG_T_I64):
+    """A SigParam (lmn_sig_param_t) from Python values."""
+    p = SigParam()
+    p.smooth, p.bce_scale, p.dice_scale, p.focal_scale = float(smooth), float(bce_scale), float(dice_scale), float(focal_scale)
+    p.focal_gamma, p.focal_alpha, p.target_kind = float(focal_gamma), float(focal_alpha), int(target_kind)
+    return p
+
+
+def sig_target_kind(target):
+    """LMN_SIG_T_* of a target tensor: uint8 or int64."""
+    if target.dtype == torch.uint8:
+        return SIG_T_U8
+    if target.dtype == torch.int64:
+        return SIG_T_I64
+    raise ValueError("lm_net_amd: sigmoid targets are uint8 or int64, got %s" % target.dtype)
+
+
+def sig_logit_threshold(threshold):
+    """log(thr / (1 - thr)) in float64, rounded to fp32: the logit at which sigmoid crosses thr (exactly 0 at 0.5)."""
+    thr = float(threshold)
+    if not 0.0 < thr < 1.0:
+        raise ValueError("lm_net_amd: threshold = %g outside (0, 1)" % thr)
+    return float(np.float32(np.log(np.float64(thr) / (1.0 - np.float64(thr)))))
+
+
+def _sig_dims(logits, target, what):
+    B, Cn = logits.shape[0], logits.shape[1]
+    hw = logits.numel() // max(B * Cn, 1)
+    if logits.dim() < 3 or not logits.is_contiguous():
+        raise ValueError("lm_net_amd.%s: contiguous logits [B, C, ...] required" % what)
+    if target is not None and (target.numel() != logits.numel() or not target.is_contiguous() or not target.is_cuda):
+        raise ValueError("lm_net_amd.%s: target %s does not match logits %s (contiguous device tensor of the same size)"
+                         % (what, tuple(target.shape), tuple(logits.shape)))
+    return B, Cn, hw
+
+
+def sigloss_fwd(logits, target, w_bce, pos_weight, w_dice, param, sums, coef, loss4):
+    """loss4 = [total, bce, dice, focal] of fp32 logits [B, C, ...] against a uint8 / int64 target of the same size, every class a
+    binary problem of its own (lmn_sigloss_fwd); param: a SigParam whose target_kind matches the target; sums: int32 workspace of at
+    least sig_sums_words(C); coef: fp32 workspace of at least sig_coef_floats(C)."""
+    B, Cn, hw = _sig_dims(logits, target, "sigloss_fwd")
+    if param.target_kind != sig_target_kind(target):
+        raise ValueError("lm_net_amd.sigloss_fwd: param.target_kind does not match the target's dtype %s" % target.dtype)
+    if sums.numel() < sig_sums_words(Cn) or coef.numel() < sig_coef_floats(Cn) or loss4.numel() < 4:
+        raise ValueError("lm_net_amd.sigloss_fwd: workspace too small for %d classes" % Cn)
+    if min(w_bce.numel(), pos_weight.numel(), w_dice.numel()) < Cn:
+        raise ValueError("lm_net_amd.sigloss_fwd: a weight vector is shorter than %d classes" % Cn)
+    _check(load().lmn_sigloss_fwd(_p(logits), C.c_void_p(target.data_ptr()), _p(w_bce), _p(pos_weight), _p(w_dice), B, Cn, _i64(hw),
+                                  C.byref(param), _raw(sums, torch.int32, "sigloss_fwd"), _p(coef), _p(loss4), _stream()), "sigloss_fwd")
+
+
+def sigloss_bwd(logits, target, pos_weight, coef, gscale, param, dlogits):
+    """dlogits = gscale[0] * d total / d logits (gscale None: 1) from the coef of sigloss_fwd (lmn_sigloss_bwd)."""
+    B, Cn, hw = _sig_dims(logits, target, "sigloss_bwd")
+    if param.target_kind != sig_target_kind(target):
+        raise ValueError("lm_net_amd.sigloss_bwd: param.target_kind does not match the target's dtype %s" % target.dtype)
+    if coef.numel() < sig_coef_floats(Cn) or dlogits.numel() != logits.numel() or pos_weight.numel() < Cn:
+        raise ValueError("lm_net_amd.sigloss_bwd: coef, pos_weight or dlogits does not match %d classes" % Cn)
+    _check(load().lmn_sigloss_bwd(_p(logits), C.c_void_p(target.data_ptr()), _p(pos_weight), _p(coef), _p(gscale), B, Cn, _i64(hw),
+                                  C.byref(param), _p(dlogits), _stream()), "sigloss_bwd")
+
+
+def sigmoid_stats(logits, target, logit_threshold, stats=None, labels_out=None):
+    """Thresholded statistics and / or label maps of fp32 logits [B, C, ...] (lmn_sigmoid_stats): stats int64 [B, C, 4] = tp, fp, fn,
+    tn over the valid elements (target 0 or 1) of each plane, overwritten; labels_out uint8 of the logits' size = (z >= logit_threshold).
+    target: uint8 or int64 of the logits' size, or None for the label maps alone."""
+    B, Cn, hw = _sig_dims(logits, target, "sigmoid_stats")
+    if stats is None and labels_out is None:
+        raise ValueError("lm_net_amd.sigmoid_stats: at least one of stats and labels_out must be given")
+    if stats is not None and (target is None or stats.numel() != B * Cn * 4):
+        raise ValueError("lm_net_amd.sigmoid_stats: stats needs a target and must hold [%d, %d, 4] int64" % (B, Cn))
+    if labels_out is not None and labels_out.numel() != logits.numel():
+        raise ValueError("lm_net_amd.sigmoid_stats: labels_out must hold one uint8 per logit")
+    kind = SIG_T_U8 if target is None else sig_target_kind(target)
+    _check(load().lmn_sigmoid_stats(_p(logits), None if target is None else C.c_void_p(target.data_ptr()), kind, _f(logit_threshold),
+                                    B, Cn, _i64(hw), _raw(stats, torch.int64, "sigmoid_stats"),
+                                    _raw(labels_out, torch.uint8, "sigmoid_stats"), _stream()), "sigmoid_stats")
 
 
 def surface_workspace(B, nk, H, W):

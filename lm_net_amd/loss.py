@@ -148,3 +148,96 @@ class FocalLoss(SegLoss):
         if logits.shape[1] != self.num_classes:
             raise ValueError("FocalLoss: %d classes in the logits, num_classes = %d" % (logits.shape[1], self.num_classes))
         return super().forward(logits, target)
+
+
+class _SigmoidSegLossFn(torch.autograd.Function):
+    """The loss entries of include/lmnet_sigmoid.h.  `holder.terms` receives the device tensor [total, bce, dice, focal]."""
+
+    @staticmethod
+    def forward(ctx, logits, target, w_bce, pos_weight, w_dice, param, holder):
+        Cn = logits.shape[1]
+        sums = torch.empty(hip.sig_sums_words(Cn), device=logits.device, dtype=torch.int32)
+        coef = torch.empty(hip.sig_coef_floats(Cn), device=logits.device)
+        loss4 = torch.empty(4, device=logits.device)
+        hip.sigloss_fwd(logits, target, w_bce, pos_weight, w_dice, param, sums, coef, loss4)
+        ctx.save_for_backward(logits, target, pos_weight, coef)
+        ctx.param = param
+        holder.terms = loss4
+        return loss4[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, pos_weight, coef = ctx.saved_tensors
+        d = torch.empty_like(logits)
+        hip.sigloss_bwd(logits, target, pos_weight, coef, g.reshape(1).contiguous().float(), ctx.param, d)
+        return d, None, None, None, None, None, None
+
+
+class SigmoidSegLoss(torch.nn.Module):
+    """BCE + Dice (+ focal) for sigmoid heads: one-logit binary models and multi-label models, every class a binary problem of its own.
+
+    ``bce_scale * F.binary_cross_entropy_with_logits(z, t, weight=bce_weight, pos_weight=pos_weight)`` (weights per class, mean over the
+    valid elements) ``+ dice_scale *`` the reference's ``DiceLoss._dice_loss(sigmoid(z[:, c]), t[:, c], ignore_c)`` weighted by
+    ``dice_weight`` and averaged over classes as ``DiceLoss.forward`` does (``utils/loss.py:183-206``) ``+ focal_scale *`` the
+    reference's ``FocalLoss`` (``utils/loss.py:126-148``), each class's mean taken over its valid elements.
+
+    logits ``[B, C, H, W]`` with 1 <= C <= 64; target ``[B, C, H, W]`` -- or ``[B, H, W]`` / ``[B, 1, H, W]`` when C = 1 -- of dtype
+    uint8, bool (taken as uint8) or int64, e.g. the int64 {0, 1} masks of ``DevicePreprocess`` / ``DeviceAugment(mask_mode="binary")``
+    as they are.  An element is valid when its target is 0 or 1; every other value (255, -100, ...) is void for that element alone: it
+    adds to no sum and receives a zero gradient, which also covers a class that is not annotated in some image.  Soft (floating-point)
+    targets are out of scope.  ``None`` weights mean all ones, sized from the logits.  ``terms`` holds the device tensor
+    ``[total, bce, dice, focal]`` of the last call; nothing synchronises.  Deliberate difference from torch: without a valid element
+    the BCE term and its gradient are 0, and a class without a valid element adds 0 to the focal term (torch: NaN)."""
+
+    MAX_CLASSES = 64
+
+    def __init__(self, bce_weight=None, pos_weight=None, dice_weight=None, smooth=1e-5, bce_scale=1.0, dice_scale=1.0, focal_scale=0.0,
+                 focal_gamma=2.0, focal_alpha=0.25):
+        super().__init__()
+        if min(bce_scale, dice_scale, focal_scale) < 0:
+            raise ValueError("SigmoidSegLoss: negative scale (bce %g, dice %g, focal %g)" % (bce_scale, dice_scale, focal_scale))
+        if focal_gamma < 0 or focal_alpha > 1:
+            raise ValueError("SigmoidSegLoss: focal_gamma = %g must be >= 0 and focal_alpha = %g <= 1" % (focal_gamma, focal_alpha))
+        if smooth < 0:
+            raise ValueError("SigmoidSegLoss: smooth = %g is negative" % smooth)
+        self.args = (float(smooth), float(bce_scale), float(dice_scale), float(focal_scale), float(focal_gamma), float(focal_alpha))
+        self.terms = None
+        for name, w in (("bce_weight", bce_weight), ("pos_weight", pos_weight), ("dice_weight", dice_weight)):
+            w = None if w is None else torch.as_tensor(w, dtype=torch.float32).reshape(-1).clone()
+            if w is not None and not 1 <= w.numel() <= self.MAX_CLASSES:
+                raise ValueError("SigmoidSegLoss: %d %s entries; the loss takes 1..%d classes" % (w.numel(), name, self.MAX_CLASSES))
+            self.register_buffer(name, w)
+
+    def _weight(self, w, Cn, dev, what):
+        if w is None:
+            return torch.ones(Cn, device=dev, dtype=torch.float32)
+        if w.numel() != Cn:
+            raise ValueError("SigmoidSegLoss: %d classes in the logits, %d %s weights" % (Cn, w.numel(), what))
+        return w.to(dev)
+
+    def forward(self, logits, target):
+        if logits.dim() != 4:
+            raise ValueError("SigmoidSegLoss: logits must be [B, C, H, W], got %s" % (tuple(logits.shape),))
+        B, Cn, H, W = logits.shape
+        if not 1 <= Cn <= self.MAX_CLASSES:
+            raise ValueError("SigmoidSegLoss: %d classes in the logits; the loss takes 1..%d" % (Cn, self.MAX_CLASSES))
+        if target.is_floating_point():
+            raise ValueError("SigmoidSegLoss: floating-point (soft) targets are not supported; pass uint8, bool or int64, got %s" % target.dtype)
+        if target.dtype == torch.bool:
+            target = target.to(torch.uint8)
+        if target.dtype not in (torch.uint8, torch.int64):
+            raise ValueError("SigmoidSegLoss: target must be uint8, bool or int64, got %s" % target.dtype)
+        ok = tuple(target.shape) == (B, Cn, H, W) or (Cn == 1 and tuple(target.shape) == (B, H, W))
+        if not ok:
+            raise ValueError("SigmoidSegLoss: target %s does not match logits %s ([B, C, H, W], or [B, H, W] when C = 1)"
+                             % (tuple(target.shape), tuple(logits.shape)))
+        if B * Cn > 65535 or H * W >= 1 << 31 or B * H * W >= 1 << 31:
+            raise ValueError("SigmoidSegLoss: B * C = %d, H * W = %d beyond the limits B * C <= 65535, H * W < 2^31, B * H * W < 2^31"
+                             % (B * Cn, H * W))
+        w_bce = self._weight(self.bce_weight, Cn, logits.device, "bce")
+        pos_w = self._weight(self.pos_weight, Cn, logits.device, "pos")
+        w_dice = self._weight(self.dice_weight, Cn, logits.device, "dice")
+        if not logits.is_cuda or not target.is_cuda:
+            raise RuntimeError("lm_net_amd.SigmoidSegLoss: device tensors required (the HIP path has no CPU fallback)")
+        param = hip.sig_param(*self.args, target_kind=hip.sig_target_kind(target))
+        return _SigmoidSegLossFn.apply(logits.float().contiguous(), target.contiguous(), w_bce, pos_w, w_dice, param, self)

@@ -146,7 +146,41 @@ def stats_score(tp, fp, fn, tn, metric, reduction="micro", class_weights=None, z
         return float(score.mean(1).sum())
 
 
-class ImageStatsMeter:
+class _RawStatsMeter:
+    """What the statistics meters share: a list of raw [N, C, 4] int64 device tensors (tp, fp, fn, tn per image and class) and their
+    scores.  A subclass sets ``n`` and ``device`` and appends to ``_stats`` in its update()."""
+
+    def reset(self):
+        self._stats = []
+
+    def add_raw(self, stats):
+        """Append raw statistics [N, C, 4] int64 (tp, fp, fn, tn), e.g. another rank's raw()."""
+        if stats.dim() != 3 or tuple(stats.shape[1:]) != (self.n, 4):
+            raise ValueError("%s.add_raw: shape %s" % (type(self).__name__, tuple(stats.shape)))
+        self._stats.append(stats.to(self.device, torch.int64))
+
+    def raw(self):
+        """The statistics so far, in update order: int64 [N, C, 4] on the device."""
+        return torch.cat(self._stats) if self._stats else torch.zeros(0, self.n, 4, device=self.device, dtype=torch.int64)
+
+    def stats(self):
+        """tp, fp, fn, tn as four [N, C] int64 host tensors (synchronises)."""
+        r = self.raw().cpu()
+        return r[..., 0], r[..., 1], r[..., 2], r[..., 3]
+
+    def score(self, metric, reduction="micro", class_weights=None, zero_division=1.0, beta=1.0):
+        """stats_score of everything seen so far: float64 on the host."""
+        tp, fp, fn, tn = (a.numpy() for a in self.stats())
+        return stats_score(tp, fp, fn, tn, metric, reduction, class_weights, zero_division, beta)
+
+    def per_image(self, metric, zero_division=1.0, beta=1.0):
+        """The [N, C] float64 scores of one metric per image and class (0/0 -> zero_division): mean +/- std over cases from these."""
+        tp, fp, fn, tn = (a.numpy().astype(np.float64) for a in self.stats())
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _zero_div(_metric_fn(metric, beta)(tp, fp, fn, tn), zero_division)
+
+
+class ImageStatsMeter(_RawStatsMeter):
     """tp, fp, fn, tn per image and class, accumulated on the device (``lmn_image_stats``: integer arithmetic, exact).
 
     A pixel whose label lies outside [0, C) is void -- ``ignore_index`` (which must lie outside [0, C)) and any other out-of-range
@@ -162,9 +196,6 @@ class ImageStatsMeter:
         if ignore_index is not None and 0 <= int(ignore_index) < n_classes:
             raise ValueError("ImageStatsMeter: ignore_index = %d lies inside [0, %d)" % (ignore_index, n_classes))
         self.n, self.ignore_index, self.device = n_classes, None if ignore_index is None else int(ignore_index), torch.device(device)
-        self._stats = []
-
-    def reset(self):
         self._stats = []
 
     @torch.no_grad()
@@ -188,31 +219,76 @@ class ImageStatsMeter:
         hip.image_stats(pred, target, self.n, self.ignore_index, stats)
         self._stats.append(stats)
 
-    def add_raw(self, stats):
-        """Append raw statistics [N, C, 4] int64 (tp, fp, fn, tn), e.g. another rank's raw()."""
-        if stats.dim() != 3 or tuple(stats.shape[1:]) != (self.n, 4):
-            raise ValueError("ImageStatsMeter.add_raw: shape %s" % (tuple(stats.shape),))
-        self._stats.append(stats.to(self.device, torch.int64))
 
-    def raw(self):
-        """The statistics so far, in update order: int64 [N, C, 4] on the device."""
-        return torch.cat(self._stats) if self._stats else torch.zeros(0, self.n, 4, device=self.device, dtype=torch.int64)
+def _sigmoid_inputs(logits, target, n_classes, what):
+    """logits fp32 contiguous [B, C, H, W]; target uint8 / int64 contiguous of the same size (bool -> uint8; [B, H, W] when C = 1)."""
+    if logits.dim() != 4 or not logits.is_floating_point():
+        raise ValueError("%s: logits must be floating-point [B, C, H, W], got %s %s" % (what, logits.dtype, tuple(logits.shape)))
+    B, Cn, H, W = logits.shape
+    if not 1 <= Cn <= 64 or (n_classes is not None and Cn != n_classes):
+        raise ValueError("%s: logits with %d channels, n_classes = %s (1..64)" % (what, Cn, n_classes))
+    if B * Cn > 65535 or B * H * W >= 1 << 31:
+        raise ValueError("%s: B * C = %d, B * H * W = %d beyond the limits B * C <= 65535, B * H * W < 2^31" % (what, B * Cn, B * H * W))
+    if not logits.is_cuda or (target is not None and not target.is_cuda):
+        raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % what)
+    if target is not None:
+        if target.is_floating_point():
+            raise ValueError("%s: the target must be uint8, bool or int64, got %s" % (what, target.dtype))
+        if target.dtype == torch.bool:
+            target = target.to(torch.uint8)
+        elif target.dtype not in (torch.uint8, torch.int64):
+            target = target.long()
+        if tuple(target.shape) != (B, Cn, H, W) and not (Cn == 1 and tuple(target.shape) == (B, H, W)):
+            raise ValueError("%s: target %s does not match logits %s" % (what, tuple(target.shape), tuple(logits.shape)))
+        target = target.contiguous()
+    return logits.float().contiguous(), target
 
-    def stats(self):
-        """tp, fp, fn, tn as four [N, C] int64 host tensors (synchronises)."""
-        r = self.raw().cpu()
-        return r[..., 0], r[..., 1], r[..., 2], r[..., 3]
 
-    def score(self, metric, reduction="micro", class_weights=None, zero_division=1.0, beta=1.0):
-        """stats_score of everything seen so far: float64 on the host."""
-        tp, fp, fn, tn = (a.numpy() for a in self.stats())
-        return stats_score(tp, fp, fn, tn, metric, reduction, class_weights, zero_division, beta)
+@torch.no_grad()
+def sigmoid_labels(logits, threshold=0.5):
+    """uint8 [B, C, H, W]: 1 where sigmoid(logits) >= threshold -- compared as logits >= log(thr / (1 - thr)) in fp32 -- else 0
+    (``lmn_sigmoid_stats``, no synchronisation).  Viewed as [B * C, H, W] these are ordinary two-class label maps for
+    ``ConfusionMeter(2)``, ``SurfaceDistanceMeter(2)`` and ``DevicePostprocess(2)``."""
+    lt = hip.sig_logit_threshold(threshold)
+    logits, _ = _sigmoid_inputs(logits, None, None, "sigmoid_labels")
+    out = torch.empty(logits.shape, device=logits.device, dtype=torch.uint8)
+    hip.sigmoid_stats(logits, None, lt, None, out)
+    return out
 
-    def per_image(self, metric, zero_division=1.0, beta=1.0):
-        """The [N, C] float64 scores of one metric per image and class (0/0 -> zero_division): mean +/- std over cases from these."""
-        tp, fp, fn, tn = (a.numpy().astype(np.float64) for a in self.stats())
-        with np.errstate(divide="ignore", invalid="ignore"):
-            return _zero_div(_metric_fn(metric, beta)(tp, fp, fn, tn), zero_division)
+
+class SigmoidStatsMeter(_RawStatsMeter):
+    """tp, fp, fn, tn per image and class of a sigmoid head -- a one-logit binary model or a multi-label one -- accumulated on the
+    device (``lmn_sigmoid_stats``: integer arithmetic, exact): ``get_stats`` of ``utils/functional.py:61-219`` in the modes "binary"
+    and "multilabel" on ``sigmoid(logits)`` with ``threshold``, away from rounding ties.
+
+    An element is predicted on when ``logits >= log(threshold / (1 - threshold))`` (fp32; exactly 0 at 0.5).  An element whose target
+    is neither 0 nor 1 is void and adds to none of the four, so tp + fp + fn + tn is the valid count of its (image, class) plane.
+    update(logits, target): logits [B, C, H, W]; target of the same shape ([B, H, W] when C = 1), uint8, bool or int64; the [B, C, 4]
+    int64 result stays on the device and nothing synchronises.  Scores are those of ``ImageStatsMeter``."""
+
+    def __init__(self, n_classes, threshold=0.5, device="cuda"):
+        if not 1 <= n_classes <= 64:
+            raise ValueError("SigmoidStatsMeter: n_classes = %d outside [1, 64]" % n_classes)
+        if not 0.0 < float(threshold) < 1.0:
+            raise ValueError("SigmoidStatsMeter: threshold = %g outside (0, 1)" % threshold)
+        self.n, self.threshold, self.device = n_classes, float(threshold), torch.device(device)
+        self.logit_threshold = hip.sig_logit_threshold(threshold)
+        self._stats = []
+
+    @torch.no_grad()
+    def update(self, logits, target):
+        logits, target = _sigmoid_inputs(logits, target, self.n, "SigmoidStatsMeter")
+        stats = torch.empty(logits.shape[0], self.n, 4, device=logits.device, dtype=torch.int64)
+        hip.sigmoid_stats(logits, target, self.logit_threshold, stats, None)
+        self._stats.append(stats)
+
+    @torch.no_grad()
+    def labels(self, logits):
+        """The thresholded uint8 [B, C, H, W] maps of the logits (sigmoid_labels at the meter's threshold)."""
+        logits, _ = _sigmoid_inputs(logits, None, self.n, "SigmoidStatsMeter")
+        out = torch.empty(logits.shape, device=logits.device, dtype=torch.uint8)
+        hip.sigmoid_stats(logits, None, self.logit_threshold, None, out)
+        return out
 
 
 class SurfaceDistanceMeter:
