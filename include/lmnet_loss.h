@@ -1,7 +1,7 @@
 /* Void (ignore) labels in the training loss, a focal term, and per-image tp / fp / fn / tn statistics: the entries of
  * liblmnet_hip.so behind lm_net_amd.SegLoss(ignore_index=..., focal_scale=...), lm_net_amd.FocalLoss and lm_net_amd.ImageStatsMeter.
- * Kept apart from lmnet_hip.h, whose declarations are frozen at ABI 15 by the export and guard-manifest checks; these symbols are
- * additive, listed in lm_net_amd.hip.SYMBOLS_LOSS and guarded by tests/test_guard_loss_gpu.py.
+ * One header per feature: these symbols are listed in lm_net_amd.hip.SYMBOLS_LOSS, which lm_net_amd.hip.HEADERS files under this
+ * header's name, and the guard manifest (tests/guard.py) ties them to tests/test_guard_loss_gpu.py.
  *
  * A pixel is VALID when its label y lies in [0, C); every other label is void: ignore_index (which must lie outside [0, C), e.g. the
  * 255 of VOC2012 or torch's -100) and any other out-of-range value alike, in line with the confusion entry of lmnet_hip.h, which

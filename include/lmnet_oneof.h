@@ -1,7 +1,7 @@
 /* The OneOf block of the training augmentations (dataset/data_loading.py:215-225) on the device: the entries of liblmnet_hip.so
- * behind lm_net_amd.data.DeviceAugment(one_of=...).  Kept apart from lmnet_hip.h, whose declarations are frozen at ABI 15 by the
- * export and guard-manifest checks; these symbols are additive, listed in lm_net_amd.hip.SYMBOLS_ONEOF and guarded by
- * tests/test_guard_oneof_gpu.py.                                                                                              */
+ * behind lm_net_amd.data.DeviceAugment(one_of=...).  One header per feature: these symbols are listed in
+ * lm_net_amd.hip.SYMBOLS_ONEOF, which lm_net_amd.hip.HEADERS files under this header's name, and the guard manifest
+ * (tests/guard.py) ties them to tests/test_guard_oneof_gpu.py.                                                                */
 #ifndef LMNET_ONEOF_H
 #define LMNET_ONEOF_H
 #include "lmnet_hip.h"

@@ -1,7 +1,7 @@
 /* Sigmoid heads: a per-class binary loss (BCE + Dice + focal) and thresholded tp / fp / fn / tn statistics for one-logit (binary) and
  * multi-label models: the entries of liblmnet_hip.so behind lm_net_amd.SigmoidSegLoss, lm_net_amd.SigmoidStatsMeter and
- * lm_net_amd.metrics.sigmoid_labels.  Kept apart from lmnet_hip.h, whose declarations are frozen at ABI 15 by the export and
- * guard-manifest checks; these symbols are additive, listed in lm_net_amd.hip.SYMBOLS_SIGMOID and guarded by
+ * lm_net_amd.metrics.sigmoid_labels.  One header per feature: these symbols are listed in lm_net_amd.hip.SYMBOLS_SIGMOID, which
+ * lm_net_amd.hip.HEADERS files under this header's name, and the guard manifest (tests/guard.py) ties them to
  * tests/test_guard_sigmoid_gpu.py.
  *
  * Logits are fp32 NCHW [B, C, HW] with C in [1, 64]; the target has the same shape and is uint8 (target_kind LMN_SIG_T_U8) or int64

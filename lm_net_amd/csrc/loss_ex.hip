@@ -7,46 +7,13 @@
 //         [4+c] a_c  [4+C+c] b_c   with dL_dice/dp_c = a_c*t_c + b_c*p_c
 // A pixel is valid when 0 <= y < C.  ignore_index lies outside [0, C) (checked by the entries), so that one unsigned compare covers
 // it and every other out-of-range label.
-#include "common.h"
+#include "loss_common.h"
 #include "../../include/lmnet_loss.h"
 
 namespace {
 
 constexpr int LX_STRIDE = 65;   // row stride of the staged tile of the general sums kernel (conflict-free row reads)
 constexpr int LX_MAXC = 64;
-
-struct FocalK { float gamma, alpha; };   // alpha < 0: no alpha weighting
-
-__device__ __forceinline__ float lx_wave_sum(float v) {
-#pragma unroll
-  for (int m = 1; m <= 32; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// One class of the sigmoid focal loss at logit z with target t (true: this is the pixel's class).  With s = +z for t, -z otherwise,
-// q_t = sigmoid(s):  -log q_t = max(-s, 0) + l  and  log(1 - q_t) = -(max(s, 0) + l),  l = log1p(exp(-|s|)) -- one softplus, no
-// cancellation at large |z|, no overflow.  gamma = 0: exp(0) = 1 exactly.
-__device__ __forceinline__ float focal_value(float z, bool t, FocalK k) {
-  const float s = t ? z : -z;
-  const float l = log1pf(expf(-fabsf(s)));
-  const float bce = fmaxf(-s, 0.f) + l;
-  const float l1 = -(fmaxf(s, 0.f) + l);
-  const float at = k.alpha < 0.f ? 1.f : (t ? k.alpha : 1.f - k.alpha);
-  return at * expf(k.gamma * l1) * bce;
-}
-// d focal_value / dz = (2t - 1) * a_t * (1 - q_t)^gamma * [-gamma * q_t * bce - (1 - q_t)]
-__device__ __forceinline__ float focal_grad(float z, bool t, FocalK k) {
-  const float s = t ? z : -z;
-  const float e = expf(-fabsf(s));
-  const float l = log1pf(e);
-  const float r = 1.f / (1.f + e);
-  const float qt = s >= 0.f ? r : e * r, omq = s >= 0.f ? e * r : r;
-  const float bce = fmaxf(-s, 0.f) + l;
-  const float l1 = -(fmaxf(s, 0.f) + l);
-  const float at = k.alpha < 0.f ? 1.f : (t ? k.alpha : 1.f - k.alpha);
-  const float ds = at * expf(k.gamma * l1) * (-k.gamma * qt * bce - omq);
-  return t ? ds : -ds;
-}
 
 template <int C>
 __device__ __forceinline__ void lx_softmax(const float (&z)[C], float (&p)[C], float& lse) {
@@ -95,7 +62,7 @@ __global__ __launch_bounds__(256) void segloss_ex_sums_kernel(const float* __res
       acc[4 + c] += p[c] * t;
       acc[4 + C + c] += p[c] * p[c];
       acc[4 + 2 * C + c] += t;
-      if (FOCAL) acc[3] += focal_value(z[c], c == y, fk);
+      if (FOCAL) acc[3] += focal_value(sig_point(z[c]), c == y, fk);
     }
     acc[2] += sm;
   }
@@ -103,7 +70,7 @@ __global__ __launch_bounds__(256) void segloss_ex_sums_kernel(const float* __res
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    const float v = lx_wave_sum(acc[k]);
+    const float v = loss_wave_sum(acc[k]);
     if (lane == 0) red[wv][k] = v;
   }
   __syncthreads();
@@ -183,7 +150,7 @@ __global__ __launch_bounds__(256) void segloss_ex_bwd_kernel(const float* __rest
     for (int c = 0; c < C; ++c) {
       const float t = (c == y) ? 1.f : 0.f;
       float v = k_nll * wy * (p[c] - t) + k_sm * (p[c] * wsum - w[c]) + p[c] * (g[c] - gp);
-      if (FOCAL) v += k_f * focal_grad(z[c], c == y, fk);
+      if (FOCAL) v += k_f * focal_grad(sig_point(z[c]), c == y, fk);
       d[c * hw] = gs * v;
     }
   }
@@ -250,7 +217,7 @@ __global__ __launch_bounds__(256) void segloss_ex_sums_gen_kernel(const float* _
         a_pt += pc * t;
         a_pp += pc * pc;
         a_t += t;
-        if (FOCAL) a_f += focal_value(z, yp == cc, fk);
+        if (FOCAL) a_f += focal_value(sig_point(z), yp == cc, fk);
       }
     }
     __syncthreads();
@@ -258,10 +225,10 @@ __global__ __launch_bounds__(256) void segloss_ex_sums_gen_kernel(const float* _
   s_part[wv][0][lane] = a_pt;
   s_part[wv][1][lane] = a_pp;
   s_part[wv][2][lane] = a_t;
-  a_w = lx_wave_sum(a_w);
-  a_nll = lx_wave_sum(a_nll);
-  a_sm = lx_wave_sum(a_sm);
-  a_f = lx_wave_sum(a_f);
+  a_w = loss_wave_sum(a_w);
+  a_nll = loss_wave_sum(a_nll);
+  a_sm = loss_wave_sum(a_sm);
+  a_f = loss_wave_sum(a_f);
   if (lane == 0) { s_red[wv][0] = a_w; s_red[wv][1] = a_nll; s_red[wv][2] = a_sm; s_red[wv][3] = a_f; }
   __syncthreads();
   if (lane < C) {
@@ -325,7 +292,7 @@ __global__ __launch_bounds__(256) void segloss_ex_bwd_gen_kernel(const float* __
       const float p = __expf(zc - mx) * r;
       const float t = (c == y) ? 1.f : 0.f;
       float v = k_nll * wy * (p - t) + k_sm * (p * wsum - wce[c]) + p * (a[c] * t + bq[c] * p - gp);
-      if (FOCAL) v += k_f * focal_grad(zc, c == y, fk);
+      if (FOCAL) v += k_f * focal_grad(sig_point(zc), c == y, fk);
       d[c * hw] = gs * v;
     }
   }
@@ -396,29 +363,14 @@ __global__ __launch_bounds__(256) void image_stats_kernel(const float* __restric
   }
 }
 
-// the zeroed start of a reduction (words of 4 bytes)
-__global__ void lx_zero_kernel(uint32_t* __restrict__ p, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0u;
-}
-
-inline int lx_grid(int64_t work_items, int cap) {
-  int64_t g = (work_items + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // the argument checks shared by the two loss entries
 int lx_check(const char* what, int B, int C, int64_t HW, const lmn_loss_param_t* p) {
   LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= LX_MAXC, "%s: C=%d not in [2, %d]", what, C, LX_MAXC);
   LMN_REQUIRE(!p->has_ignore || p->ignore_index < 0 || p->ignore_index >= C, "%s: ignore_index=%lld inside [0, %d)", what,
               (long long)p->ignore_index, C);
   LMN_REQUIRE(p->label_smoothing >= 0.f && p->label_smoothing <= 1.f, "%s: label_smoothing=%g not in [0, 1]", what, (double)p->label_smoothing);
-  LMN_REQUIRE(p->smooth >= 0.f, "%s: smooth=%g is negative", what, (double)p->smooth);
-  LMN_REQUIRE(p->ce_scale >= 0.f && p->dice_scale >= 0.f && p->focal_scale >= 0.f, "%s: negative scale (ce %g, dice %g, focal %g)", what,
-              (double)p->ce_scale, (double)p->dice_scale, (double)p->focal_scale);
-  LMN_REQUIRE(p->focal_gamma >= 0.f, "%s: focal_gamma=%g is negative", what, (double)p->focal_gamma);
-  LMN_REQUIRE(p->focal_alpha <= 1.f, "%s: focal_alpha=%g above 1", what, (double)p->focal_alpha);
+  if (int rc = loss_check_terms(what, "ce", p->smooth, p->ce_scale, p->dice_scale, p->focal_scale, p->focal_gamma, p->focal_alpha))
+    return rc;
   return 0;
 }
 
@@ -435,10 +387,10 @@ int lmn_segloss_ex_fwd(const float* logits, const int64_t* target, const float* 
   hipStream_t st = (hipStream_t)stream;
   const bool focal = param->focal_scale > 0.f;
   const int NS = LMN_LOSS_SUMS_FLOATS(C);
-  const int grid = lx_grid((int64_t)B * HW, 1024);     // (the general form runs one 256-pixel tile per block and iteration)
+  const int grid = loss_grid((int64_t)B * HW, 1024);   // (the general form runs one 256-pixel tile per block and iteration)
   const FocalK fk{param->focal_gamma, param->focal_alpha};
   const FinishK fin{param->label_smoothing, param->smooth, param->ce_scale, param->dice_scale, param->focal_scale};
-  LMN_LAUNCH(lx_zero_kernel, dim3(1), dim3(256), 0, st, (uint32_t*)sums, (int64_t)NS);
+  LMN_LAUNCH(loss_zero_kernel, dim3(1), dim3(256), 0, st, (uint32_t*)sums, (int64_t)NS);
   float* sd = sums;
   if (g_lmn_det) {
     lmn_det_begin(st);
@@ -476,7 +428,7 @@ int lmn_segloss_ex_bwd(const float* logits, const int64_t* target, const float* 
   if (int rc = lx_check("segloss_ex_bwd", B, C, HW, param)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const bool focal = param->focal_scale > 0.f;
-  const int grid = lx_grid((int64_t)B * HW, 4096);
+  const int grid = loss_grid((int64_t)B * HW, 4096);
   const FocalK fk{param->focal_gamma, param->focal_alpha};
 #define LX_BWD(CC)                                                                                                                 \
   case CC:                                                                                                                         \
@@ -505,9 +457,9 @@ int lmn_image_stats(const float* logits, const uint8_t* pred_labels, const int64
   LMN_REQUIRE(!has_ignore || ignore_index < 0 || ignore_index >= C, "image_stats: ignore_index=%lld inside [0, %d)", (long long)ignore_index, C);
   hipStream_t st = (hipStream_t)stream;
   const int64_t words = (int64_t)B * C * 8;
-  LMN_LAUNCH(lx_zero_kernel, dim3(lx_grid(words, 64)), dim3(256), 0, st, (uint32_t*)stats, words);
+  LMN_LAUNCH(loss_zero_kernel, dim3(loss_grid(words, 64)), dim3(256), 0, st, (uint32_t*)stats, words);
   const int per_image = 512 / B > 0 ? 512 / B : 1;          // (few blocks per image: every block ends in 4C same-address atomics)
-  LMN_LAUNCH(image_stats_kernel, dim3(lx_grid(HW, per_image), B), dim3(256), 0, st, logits, pred_labels, target, C, HW,
+  LMN_LAUNCH(image_stats_kernel, dim3(loss_grid(HW, per_image), B), dim3(256), 0, st, logits, pred_labels, target, C, HW,
              (unsigned long long*)stats);
   return lmn_launch_status("image_stats");
 }

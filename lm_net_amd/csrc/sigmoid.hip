@@ -6,26 +6,13 @@
 //   sums (4-byte words, [k][C]): [0] N_c = valid elements (uint32)   [1] Y_c = sum_valid t (uint32)   [2] I_c = sum_valid p t
 //                                [3] Z_c = sum_valid p^2   [4] sum_valid pw_c t softplus(-z) + (1 - t) softplus(z)   [5] focal sum
 //   coef (floats, [k][C]):       [0] a_c  [1] b_c  with dL_dice/dp = a_c t + b_c p   [2] bce_scale w_bce[c] / N   [3] focal_scale / N_c
-#include "common.h"
+#include "loss_common.h"
 #include "../../include/lmnet_sigmoid.h"
 
 namespace {
 
 constexpr int SG_MAXC = 64;
 constexpr int SG_NSUM = 6, SG_NFLT = 4;   // words per class in sums; the float ones among them (slot copies in deterministic mode)
-
-struct SgFocalK { float gamma, alpha; };   // alpha < 0: no alpha weighting
-
-__device__ __forceinline__ float sg_wave_sum(float v) {
-#pragma unroll
-  for (int m = 1; m <= 32; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned sg_wave_sum(unsigned v) {
-#pragma unroll
-  for (int m = 1; m <= 32; m <<= 1) v += (unsigned)__shfl_xor((int)v, m, 64);
-  return v;
-}
 
 // E consecutive targets of a plane as 0, 1 or 2 (void: every value but 0 and 1).  KIND 0: uint8, 1: int64.
 template <int KIND, int E>
@@ -67,39 +54,9 @@ __device__ __forceinline__ void sg_load_z(const float* __restrict__ plane, int64
   }
 }
 
-// One softplus serves the sigmoid, both binary cross entropies and the focal factor (the formulation of focal_value in loss_ex.hip):
-// with e = exp(-|z|), l = log1p(e):  softplus(z) = max(z, 0) + l = -log(1 - p),  softplus(-z) = max(-z, 0) + l = -log p,
-// p = sigmoid(z) = 1 / (1 + e) or e / (1 + e).  No cancellation at large |z|, no overflow.
-struct SgPoint { float p, omp, sp_pos, sp_neg; };   // p, 1 - p, softplus(z), softplus(-z)
-__device__ __forceinline__ SgPoint sg_point(float z) {
-  const float e = expf(-fabsf(z));
-  const float l = log1pf(e);
-  const float r = 1.f / (1.f + e);
-  SgPoint s;
-  s.p = z >= 0.f ? r : e * r;
-  s.omp = z >= 0.f ? e * r : r;
-  s.sp_pos = fmaxf(z, 0.f) + l;
-  s.sp_neg = fmaxf(-z, 0.f) + l;
-  return s;
-}
-// a_t (1 - q_t)^gamma bce(z, t): bce = -log q_t, log(1 - q_t) = -(the other softplus).  gamma = 0: exp(0) = 1 exactly.
-__device__ __forceinline__ float sg_focal_value(const SgPoint& s, bool t, SgFocalK k) {
-  const float bce = t ? s.sp_neg : s.sp_pos, l1 = -(t ? s.sp_pos : s.sp_neg);
-  const float at = k.alpha < 0.f ? 1.f : (t ? k.alpha : 1.f - k.alpha);
-  return at * expf(k.gamma * l1) * bce;
-}
-// d/dz of it = (2t - 1) a_t (1 - q_t)^gamma [-gamma q_t bce - (1 - q_t)]   (as focal_grad of loss_ex.hip)
-__device__ __forceinline__ float sg_focal_grad(const SgPoint& s, bool t, SgFocalK k) {
-  const float bce = t ? s.sp_neg : s.sp_pos, l1 = -(t ? s.sp_pos : s.sp_neg);
-  const float qt = t ? s.p : s.omp, omq = t ? s.omp : s.p;
-  const float at = k.alpha < 0.f ? 1.f : (t ? k.alpha : 1.f - k.alpha);
-  const float ds = at * expf(k.gamma * l1) * (-k.gamma * qt * bce - omq);
-  return t ? ds : -ds;
-}
-
 template <int KIND, bool VEC, bool FOCAL>
 __global__ __launch_bounds__(256) void sigloss_sums_kernel(const float* __restrict__ logits, const void* __restrict__ target,
-                                                           const float* __restrict__ pos_weight, int C, int64_t hw, SgFocalK fk,
+                                                           const float* __restrict__ pos_weight, int C, int64_t hw, FocalK fk,
                                                            uint32_t* __restrict__ sums, float* __restrict__ slots) {
   constexpr int E = VEC ? 4 : 1;
   const int plane = blockIdx.y, c = plane % C;
@@ -117,25 +74,25 @@ __global__ __launch_bounds__(256) void sigloss_sums_kernel(const float* __restri
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       if (t[j] > 1) continue;                         // void: adds to no sum
-      const SgPoint s = sg_point(z[j]);
+      const SigPoint s = sig_point(z[j]);
       const bool on = t[j] == 1;
       n_v += 1u;
       n_y += on ? 1u : 0u;
       a_i += on ? s.p : 0.f;
       a_z += s.p * s.p;
       a_b += on ? pw * s.sp_neg : s.sp_pos;
-      if (FOCAL) a_f += sg_focal_value(s, on, fk);
+      if (FOCAL) a_f += focal_value(s, on, fk);
     }
   }
   __shared__ float red_f[4][SG_NFLT];
   __shared__ unsigned red_u[4][2];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  n_v = sg_wave_sum(n_v);
-  n_y = sg_wave_sum(n_y);
-  a_i = sg_wave_sum(a_i);
-  a_z = sg_wave_sum(a_z);
-  a_b = sg_wave_sum(a_b);
-  if (FOCAL) a_f = sg_wave_sum(a_f);
+  n_v = loss_wave_sum(n_v);
+  n_y = loss_wave_sum(n_y);
+  a_i = loss_wave_sum(a_i);
+  a_z = loss_wave_sum(a_z);
+  a_b = loss_wave_sum(a_b);
+  if (FOCAL) a_f = loss_wave_sum(a_f);
   if (lane == 0) {
     red_u[wv][0] = n_v; red_u[wv][1] = n_y;
     red_f[wv][0] = a_i; red_f[wv][1] = a_z; red_f[wv][2] = a_b; red_f[wv][3] = a_f;
@@ -194,7 +151,7 @@ __global__ void sigloss_finish_kernel(const uint32_t* __restrict__ sums, const f
 template <int KIND, bool VEC, bool FOCAL>
 __global__ __launch_bounds__(256) void sigloss_bwd_kernel(const float* __restrict__ logits, const void* __restrict__ target,
                                                           const float* __restrict__ pos_weight, const float* __restrict__ coef,
-                                                          const float* __restrict__ gscale, int C, int64_t hw, SgFocalK fk,
+                                                          const float* __restrict__ gscale, int C, int64_t hw, FocalK fk,
                                                           float* __restrict__ dlogits) {
   constexpr int E = VEC ? 4 : 1;
   const int plane = blockIdx.y, c = plane % C;
@@ -213,11 +170,11 @@ __global__ __launch_bounds__(256) void sigloss_bwd_kernel(const float* __restric
     for (int j = 0; j < E; ++j) {
       d[j] = 0.f;                                     // void: +0
       if (t[j] > 1) continue;
-      const SgPoint s = sg_point(z[j]);
+      const SigPoint s = sig_point(z[j]);
       const bool on = t[j] == 1;
       float v = ((on ? a : 0.f) + bq * s.p) * (s.p * s.omp);         // dice: dL/dp through p (1 - p)
       v += k_b * (on ? -pw * s.omp : s.p);                            // bce: -pw t (1 - p) + (1 - t) p
-      if (FOCAL) v += k_f * sg_focal_grad(s, on, fk);
+      if (FOCAL) v += k_f * focal_grad(s, on, fk);
       d[j] = gs * v;
     }
     if constexpr (VEC) st4(dl + q * 4, f32x4{d[0], d[1], d[2], d[3]});
@@ -283,19 +240,8 @@ __global__ __launch_bounds__(256) void sigmoid_stats_kernel(const float* __restr
   }
 }
 
-// the zeroed start of a reduction (words of 4 bytes)
-__global__ void sg_zero_kernel(uint32_t* __restrict__ p, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0u;
-}
-
 // blocks per plane: enough for one 256-lane trip each, capped so that the whole grid stays near `cap` blocks
-inline int sg_grid_x(int64_t items, int planes, int cap) {
-  int64_t g = (items + 255) / 256;
-  const int64_t per_plane = cap / planes > 0 ? cap / planes : 1;
-  if (g > per_plane) g = per_plane;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+inline int sg_grid_x(int64_t items, int planes, int cap) { return loss_grid(items, cap / planes > 0 ? cap / planes : 1); }
 
 inline bool sg_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
@@ -308,11 +254,8 @@ int sg_check_sizes(const char* what, int B, int C, int64_t HW) {
 
 int sg_check(const char* what, int B, int C, int64_t HW, const lmn_sig_param_t* p) {
   if (int rc = sg_check_sizes(what, B, C, HW)) return rc;
-  LMN_REQUIRE(p->smooth >= 0.f, "%s: smooth=%g is negative", what, (double)p->smooth);
-  LMN_REQUIRE(p->bce_scale >= 0.f && p->dice_scale >= 0.f && p->focal_scale >= 0.f, "%s: negative scale (bce %g, dice %g, focal %g)", what,
-              (double)p->bce_scale, (double)p->dice_scale, (double)p->focal_scale);
-  LMN_REQUIRE(p->focal_gamma >= 0.f, "%s: focal_gamma=%g is negative", what, (double)p->focal_gamma);
-  LMN_REQUIRE(p->focal_alpha <= 1.f, "%s: focal_alpha=%g above 1", what, (double)p->focal_alpha);
+  if (int rc = loss_check_terms(what, "bce", p->smooth, p->bce_scale, p->dice_scale, p->focal_scale, p->focal_gamma, p->focal_alpha))
+    return rc;
   LMN_REQUIRE(p->target_kind == LMN_SIG_T_U8 || p->target_kind == LMN_SIG_T_I64, "%s: unknown target_kind %d", what, (int)p->target_kind);
   return 0;
 }
@@ -345,9 +288,9 @@ int lmn_sigloss_fwd(const float* logits, const void* target, const float* w_bce,
   const bool vec = HW % 4 == 0 && sg_aligned(logits, 16) && sg_aligned(target, kind == LMN_SIG_T_I64 ? 16 : 4);
   const int planes = B * C;
   const int gx = sg_grid_x(vec ? HW / 4 : HW, planes, 2048);
-  const SgFocalK fk{param->focal_gamma, param->focal_alpha};
+  const FocalK fk{param->focal_gamma, param->focal_alpha};
   const SgFinishK fin{param->smooth, param->bce_scale, param->dice_scale, param->focal_scale};
-  LMN_LAUNCH(sg_zero_kernel, dim3(1), dim3(256), 0, st, (uint32_t*)sums, (int64_t)LMN_SIG_SUMS_WORDS(C));
+  LMN_LAUNCH(loss_zero_kernel, dim3(1), dim3(256), 0, st, (uint32_t*)sums, (int64_t)LMN_SIG_SUMS_WORDS(C));
   float* slots = nullptr;
   if (g_lmn_det) {
     lmn_det_begin(st);
@@ -373,7 +316,7 @@ int lmn_sigloss_bwd(const float* logits, const void* target, const float* pos_we
   const bool vec = HW % 4 == 0 && sg_aligned(logits, 16) && sg_aligned(dlogits, 16) && sg_aligned(target, kind == LMN_SIG_T_I64 ? 16 : 4);
   const int planes = B * C;
   const int gx = sg_grid_x(vec ? HW / 4 : HW, planes, 4096);
-  const SgFocalK fk{param->focal_gamma, param->focal_alpha};
+  const FocalK fk{param->focal_gamma, param->focal_alpha};
   SG_DISPATCH(kind, vec, {
     if (focal) LMN_LAUNCH((sigloss_bwd_kernel<KIND, VEC, true>), dim3(gx, planes), dim3(256), 0, st, logits, target, pos_weight, coef, gscale, C, HW, fk, dlogits);
     else LMN_LAUNCH((sigloss_bwd_kernel<KIND, VEC, false>), dim3(gx, planes), dim3(256), 0, st, logits, target, pos_weight, coef, gscale, C, HW, fk, dlogits);
@@ -398,7 +341,7 @@ int lmn_sigmoid_stats(const float* logits, const void* target, int target_kind, 
   unsigned long long* so = (unsigned long long*)stats;
   if (has_t) {
     const int64_t words = (int64_t)planes * 8;
-    LMN_LAUNCH(sg_zero_kernel, dim3((unsigned)((words + 255) / 256 > 64 ? 64 : (words + 255) / 256)), dim3(256), 0, st, (uint32_t*)stats, words);
+    LMN_LAUNCH(loss_zero_kernel, dim3(loss_grid(words, 64)), dim3(256), 0, st, (uint32_t*)stats, words);
     SG_DISPATCH(target_kind, vec, {
       LMN_LAUNCH((sigmoid_stats_kernel<KIND, VEC, true>), dim3(gx, planes), dim3(256), 0, st, logits, target, logit_threshold, HW, so, labels_out);
     });

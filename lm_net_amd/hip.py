@@ -131,6 +131,13 @@ class ReduceJob(C.Structure):
                 ("dW", C.c_void_p), ("dW_src", C.c_void_p * 3), ("db", C.c_void_p), ("db2", C.c_void_p)]
 
 
+class PackJob(C.Structure):
+    """Mirror of lmn_pack_job_t."""
+    _fields_ = [("w", C.c_void_p), ("wpack", C.c_void_p), ("total", C.c_int64), ("first_block", C.c_int64),
+                ("ksize", C.c_int32), ("Cout", C.c_int32), ("Cin", C.c_int32), ("nsrc", C.c_int32),
+                ("c", C.c_int32 * 3), ("transposed", C.c_int32), ("row_off", C.c_int32), ("rows", C.c_int32),
+                ("dtype", C.c_int32), ("_pad", C.c_int32)]
+
 
 class AugParam(C.Structure):
     """Mirror of lmn_aug_param_t: one sample's parameters of lmn_augment_u8 (lm_net_amd.data.DeviceAugment)."""
@@ -194,7 +201,9 @@ class PostParam(C.Structure):
     _fields_ = [("connectivity", C.c_int32), ("hole_limit", C.c_int32), ("class_mask", C.c_uint64), ("keep_largest_mask", C.c_uint64),
                 ("min_area", C.c_int32 * 64)]
 
-# every symbol include/lmnet_hip.h declares (the CPU test suite checks the library exports all of them)
+# The C ABI, one list per header: every symbol that header declares.  The headers stay apart, one per feature; HEADERS is the one
+# registry of them.  load() checks the library against it, tests/test_host_cpu.py checks it against the headers, and the guard manifest
+# (tests/guard.py) partitions EXPORTS, so that a new export in any header needs a guard test or a stated reason why none applies.
 SYMBOLS = [
     "lmn_abi_version", "lmn_sizeof_conv_args", "lmn_sizeof_src", "lmn_sizeof_wgrad_args", "lmn_last_error",
     "lmn_conv_pack_size", "lmn_conv_pack", "lmn_conv_pack_batch", "lmn_sizeof_pack_job", "lmn_conv_fwd", "lmn_conv_dma_config", "lmn_conv_chain_ok", "lmn_conv_wgrad", "lmn_conv_wgrad_workspace",
@@ -208,18 +217,24 @@ SYMBOLS = [
     "lmn_plan_run", "lmn_prof_begin", "lmn_prof_end",
 ]
 
-# every symbol include/lmnet_oneof.h declares (the OneOf block of the training augmentations).  Kept apart from SYMBOLS because the
-# guard manifest (tests/guard.py) partitions SYMBOLS and is frozen; tests/test_guard_oneof_gpu.py guards these until a later change
-# folds them into the manifest.
+# include/lmnet_oneof.h: the OneOf block of the training augmentations
 SYMBOLS_ONEOF = ["lmn_sizeof_oneof_param", "lmn_oneof_workspace", "lmn_augment_oneof_u8"]
 
-# every symbol include/lmnet_loss.h declares (void labels and the focal term of the loss, per-image statistics); apart from SYMBOLS for
-# the same reason, guarded by tests/test_guard_loss_gpu.py.
+# include/lmnet_loss.h: void labels and the focal term of the loss, per-image statistics
 SYMBOLS_LOSS = ["lmn_sizeof_loss_param", "lmn_segloss_ex_fwd", "lmn_segloss_ex_bwd", "lmn_image_stats"]
 
-# every symbol include/lmnet_sigmoid.h declares (the loss and the statistics of sigmoid heads); apart from SYMBOLS for the same reason,
-# guarded by tests/test_guard_sigmoid_gpu.py.
+# include/lmnet_sigmoid.h: the loss and the statistics of sigmoid heads
 SYMBOLS_SIGMOID = ["lmn_sizeof_sig_param", "lmn_sigloss_fwd", "lmn_sigloss_bwd", "lmn_sigmoid_stats"]
+
+HEADERS = {"lmnet_hip.h": SYMBOLS, "lmnet_oneof.h": SYMBOLS_ONEOF, "lmnet_loss.h": SYMBOLS_LOSS, "lmnet_sigmoid.h": SYMBOLS_SIGMOID}
+EXPORTS = [name for names in HEADERS.values() for name in names]
+
+# every struct mirror whose size the library reports, with the export that reports it.  (DwPre, SeFuse, SeBwd and SeParamsT
+# have no lmn_sizeof_* export and stay unchecked.)
+STRUCTS = [(ConvArgs, "lmn_sizeof_conv_args"), (SrcT, "lmn_sizeof_src"), (WgradArgs, "lmn_sizeof_wgrad_args"),
+           (PackJob, "lmn_sizeof_pack_job"), (ReduceJob, "lmn_sizeof_reduce_job"), (AugParam, "lmn_sizeof_aug_param"),
+           (PostParam, "lmn_sizeof_post_param"), (OneOfParam, "lmn_sizeof_oneof_param"), (LossParam, "lmn_sizeof_loss_param"),
+           (SigParam, "lmn_sizeof_sig_param")]
 
 _lib = None
 
@@ -234,7 +249,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in SYMBOLS + SYMBOLS_ONEOF + SYMBOLS_LOSS + SYMBOLS_SIGMOID:
+    for name in EXPORTS:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -249,12 +264,11 @@ def load():
     lib.lmn_prof_end.restype = C.c_int64
     if lib.lmn_abi_version() != ABI_VERSION:
         raise RuntimeError("lm_net_amd: ABI version mismatch")
-    if (lib.lmn_sizeof_conv_args() != C.sizeof(ConvArgs) or lib.lmn_sizeof_src() != C.sizeof(SrcT)
-            or lib.lmn_sizeof_wgrad_args() != C.sizeof(WgradArgs) or lib.lmn_sizeof_reduce_job() != C.sizeof(ReduceJob)
-            or lib.lmn_sizeof_aug_param() != C.sizeof(AugParam) or lib.lmn_sizeof_post_param() != C.sizeof(PostParam)
-            or lib.lmn_sizeof_oneof_param() != C.sizeof(OneOfParam) or lib.lmn_sizeof_loss_param() != C.sizeof(LossParam)
-            or lib.lmn_sizeof_sig_param() != C.sizeof(SigParam)):
-        raise RuntimeError("lm_net_amd: argument struct layout differs between hip.py and lmnet_hip.h")
+    for struct, sizeof in STRUCTS:
+        n = getattr(lib, sizeof)()
+        if n != C.sizeof(struct):
+            raise RuntimeError("lm_net_amd: layout of %s differs between hip.py (%d bytes) and the library (%s() = %d)"
+                               % (struct.__name__, C.sizeof(struct), sizeof, n))
     _lib = lib
     return lib
 
@@ -431,14 +445,6 @@ def conv_pack_size(ksize, rows, src_channels):
     return int(load().lmn_conv_pack_size(ksize, rows, len(src_channels), arr))
 
 
-class PackJob(C.Structure):
-    """Mirror of lmn_pack_job_t."""
-    _fields_ = [("w", C.c_void_p), ("wpack", C.c_void_p), ("total", C.c_int64), ("first_block", C.c_int64),
-                ("ksize", C.c_int32), ("Cout", C.c_int32), ("Cin", C.c_int32), ("nsrc", C.c_int32),
-                ("c", C.c_int32 * 3), ("transposed", C.c_int32), ("row_off", C.c_int32), ("rows", C.c_int32),
-                ("dtype", C.c_int32), ("_pad", C.c_int32)]
-
-
 class PackPlan:
     """Packed forms of the PERSISTENT weights (nn.Parameter storage) used by one pass (forward or backward).
 
@@ -473,8 +479,6 @@ class PackPlan:
                 a.transposed, a.row_off, a.rows = f["transposed"], f["row_off"], f["rows"]
                 a.dtype = f.get("dtype", F32)
                 blk += (out.numel() + 1023) // 1024
-            if C.sizeof(PackJob) != load().lmn_sizeof_pack_job():
-                raise RuntimeError("lm_net_amd: lmn_pack_job_t layout differs between hip.py and lmnet_hip.h")
             dev = next(iter(self.jobs.values()))[1].device
             host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
             self.table, self.blocks = host.to(dev), blk
@@ -1273,30 +1277,19 @@ def post_render(labels_net, src_hw, Hs, Ws, frames, palette, n_classes, alpha256
 
 def preprocess_u8(images, masks, flips, out, labels, mean, std):
     """uint8 HWC images [B,Hs,Ws,3] / masks [B,Hs,Ws] -> fp32 NCHW `out` [B,3,H,W] / int64 `labels` [B,H,W]."""
-    def raw(t, dt):
-        if t is None:
-            return None
-        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-            raise RuntimeError("lm_net_amd.preprocess_u8: contiguous %s device tensor required" % dt)
-        return C.c_void_p(t.data_ptr())
     ref = images if images is not None else masks
     B, Hs, Ws = ref.shape[0], ref.shape[1], ref.shape[2]
     dst = out if out is not None else labels
     H, W = dst.shape[-2], dst.shape[-1]
     m3, s3 = (C.c_double * 3)(*[float(v) for v in mean]), (C.c_double * 3)(*[float(v) for v in std])
-    _check(load().lmn_preprocess_u8(raw(images, torch.uint8), raw(masks, torch.uint8), raw(flips, torch.uint8), B, Hs, Ws,
-                                    H, W, m3, s3, _p(out), raw(labels, torch.int64), _stream()), "preprocess_u8")
+    u8, what = torch.uint8, "preprocess_u8"
+    _check(load().lmn_preprocess_u8(_raw(images, u8, what), _raw(masks, u8, what), _raw(flips, u8, what), B, Hs, Ws,
+                                    H, W, m3, s3, _p(out), _raw(labels, torch.int64, what), _stream()), what)
 
 
 def preprocess_u8_ex(images, masks, flips, out, labels, mean, std, channels, mask_mode):
     """uint8 images [B,Hs,Ws,channels] (channels 1: also [B,Hs,Ws]) / masks [B,Hs,Ws] -> fp32 NCHW `out` [B,channels,H,W] / int64
     `labels` [B,H,W]; mask_mode 0 thresholds the mask at 127 into {0, 1}, 1 passes class ids through."""
-    def raw(t, dt):
-        if t is None:
-            return None
-        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-            raise RuntimeError("lm_net_amd.preprocess_u8_ex: contiguous %s device tensor required" % dt)
-        return C.c_void_p(t.data_ptr())
     ref = images if images is not None else masks
     B, Hs, Ws = ref.shape[0], ref.shape[1], ref.shape[2]
     dst = out if out is not None else labels
@@ -1309,9 +1302,10 @@ def preprocess_u8_ex(images, masks, flips, out, labels, mean, std, channels, mas
         raise ValueError("lm_net_amd.preprocess_u8_ex: tensor sizes do not match B=%d, %dx%d -> %dx%d, %d channel(s)"
                          % (B, Hs, Ws, H, W, channels))
     mc, sc = (C.c_double * channels)(*[float(v) for v in mean]), (C.c_double * channels)(*[float(v) for v in std])
-    _check(load().lmn_preprocess_u8_ex(raw(images, torch.uint8), raw(masks, torch.uint8), raw(flips, torch.uint8), B, Hs, Ws,
-                                       H, W, int(channels), int(mask_mode), mc, sc, _p(out), raw(labels, torch.int64), _stream()),
-           "preprocess_u8_ex")
+    u8, what = torch.uint8, "preprocess_u8_ex"
+    _check(load().lmn_preprocess_u8_ex(_raw(images, u8, what), _raw(masks, u8, what), _raw(flips, u8, what), B, Hs, Ws,
+                                       H, W, int(channels), int(mask_mode), mc, sc, _p(out), _raw(labels, torch.int64, what), _stream()),
+           what)
 
 
 
@@ -1320,12 +1314,6 @@ def augment_u8(images, masks, params, src_hw, params_dev, scratch, gray_sum, out
     `labels` [B,H,W] through lmn_augment_u8.  params: host ctypes array of B AugParam (checked and copied into the device buffer
     params_dev, uint8 [B * sizeof(AugParam)]); src_hw: host int32 numpy array [B,2] or None; scratch: uint8 [B,H,W,channels];
     gray_sum: int64 [B] (the kernels' uint64 sums)."""
-    def raw(t, dt):
-        if t is None:
-            return None
-        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-            raise RuntimeError("lm_net_amd.augment_u8: contiguous %s device tensor required" % dt)
-        return C.c_void_p(t.data_ptr())
     ref = images if images is not None else masks
     if ref is None:
         raise ValueError("lm_net_amd.augment_u8: images or masks required")
@@ -1349,9 +1337,10 @@ def augment_u8(images, masks, params, src_hw, params_dev, scratch, gray_sum, out
     hw_arr = None if src_hw is None else np.ascontiguousarray(src_hw, dtype=np.int32)   # (kept alive across the call)
     hw = None if hw_arr is None else hw_arr.ctypes.data_as(C.POINTER(C.c_int32))
     mc, sc = (C.c_double * channels)(*[float(v) for v in mean]), (C.c_double * channels)(*[float(v) for v in std])
-    _check(load().lmn_augment_u8(raw(images, torch.uint8), raw(masks, torch.uint8), params, hw, raw(params_dev, torch.uint8), B, Hs,
-                                 Ws, H, W, int(channels), int(mask_mode), mc, sc, raw(scratch, torch.uint8),
-                                 raw(gray_sum, torch.int64), _p(out), raw(labels, torch.int64), _stream()), "augment_u8")
+    u8, i64, what = torch.uint8, torch.int64, "augment_u8"
+    _check(load().lmn_augment_u8(_raw(images, u8, what), _raw(masks, u8, what), params, hw, _raw(params_dev, u8, what), B, Hs,
+                                 Ws, H, W, int(channels), int(mask_mode), mc, sc, _raw(scratch, u8, what),
+                                 _raw(gray_sum, i64, what), _p(out), _raw(labels, i64, what), _stream()), what)
 
 
 def oneof_workspace(B, H, W, channels, n_elastic):
@@ -1369,12 +1358,6 @@ def augment_oneof_u8(images, masks, params, src_hw, params_dev, scratch, gray_su
     sizeof(OneOfParam)]); tables: host float32 numpy array (grid-distortion maps, elastic weights and noise) or None, copied into
     tables_dev (fp32, same length); lab_tables: int32 [LAB_TABLE_INTS] device tensor or None; scratch2: uint8 like scratch;
     labels_tmp: int64 like labels or None; workspace: uint8, at least oneof_workspace(...) bytes."""
-    def raw(t, dt):
-        if t is None:
-            return None
-        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-            raise RuntimeError("lm_net_amd.augment_oneof_u8: contiguous %s device tensor required" % dt)
-        return C.c_void_p(t.data_ptr())
     ref = images if images is not None else masks
     dst = out if out is not None else labels
     if ref is None or dst is None:
@@ -1401,12 +1384,13 @@ def augment_oneof_u8(images, masks, params, src_hw, params_dev, scratch, gray_su
     tab_arr = None if not nt else np.ascontiguousarray(tables)                           # (kept alive across the call)
     tab = None if not nt else tab_arr.ctypes.data_as(C.POINTER(C.c_float))
     mc, sc = (C.c_double * channels)(*[float(v) for v in mean]), (C.c_double * channels)(*[float(v) for v in std])
+    u8, i64, what = torch.uint8, torch.int64, "augment_oneof_u8"
     _check(load().lmn_augment_oneof_u8(
-        raw(images, torch.uint8), raw(masks, torch.uint8), params, hw, raw(params_dev, torch.uint8), B, Hs, Ws, H, W, int(channels),
-        int(mask_mode), mc, sc, raw(scratch, torch.uint8), raw(gray_sum, torch.int64), _p(out), raw(labels, torch.int64), oneof,
-        raw(oneof_dev, torch.uint8), tab, C.c_int64(nt), _p(tables_dev) if nt else None, raw(lab_tables, torch.int32),
-        raw(scratch2, torch.uint8), raw(labels_tmp, torch.int64), raw(workspace, torch.uint8), C.c_int64(workspace.numel()), _stream()),
-        "augment_oneof_u8")
+        _raw(images, u8, what), _raw(masks, u8, what), params, hw, _raw(params_dev, u8, what), B, Hs, Ws, H, W, int(channels),
+        int(mask_mode), mc, sc, _raw(scratch, u8, what), _raw(gray_sum, i64, what), _p(out), _raw(labels, i64, what), oneof,
+        _raw(oneof_dev, u8, what), tab, C.c_int64(nt), _p(tables_dev) if nt else None, _raw(lab_tables, torch.int32, what),
+        _raw(scratch2, u8, what), _raw(labels_tmp, i64, what), _raw(workspace, u8, what), C.c_int64(workspace.numel()), _stream()),
+        what)
 
 
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2):

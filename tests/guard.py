@@ -293,6 +293,9 @@ class LaunchLog:
 # ---------------------------------------------------------------------------------------------------------------- coverage manifest
 MODEL = "tests/test_guard_model_gpu.py"
 KERN = "tests/test_guard_kernels_gpu.py"
+ONEOF = "tests/test_guard_oneof_gpu.py"
+LOSS = "tests/test_guard_loss_gpu.py"
+SIGMOID = "tests/test_guard_sigmoid_gpu.py"
 
 
 def _fam(*wrappers):
@@ -301,7 +304,8 @@ def _fam(*wrappers):
 
 
 # C entry -> (test file, test function, `hip.` wrapper through which that test issues the entry).  tests/test_guard_cpu.py checks that
-# this and EXEMPT partition hip.SYMBOLS and that the named test's file names the wrapper: a new export needs a guard test.
+# this and EXEMPT partition hip.EXPORTS (every header's list) and that the named test's file calls `hip.<wrapper>` -- or, where the
+# test reaches the entry through a class of the package, asserts the wrapper's name in its launch log: a new export needs a guard test.
 # (The engine-allocated side of the same entries -- every intermediate of the model's own pass -- is tests/test_guard_model_gpu.py.)
 COVERED = dict(_fam(
     "conv_fwd", "conv_wgrad", "reparam_fold", "reparam_wfin", "affine2", "bnact_fwd_fin", "bnact_bwd_fin",
@@ -332,6 +336,13 @@ COVERED.update({
     "lmn_cc_label": (KERN, "test_post_clean_render_and_cc_label", "cc_label"),
     "lmn_post_clean": (KERN, "test_post_clean_render_and_cc_label", "post_clean"),
     "lmn_post_render": (KERN, "test_post_clean_render_and_cc_label", "post_render"),
+    "lmn_augment_oneof_u8": (ONEOF, "test_augment_oneof_u8_every_member", "augment_oneof_u8"),
+    "lmn_segloss_ex_fwd": (LOSS, "test_loss_and_image_stats_entries", "segloss_ex_fwd"),
+    "lmn_segloss_ex_bwd": (LOSS, "test_loss_and_image_stats_entries", "segloss_ex_bwd"),
+    "lmn_image_stats": (LOSS, "test_loss_and_image_stats_entries", "image_stats"),
+    "lmn_sigloss_fwd": (SIGMOID, "test_loss_and_stats_entries", "sigloss_fwd"),
+    "lmn_sigloss_bwd": (SIGMOID, "test_loss_and_stats_entries", "sigloss_bwd"),
+    "lmn_sigmoid_stats": (SIGMOID, "test_loss_and_stats_entries", "sigmoid_stats"),
 })
 
 # entries that take no device output pointer -> why no guard test applies
@@ -340,10 +351,12 @@ EXEMPT = {
     "lmn_abi_version": _HOST, "lmn_last_error": "returns the host-side error string",
     "lmn_sizeof_conv_args": _HOST, "lmn_sizeof_src": _HOST, "lmn_sizeof_wgrad_args": _HOST, "lmn_sizeof_pack_job": _HOST,
     "lmn_sizeof_reduce_job": _HOST, "lmn_sizeof_aug_param": _HOST, "lmn_sizeof_post_param": _HOST,
+    "lmn_sizeof_oneof_param": _HOST, "lmn_sizeof_loss_param": _HOST, "lmn_sizeof_sig_param": _HOST,
     "lmn_conv_pack_size": _HOST + " (tested AS A BOUND by test_conv_pack_exact_size_feeds_conv_fwd)",
     "lmn_conv_wgrad_workspace": _HOST + " (tested as a bound by test_model_kernel_families: hip._workspace returns exactly this)",
     "lmn_surface_workspace": _HOST + " (tested as a bound by test_surface_dist)",
     "lmn_post_workspace": _HOST + " (tested as a bound by test_post_clean_render_and_cc_label)",
+    "lmn_oneof_workspace": _HOST + " (tested as a bound by test_augment_oneof_u8_every_member: the workspace is carved at exactly this)",
     "lmn_conv_chain_ok": "launch predicate, " + _HOST, "lmn_conv_wgrad_up2_ok": "launch predicate, " + _HOST,
     "lmn_conv_wgrad_job": "geometry query into a host struct, " + _HOST,
     "lmn_conv_dma_config": "process-wide dispatch switch, host state only",

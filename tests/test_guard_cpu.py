@@ -188,33 +188,49 @@ def test_manifest_partitions_the_c_abi():
     from lm_net_amd import hip
     cov, ex = set(guard.COVERED), set(guard.EXEMPT)
     assert not (cov & ex), sorted(cov & ex)
-    assert cov | ex == set(hip.SYMBOLS), (sorted(set(hip.SYMBOLS) - cov - ex), sorted((cov | ex) - set(hip.SYMBOLS)))
+    assert len(set(hip.EXPORTS)) == len(hip.EXPORTS) == sum(len(v) for v in hip.HEADERS.values())
+    assert cov | ex == set(hip.EXPORTS), (sorted(set(hip.EXPORTS) - cov - ex), sorted((cov | ex) - set(hip.EXPORTS)))
     bad = sorted(k for k in ex if not EXEMPT_OK.match(k))
     assert not bad, "entries with a device output pointer need a guard test: %s" % bad
     assert all(isinstance(v, str) and v for v in guard.EXEMPT.values())
     # the pattern must not swallow an entry that writes device memory
     for k in ("lmn_conv_fwd", "lmn_conv_pack", "lmn_conv_pack_batch", "lmn_conv_wgrad", "lmn_wgrad_reduce_batch", "lmn_fill", "lmn_surface_dist",
-              "lmn_post_clean", "lmn_cc_label", "lmn_adamw_step", "lmn_dw_fwd_bn", "lmn_reparam_fold"):
+              "lmn_post_clean", "lmn_cc_label", "lmn_adamw_step", "lmn_dw_fwd_bn", "lmn_reparam_fold", "lmn_augment_oneof_u8",
+              "lmn_segloss_ex_fwd", "lmn_segloss_ex_bwd", "lmn_image_stats", "lmn_sigloss_fwd", "lmn_sigloss_bwd", "lmn_sigmoid_stats"):
         assert not EXEMPT_OK.match(k) and k in cov, k
 
 
+def _code(src):
+    """Python source without its docstrings: a mention there is no call and no assertion.  (Comments stay: the tests that reach an
+    entry through a class of the package and assert it with `in log.names` name their `hip.` wrapper in a comment beside that.)"""
+    return re.sub(r"""(?s)\"{3}.*?\"{3}|'{3}.*?'{3}""", '""', src)
+
+
 def test_manifest_matches_the_gpu_test_sources():
-    """Every COVERED entry names a test function that exists in its file and whose file calls (or, for the model file, lists as
-    reached and asserts at run time) the entry's `hip.` wrapper; the wrapper's source really issues that C entry."""
+    """Every COVERED entry names a test function that exists in its file and whose body calls (or, for the model file, lists as
+    reached and asserts at run time) the entry's `hip.` wrapper -- or, where it reaches the entry through a class of the package,
+    compares a LaunchLog's `names` with a list that holds the wrapper's name; the wrapper's source really issues that C entry.
+    A docstring counts for nothing."""
     from lm_net_amd import hip
-    src = {f: open(os.path.join(ROOT, f)).read() for f in (guard.MODEL, guard.KERN)}
+    src = {f: _code(open(os.path.join(ROOT, f)).read()) for f in sorted({v[0] for v in guard.COVERED.values()} | {guard.MODEL})}
     hip_src = open(os.path.join(ROOT, "lm_net_amd", "hip.py")).read()
-    kc_src = open(os.path.join(ROOT, "tests", "kernel_checks.py")).read()
+    kc_src = _code(open(os.path.join(ROOT, "tests", "kernel_checks.py")).read())
     assert "dir(kc)" in src[guard.KERN] and 'startswith("check_")' in src[guard.KERN]      # the families are enumerated, not listed
     for entry, (f, test, wrapper) in sorted(guard.COVERED.items()):
         assert f in src, (entry, f)
-        assert re.search(r"^def %s\(" % re.escape(test), src[f], re.M), (entry, test)
+        fn = re.search(r"^def %s\(.*?(?=^def |^class |^@|\Z)" % re.escape(test), src[f], re.M | re.S)
+        assert fn, (entry, test)
         if test == "test_model_kernel_families":                     # runs every check_* of kernel_checks.py: the call is there
             assert re.search(r"\bhip\.%s\(" % re.escape(wrapper), kc_src), (entry, wrapper)
         else:
-            assert re.search(r"\bhip\.%s\b" % re.escape(wrapper), src[f]), (entry, wrapper)
+            called = re.search(r"\bhip\.%s\b" % re.escape(wrapper), fn.group(0))       # (inside the named test function)
+            logged = any('"%s"' % wrapper in m for m in re.findall(r"\.names == \[([^\]]*)\]", fn.group(0)))
+            assert called or logged, (entry, wrapper)
         assert callable(getattr(hip, wrapper)), (entry, wrapper)
         body = re.search(r"^def %s\(.*?(?=^def |^class |\Z)" % re.escape(wrapper), hip_src, re.M | re.S)
         if body is None:                                             # a class (PackPlan.refresh issues lmn_conv_pack_batch)
             body = re.search(r"^class %s\b.*?(?=^class |^def |\Z)" % re.escape(wrapper), hip_src, re.M | re.S)
         assert body is not None and re.search(r"\b%s\b" % entry, body.group(0)), (entry, wrapper)
+    # the stripping itself: a docstring that names a wrapper satisfies neither rule
+    fake = _code('"""calls hip.fake_wrapper( and asserts log.names == ["fake_wrapper"]"""\nx = 1\n' + "'''hip.fake_wrapper('''\n")
+    assert "fake_wrapper" not in fake and "x = 1" in fake

@@ -1,5 +1,5 @@
-"""GPU: the entries of include/lmnet_loss.h inside guard bands (tests/guard.py).  They are not in the guard manifest (it partitions
-hip.SYMBOLS, which is frozen); this test stands in for the manifest entries: every buffer of lmn_segloss_ex_fwd, lmn_segloss_ex_bwd
+"""GPU: the entries of include/lmnet_loss.h inside guard bands (tests/guard.py): the guard manifest's test of these
+entries.  Every buffer of lmn_segloss_ex_fwd, lmn_segloss_ex_bwd
 and lmn_image_stats -- logits, labels, both weight vectors, `sums` and `coef` at exactly the header's float counts, loss4, gscale,
 dlogits, the uint8 prediction and stats -- is carved from a GuardPool at its exact size, canaries flush against each."""
 import pytest

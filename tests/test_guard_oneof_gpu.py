@@ -1,8 +1,8 @@
-"""GPU: lmn_augment_oneof_u8 inside guard bands (tests/guard.py).  The entries of include/lmnet_oneof.h are not in the guard
-manifest (it partitions hip.SYMBOLS, which is frozen); this test stands in for the manifest entry: one mixed batch containing
-every member, every buffer of the call carved from a GuardPool at its exact size -- frames, masks, both parameter tables, the
-uploaded host tables, the LAB tables, both scratches, the label copy, the gray sums, the workspace at exactly
-lmn_oneof_workspace bytes, out and labels -- with canaries flush against each."""
+"""GPU: lmn_augment_oneof_u8 inside guard bands (tests/guard.py): the guard manifest's test of the entry, which it reaches through
+DeviceAugment (the launch log below names the wrapper).  One mixed batch containing every member, every buffer of the call carved
+from a GuardPool at its exact size -- frames, masks, both parameter tables, the uploaded host tables, the LAB tables, both scratches,
+the label copy, the gray sums, the workspace at exactly lmn_oneof_workspace bytes, out and labels -- with canaries flush against
+each."""
 import numpy as np
 import pytest
 import torch

@@ -1,5 +1,5 @@
-"""GPU: the entries of include/lmnet_sigmoid.h inside guard bands (tests/guard.py).  They are not in the guard manifest (it partitions
-hip.SYMBOLS, which is frozen); this test stands in for the manifest entries: every buffer of lmn_sigloss_fwd, lmn_sigloss_bwd and
+"""GPU: the entries of include/lmnet_sigmoid.h inside guard bands (tests/guard.py): the guard manifest's test of these
+entries.  Every buffer of lmn_sigloss_fwd, lmn_sigloss_bwd and
 lmn_sigmoid_stats -- logits, the target, the three weight vectors, `sums` and `coef` at exactly the header's sizes, loss4, gscale,
 dlogits, stats and the uint8 label maps -- is carved from a GuardPool at its exact size, canaries flush against each.  HW = 37 * 45
 is odd (one element per lane, and the int64 / uint8 planes end on no 16-byte boundary); 36 * 44 runs the four-element form, whose

@@ -13,18 +13,38 @@ from helpers import GOLDEN, ROOT
 
 
 def test_library_exports_every_declared_symbol():
+    """hip.HEADERS against include/: every header is in the table and declares exactly its list, no name or struct typedef
+    belongs to two headers, the library exports every name, and every struct mirror has the size the library reports."""
     from lm_net_amd import hip
     lib = hip.load()
-    hdr = open(os.path.join(ROOT, "include", "lmnet_hip.h")).read()
-    declared = set(re.findall(r"\b(lmn_[a-z0-9_]+)\s*\(", hdr))
-    declared -= {"lmn_src_t", "lmn_stream_t"}
-    assert declared == set(hip.SYMBOLS), declared ^ set(hip.SYMBOLS)
-    for name in declared:
-        assert hasattr(lib, name), name
-    assert lib.lmn_abi_version() == hip.ABI_VERSION
-    assert lib.lmn_sizeof_conv_args() == ctypes.sizeof(hip.ConvArgs)
-    assert lib.lmn_sizeof_src() == ctypes.sizeof(hip.SrcT)
-    assert lib.lmn_sizeof_wgrad_args() == ctypes.sizeof(hip.WgradArgs)
+    inc = os.path.join(ROOT, "include")
+    assert sorted(fn for fn in os.listdir(inc) if fn.endswith(".h")) == sorted(hip.HEADERS)
+    text = {fn: open(os.path.join(inc, fn)).read() for fn in hip.HEADERS}
+    for fn, names in hip.HEADERS.items():
+        declared = set(re.findall(r"\b(lmn_[a-z0-9_]+)\s*\(", text[fn])) - {"lmn_src_t", "lmn_stream_t"}
+        assert declared == set(names) and len(set(names)) == len(names), (fn, declared ^ set(names))
+        assert all(hasattr(lib, name) for name in names), fn
+    lists = list(hip.HEADERS.values())
+    assert all(not set(a) & set(b) for i, a in enumerate(lists) for b in lists[i + 1:])      # pairwise disjoint
+    assert hip.EXPORTS == [name for names in lists for name in names]
+    typedefs = {fn: re.findall(r"^\}\s*(lmn_\w+_t)\s*;", text[fn], re.M) for fn in text}
+    names = [td for tds in typedefs.values() for td in tds]
+    assert all(typedefs.values()) and len(set(names)) == len(names)          # every header defines a struct, none is defined twice
+    # A struct is named only by the header that defines it -- or by one that includes that header, since an entry of a feature header
+    # may take a struct of lmnet_hip.h (lmn_augment_oneof_u8 takes lmn_aug_param_t).  No header includes a feature header, so ...
+    for fn, tds in typedefs.items():
+        sees = [fn] + [g for g in text if '#include "%s"' % fn in text[g]]
+        for td in tds:
+            named_by = [g for g in text if re.search(r"\b%s\b" % td, text[g])]
+            assert set(named_by) <= set(sees), (td, fn, named_by)
+    # ... the structs of the three feature headers occur in exactly one header each
+    for fn, td in (("lmnet_oneof.h", "lmn_oneof_param_t"), ("lmnet_loss.h", "lmn_loss_param_t"), ("lmnet_sigmoid.h", "lmn_sig_param_t")):
+        assert typedefs[fn] == [td] and [g for g in text if td in text[g]] == [fn], td
+    assert lib.lmn_abi_version() == hip.ABI_VERSION == 15
+    assert len(hip.STRUCTS) == 10 and len({sizeof for _, sizeof in hip.STRUCTS}) == 10
+    assert {sizeof for _, sizeof in hip.STRUCTS} == {name for name in hip.EXPORTS if name.startswith("lmn_sizeof_")}
+    for struct, sizeof in hip.STRUCTS:
+        assert getattr(lib, sizeof)() == ctypes.sizeof(struct), (struct.__name__, sizeof)
 
 
 def test_pack_size_arithmetic():

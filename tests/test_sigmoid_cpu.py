@@ -197,13 +197,8 @@ def test_exports_and_struct_size():
     from lm_net_amd import hip
     lib = hip.load()
     assert hip.SYMBOLS_SIGMOID == ["lmn_sizeof_sig_param", "lmn_sigloss_fwd", "lmn_sigloss_bwd", "lmn_sigmoid_stats"]
-    assert not set(hip.SYMBOLS_SIGMOID) & (set(hip.SYMBOLS) | set(hip.SYMBOLS_ONEOF) | set(hip.SYMBOLS_LOSS))
-    assert all(hasattr(lib, s) for s in hip.SYMBOLS_SIGMOID)
+    assert hip.HEADERS["lmnet_sigmoid.h"] is hip.SYMBOLS_SIGMOID   # (the header / export / layout checks: tests/test_host_cpu.py)
     header = open(os.path.join(ROOT, "include", "lmnet_sigmoid.h")).read()
-    assert set(re.findall(r"\b(lmn_[a-z0-9_]+)\s*\(", header)) == set(hip.SYMBOLS_SIGMOID)
-    for other in ("lmnet_hip.h", "lmnet_oneof.h", "lmnet_loss.h"):
-        text = open(os.path.join(ROOT, "include", other)).read()
-        assert not any(re.search(r"\b%s\s*\(" % s, text) for s in hip.SYMBOLS_SIGMOID) and "lmn_sig_param_t" not in text
     assert lib.lmn_sizeof_sig_param() == ctypes.sizeof(hip.SigParam) == 64 and hip.ABI_VERSION == 15
     m = re.search(r"#define LMN_SIG_SUMS_WORDS\(C\) \((\d+) \* \(C\)\)", header)
     n = re.search(r"#define LMN_SIG_COEF_FLOATS\(C\) \((\d+) \* \(C\)\)", header)

@@ -153,12 +153,8 @@ def test_exports_and_struct_size():
     from lm_net_amd import hip
     lib = hip.load()
     assert hip.SYMBOLS_LOSS == ["lmn_sizeof_loss_param", "lmn_segloss_ex_fwd", "lmn_segloss_ex_bwd", "lmn_image_stats"]
-    assert not set(hip.SYMBOLS_LOSS) & (set(hip.SYMBOLS) | set(hip.SYMBOLS_ONEOF)) and all(hasattr(lib, s) for s in hip.SYMBOLS_LOSS)
+    assert hip.HEADERS["lmnet_loss.h"] is hip.SYMBOLS_LOSS         # (the header / export / layout checks: tests/test_host_cpu.py)
     header = open(os.path.join(ROOT, "include", "lmnet_loss.h")).read()
-    assert set(re.findall(r"\b(lmn_[a-z0-9_]+)\s*\(", header)) == set(hip.SYMBOLS_LOSS)
-    for other in ("lmnet_hip.h", "lmnet_oneof.h"):
-        text = open(os.path.join(ROOT, "include", other)).read()
-        assert not any(re.search(r"\b%s\s*\(" % s, text) for s in hip.SYMBOLS_LOSS) and "lmn_loss_param_t" not in text
     assert lib.lmn_sizeof_loss_param() == ctypes.sizeof(hip.LossParam) == 64 and hip.ABI_VERSION == 15
     for C in (2, 9, 64):                                          # the workspace sizes of the header, mirrored in Python
         assert hip.loss_sums_floats(C) == 4 + 3 * C and hip.loss_coef_floats(C) == 4 + 2 * C
