@@ -1,7 +1,7 @@
 // What the two loss sources, loss_ex.hip (softmax heads) and sigmoid.hip (sigmoid heads), compute the same way: the wave sum of their
 // reductions, the sigmoid focal term and its derivative, the zero-fill of a reduction's start, the capped grid and the checks of the
 // scalar parameters both param structs carry.  Everything else -- the sums and dlogits kernels, the two finish kernels (which treat
-// dice_scale = 0 and the pixel counts differently on purpose) -- stays in its own file.
+// dice_scale = 0 and the pixel counts differently on purpose) -- stays in its own file.  metrics.hip takes the zero fill and the grid.
 #pragma once
 #include "common.h"
 

@@ -1,4 +1,4 @@
-// The training loss with void labels and a focal term, and per-image tp / fp / fn / tn statistics (include/lmnet_loss.h).
+// The training loss with void labels and a focal term (include/lmnet_loss.h; that header's lmn_image_stats is in metrics.hip).
 // Same structure as the loss of rows.hip: a sums pass, a one-block finish that writes the loss terms and the backward coefficients, a
 // dlogits pass; templates for C in {2, 3, 4, 8}, general-C kernels that stage the logits in LDS.
 //   sums: [0] S_w = sum_valid w_y   [1] sum_valid w_y*(-log p_y)   [2] sum_valid sum_c w_c*(-log p_c)   [3] focal sum
@@ -298,71 +298,6 @@ __global__ __launch_bounds__(256) void segloss_ex_bwd_gen_kernel(const float* __
   }
 }
 
-// tp / fp / fn / tn per image and class.  blockIdx.y is the image, blockIdx.x strides over ITS pixels only, so a block's LDS
-// counters (predicted, labelled and correct pixels per class, and the valid pixels) belong to one image whatever HW is.  Small C
-// counts by wave ballots (a handful of lanes would otherwise serialise on two or three LDS words); larger C by LDS atomics.
-__global__ __launch_bounds__(256) void image_stats_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ pred_labels,
-                                                          const int64_t* __restrict__ target, int C, int64_t hw,
-                                                          unsigned long long* __restrict__ stats) {
-  __shared__ int s_cnt[3 * LX_MAXC + 1];              // [0..C) tp, [C..2C) predicted, [2C..3C) labelled, [3C] valid
-  for (int i = threadIdx.x; i <= 3 * C; i += 256) s_cnt[i] = 0;
-  __syncthreads();
-  const int b = blockIdx.y, lane = threadIdx.x & 63;
-  const int64_t* tg = target + (int64_t)b * hw;
-  for (int64_t base = (int64_t)blockIdx.x * 256; base < hw; base += (int64_t)gridDim.x * 256) {   // (uniform trip count per wave)
-    const int64_t i = base + threadIdx.x;
-    int y = -1, best = -1;
-    if (i < hw) {
-      const int64_t yl = tg[i];
-      if ((uint64_t)yl < (uint64_t)C) {
-        y = (int)yl;
-        if (logits) {
-          const float* lg = logits + (int64_t)b * C * hw + i;
-          best = 0;
-          float bv = lg[0];
-#pragma unroll 8
-          for (int c = 1; c < C; ++c) {
-            const float v = lg[c * hw];
-            if (v > bv) { bv = v; best = c; }         // first maximum wins, as torch.argmax
-          }
-        } else {
-          const int p = pred_labels[(int64_t)b * hw + i];
-          best = p < C ? p : -1;                      // values >= C: no class
-        }
-      }
-    }
-    if (C <= 8) {
-      const int nv = __popcll(__ballot(y >= 0));
-      if (nv == 0) continue;
-      if (lane == 0) atomicAdd(&s_cnt[3 * C], nv);
-      for (int c = 0; c < C; ++c) {
-        const int np = __popcll(__ballot(y >= 0 && best == c)), nl = __popcll(__ballot(y == c)), nt = __popcll(__ballot(y == c && best == c));
-        if (lane == 0) {
-          if (nt) atomicAdd(&s_cnt[c], nt);
-          if (np) atomicAdd(&s_cnt[C + c], np);
-          if (nl) atomicAdd(&s_cnt[2 * C + c], nl);
-        }
-      }
-    } else if (y >= 0) {
-      atomicAdd(&s_cnt[3 * C], 1);
-      atomicAdd(&s_cnt[2 * C + y], 1);
-      if (best >= 0) atomicAdd(&s_cnt[C + best], 1);
-      if (best == y) atomicAdd(&s_cnt[y], 1);
-    }
-  }
-  __syncthreads();
-  const int nvalid = s_cnt[3 * C];
-  if (nvalid == 0) return;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const int tp = s_cnt[c], np = s_cnt[C + c], nl = s_cnt[2 * C + c];
-    unsigned long long* o = stats + ((int64_t)b * C + c) * 4;
-    if (tp) atomicAdd(o + 0, (unsigned long long)tp);
-    if (np - tp) atomicAdd(o + 1, (unsigned long long)(np - tp));
-    if (nl - tp) atomicAdd(o + 2, (unsigned long long)(nl - tp));
-    atomicAdd(o + 3, (unsigned long long)(nvalid - np - nl + tp));   // >= 0: pixels predicted or labelled c are among the valid
-  }
-}
-
 // the argument checks shared by the two loss entries
 int lx_check(const char* what, int B, int C, int64_t HW, const lmn_loss_param_t* p) {
   LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= LX_MAXC, "%s: C=%d not in [2, %d]", what, C, LX_MAXC);
@@ -446,22 +381,6 @@ int lmn_segloss_ex_bwd(const float* logits, const int64_t* target, const float* 
   }
 #undef LX_BWD
   return lmn_launch_status("segloss_ex_bwd");
-}
-
-int lmn_image_stats(const float* logits, const uint8_t* pred_labels, const int64_t* target, int B, int C, int64_t HW, int has_ignore,
-                    int64_t ignore_index, int64_t* stats, lmn_stream_t stream) {
-  LMN_REQUIRE(target && stats, "image_stats: null pointer");
-  LMN_REQUIRE((logits != nullptr) != (pred_labels != nullptr), "image_stats: exactly one of logits and pred_labels must be given");
-  LMN_REQUIRE(C >= 2 && C <= LX_MAXC, "image_stats: C=%d not in [2, %d]", C, LX_MAXC);
-  LMN_REQUIRE(B > 0 && B <= 65535 && HW > 0 && HW < (1LL << 31), "image_stats: B=%d, HW=%lld (need B <= 65535, HW < 2^31)", B, (long long)HW);
-  LMN_REQUIRE(!has_ignore || ignore_index < 0 || ignore_index >= C, "image_stats: ignore_index=%lld inside [0, %d)", (long long)ignore_index, C);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t words = (int64_t)B * C * 8;
-  LMN_LAUNCH(loss_zero_kernel, dim3(loss_grid(words, 64)), dim3(256), 0, st, (uint32_t*)stats, words);
-  const int per_image = 512 / B > 0 ? 512 / B : 1;          // (few blocks per image: every block ends in 4C same-address atomics)
-  LMN_LAUNCH(image_stats_kernel, dim3(loss_grid(HW, per_image), B), dim3(256), 0, st, logits, pred_labels, target, C, HW,
-             (unsigned long long*)stats);
-  return lmn_launch_status("image_stats");
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@
 // block: every loop is a find / union loop that either lowers a parent or ends.
 //
 // Cleaning (lmn_post_clean):
-//   4. post_labels_kernel arg-max (first maximum wins, as confusion_kernel) or the given label map -> uint8 L0 (outside [0, C) -> 0)
+//   4. post_labels_kernel arg-max (pred_common.h) or the given label map -> uint8 L0 (outside [0, C) -> 0)
 //   5. post_select_kernel root pixels offer (area << 32 | ~root) to their (sample, class) slot: block-level max in LDS, then one
 //                         64-bit atomic max per block and slot; counts components per class.
 //   6. post_apply_kernel  L1 = L0 without the components that do not survive keep_largest / min_area.
@@ -25,7 +25,7 @@
 // Render (lmn_post_render): post_render_kernel, one launch per 64 samples of a ragged batch: nearest resize to the frame (the
 // lmn_preprocess_u8 mask arithmetic with source and destination exchanged), 16 pixels per thread with 16-byte stores, fill or contour
 // overlay blended in 8-bit fixed point.  No frame-size intermediate.
-#include "common.h"
+#include "pred_common.h"
 
 #define POST_TH 32
 #define POST_TW 64
@@ -236,20 +236,11 @@ __global__ __launch_bounds__(256) void post_labels_kernel(const float* __restric
     int best;
     if (logits) {
       const int64_t b = idx / hw, i = idx - b * hw;
-      const float* lg = logits + b * C * hw + i;
-      best = 0;
-      float bv = lg[0];
-#pragma unroll 8
-      for (int c = 1; c < C; ++c) {
-        const float v = lg[c * hw];
-        if (v > bv) { bv = v; best = c; }  // first maximum wins, as torch.argmax
-      }
+      best = pred_argmax(logits + b * C * hw + i, C, hw);
     } else if (lab8) {
-      const int p = lab8[idx];
-      best = p < C ? p : 0;
+      best = pred_class(lab8[idx], C, 0);
     } else {
-      const int64_t p = lab64[idx];
-      best = (p >= 0 && p < C) ? (int)p : 0;
+      best = pred_class(lab64[idx], C, 0);
     }
     out[idx] = (uint8_t)best;
   }
@@ -451,22 +442,6 @@ __global__ __launch_bounds__(256) void post_render_kernel(const uint8_t* __restr
   }
 }
 
-// Confusion matrix of a label-map prediction (lmn_confusion with the arg-max already taken): int32 histogram per block in LDS.
-__global__ __launch_bounds__(256) void confusion_labels_kernel(const uint8_t* __restrict__ pred, const int64_t* __restrict__ target, int C,
-                                                               int64_t total, float* __restrict__ counts) {
-  extern __shared__ int s_hist[];                     // [C * C]
-  for (int i = threadIdx.x; i < C * C; i += 256) s_hist[i] = 0;
-  __syncthreads();
-  for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int p = pred[idx];
-    const int64_t y = target[idx];
-    if (p < C && y >= 0 && y < C) atomicAdd(&s_hist[(int)y * C + p], 1);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < C * C; i += 256)
-    if (s_hist[i]) atomicAdd(counts + i, (float)s_hist[i]);
-}
-
 bool post_dims_ok(int B, int H, int W) {
   return B >= 1 && B <= 65535 && H >= 2 && H <= POST_MAXSIDE && W >= 2 && W <= POST_MAXSIDE;
 }
@@ -606,17 +581,6 @@ int lmn_post_render(const uint8_t* labels_net, int B, int H, int W, const int32_
                labels_out ? labels_out + (int64_t)b0 * plane : (uint8_t*)nullptr, overlay ? overlay + (int64_t)b0 * plane * 3 : (uint8_t*)nullptr);
   }
   return lmn_launch_status("post_render");
-}
-
-int lmn_confusion_labels(const uint8_t* pred_labels, const int64_t* target, int B, int C, int64_t HW, float* counts, lmn_stream_t stream) {
-  LMN_REQUIRE(pred_labels && target && counts, "confusion_labels: null pointer");
-  LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= 64, "confusion_labels: C=%d not in [2, 64]", C);
-  LMN_REQUIRE((int64_t)B * HW < (1LL << 24) * 64, "confusion_labels: more than 2^30 pixels per call");
-  const int64_t total = (int64_t)B * HW;
-  const int grid = lmn_cdiv(total, 256) < 1024 ? lmn_cdiv(total, 256) : 1024;
-  LMN_LAUNCH(confusion_labels_kernel, dim3(grid), dim3(256), (size_t)C * C * sizeof(int), (hipStream_t)stream, pred_labels, target, C, total,
-             counts);
-  return lmn_launch_status("confusion_labels");
 }
 
 }  // extern "C"

@@ -1212,70 +1212,6 @@ __global__ __launch_bounds__(256) void preprocess_u8_ex_kernel(const uint8_t* __
 }
 
 
-// Confusion matrix of argmax(logits) against the labels: counts[t*C + p] += 1 (float counts are
-// exact up to 2^24 per launch per cell; the host accumulates in int64/double).
-template <int C>
-__global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                        int B, int64_t hw, float* __restrict__ counts) {
-  __shared__ float sc[C * C];
-  for (int i = threadIdx.x; i < C * C; i += 256) sc[i] = 0.f;
-  __syncthreads();
-  int cnt[C * C];
-#pragma unroll
-  for (int k = 0; k < C * C; ++k) cnt[k] = 0;
-  const int64_t total = (int64_t)B * hw;
-  for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = idx / hw, i = idx - b * hw;
-    const float* lg = logits + b * C * hw;
-    int best = 0;
-    float bv = lg[i];
-#pragma unroll
-    for (int c = 1; c < C; ++c) {
-      const float v = lg[c * hw + i];
-      if (v > bv) { bv = v; best = c; }  // first maximum wins, as torch.argmax
-    }
-    const int y = (int)target[idx];
-#pragma unroll
-    for (int k = 0; k < C * C; ++k) cnt[k] += (k == y * C + best) ? 1 : 0;
-  }
-#pragma unroll
-  for (int k = 0; k < C * C; ++k) {
-    int v = cnt[k];
-#pragma unroll
-    for (int m = 1; m <= 32; m <<= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&sc[k], (float)v);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < C * C; i += 256)
-    if (sc[i] != 0.f) atomicAdd(counts + i, sc[i]);
-}
-
-// General class count (5 <= C <= 64): the block's C x C histogram lives in LDS as int32 (16 KB at C = 64) instead of C^2 registers per
-// thread; labels outside [0, C) are dropped (Evaluator._generate_matrix).
-__global__ __launch_bounds__(256) void confusion_gen_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                            int B, int C, int64_t hw, float* __restrict__ counts) {
-  extern __shared__ int s_hist[];                     // [C * C]
-  for (int i = threadIdx.x; i < C * C; i += 256) s_hist[i] = 0;
-  __syncthreads();
-  const int64_t total = (int64_t)B * hw;
-  for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = idx / hw, i = idx - b * hw;
-    const float* lg = logits + b * C * hw + i;
-    int best = 0;
-    float bv = lg[0];
-#pragma unroll 8
-    for (int c = 1; c < C; ++c) {
-      const float v = lg[c * hw];
-      if (v > bv) { bv = v; best = c; }  // first maximum wins, as torch.argmax
-    }
-    const int64_t y = target[idx];
-    if (y >= 0 && y < C) atomicAdd(&s_hist[(int)y * C + best], 1);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < C * C; i += 256)
-    if (s_hist[i]) atomicAdd(counts + i, (float)s_hist[i]);
-}
-
 __global__ void copy2d_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows, int cols, int xs, int ys) {
   const int64_t n = rows * cols;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -1630,21 +1566,6 @@ int lmn_segloss_bwd(const float* logits, const int64_t* target, const float* w_c
                         gscale, B, C, HW, dlogits); break;   // (<= 64 KB of LDS at C = 64)
   }
   return lmn_launch_status("segloss_bwd");
-}
-
-int lmn_confusion(const float* logits, const int64_t* target, int B, int C, int64_t HW, float* counts, lmn_stream_t stream) {
-  LMN_REQUIRE(logits && target && counts, "confusion: null pointer");
-  LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= 64, "confusion: C=%d not in [2, 64]", C);
-  LMN_REQUIRE((int64_t)B * HW < (1LL << 24) * 64, "confusion: more than 2^30 pixels per call");
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = grid_for((int64_t)B * HW) > 512 ? 512 : grid_for((int64_t)B * HW);
-  switch (C) {
-    case 2: LMN_LAUNCH((confusion_kernel<2>), dim3(grid), dim3(256), 0, st, logits, target, B, HW, counts); break;
-    case 3: LMN_LAUNCH((confusion_kernel<3>), dim3(grid), dim3(256), 0, st, logits, target, B, HW, counts); break;
-    case 4: LMN_LAUNCH((confusion_kernel<4>), dim3(grid), dim3(256), 0, st, logits, target, B, HW, counts); break;
-    default: LMN_LAUNCH(confusion_gen_kernel, dim3(grid), dim3(256), (size_t)C * C * sizeof(int), st, logits, target, B, C, HW, counts); break;
-  }
-  return lmn_launch_status("confusion");
 }
 
 int lmn_preprocess_u8_ex(const uint8_t* images, const uint8_t* masks, const uint8_t* flips, int B, int Hs, int Ws, int H, int W,

@@ -5,8 +5,8 @@
 // pixels of the other mask.  Every squared distance is an int32 (<= 2 * 1023^2 < 2^21); the only floating-point values are the
 // two float64 sums of sqrt, formed in a fixed order.  No float atomics: two runs on one input give bit-identical statistics.
 //
-//   1. surf_labels_kernel   arg-max of the logits (first maximum wins, as confusion_kernel) or the given label map, and the
-//                           target, narrowed to uint8 (255 = no class), once for all classes.
+//   1. surf_labels_kernel   arg-max of the logits (pred_common.h) or the given label map, and the target, narrowed to uint8
+//                           (255 = no class), once for all classes.
 //   2. surf_col_kernel      per (map, pair), one lane per column: border test on the four neighbours (outside the image counts
 //                           as outside the mask) -> g(y, x) = vertical distance to the nearest border pixel of the column
 //                           (uint16, SURF_INF where the column has none).  g == 0 marks the border pixels.
@@ -17,7 +17,7 @@
 //   4. surf_finish_kernel   per pair: directed maxima, float64 sums of sqrt(D2) (per-thread sums over fixed rows, then a fixed tree) and
 //                           the two order statistics of the pooled D2 multiset by a two-level radix select (11 + 10 bits) on
 //                           integer histograms in LDS.
-#include "common.h"
+#include "pred_common.h"
 
 #define SURF_INF 32768            // column sentinel: SURF_INF^2 + 1023^2 < 2^31
 #define SURF_MAXSIDE 1024
@@ -40,21 +40,13 @@ __global__ __launch_bounds__(256) void surf_labels_kernel(const float* __restric
     int best;
     if (logits) {
       const int64_t b = idx / hw, i = idx - b * hw;
-      const float* lg = logits + b * C * hw + i;
-      best = 0;
-      float bv = lg[0];
-#pragma unroll 8
-      for (int c = 1; c < C; ++c) {
-        const float v = lg[c * hw];
-        if (v > bv) { bv = v; best = c; }  // first maximum wins, as torch.argmax
-      }
+      best = pred_argmax(logits + b * C * hw + i, C, hw);
     } else {
-      const int64_t p = plab[idx];
-      best = (p >= 0 && p < C) ? (int)p : 255;
+      best = pred_class(plab[idx], C, 255);
     }
     const int64_t t = target[idx];
     lab[idx] = (uint8_t)best;
-    lab[total + idx] = (t >= 0 && t < C) ? (uint8_t)t : (uint8_t)255;
+    lab[total + idx] = (uint8_t)pred_class(t, C, 255);
   }
 }
 

@@ -1010,23 +1010,30 @@ def _pl(t):
     return C.c_void_p(t.data_ptr())
 
 
-def segloss_fwd(logits, target, w_ce, w_dice, label_smoothing, smooth, sums, coef, loss):
+def _dims(logits):
+    """B, C and the pixels per plane of logits [B, C, ...]"""
     B, Cn = logits.shape[0], logits.shape[1]
-    hw = logits.numel() // (B * Cn)
+    return B, Cn, logits.numel() // (B * Cn)
+
+
+def segloss_fwd(logits, target, w_ce, w_dice, label_smoothing, smooth, sums, coef, loss):
+    B, Cn, hw = _dims(logits)
     _check(load().lmn_segloss_fwd(_p(logits), _pl(target), _p(w_ce), _p(w_dice), B, Cn, _i64(hw), _f(label_smoothing),
                                   _f(smooth), _p(sums), _p(coef), _p(loss), _stream()), "segloss_fwd")
 
 
 def segloss_bwd(logits, target, w_ce, coef, gscale, dlogits):
-    B, Cn = logits.shape[0], logits.shape[1]
-    hw = logits.numel() // (B * Cn)
+    B, Cn, hw = _dims(logits)
     _check(load().lmn_segloss_bwd(_p(logits), _pl(target), _p(w_ce), _p(coef), _p(gscale), B, Cn, _i64(hw), _p(dlogits),
                                   _stream()), "segloss_bwd")
 
 
 def confusion(logits, target, counts):
-    B, Cn = logits.shape[0], logits.shape[1]
-    hw = logits.numel() // (B * Cn)
+    """counts[t*C + p] += pixels with label t and arg-max p of fp32 logits [B, C, ...] (lmn_confusion); counts: C*C floats."""
+    B, Cn, hw = _dims(logits)
+    if counts.numel() != Cn * Cn or target.numel() != B * hw:
+        raise ValueError("lm_net_amd.confusion: logits %s need %d x %d counts and %d labels, got counts %s and target %s"
+                         % (tuple(logits.shape), Cn, Cn, B * hw, tuple(counts.shape), tuple(target.shape)))
     _check(load().lmn_confusion(_p(logits), _pl(target), B, Cn, _i64(hw), _p(counts), _stream()), "confusion")
 
 
@@ -1044,8 +1051,7 @@ def loss_param(ignore_index=None, label_smoothing=0.0, smooth=1e-5, ce_scale=1.0
 def segloss_ex_fwd(logits, target, w_ce, w_dice, param, sums, coef, loss4):
     """loss4 = [total, ce, dice, focal] with void labels and the focal term (lmn_segloss_ex_fwd); param: a LossParam; sums / coef:
     fp32 workspaces of at least loss_sums_floats(C) / loss_coef_floats(C)."""
-    B, Cn = logits.shape[0], logits.shape[1]
-    hw = logits.numel() // (B * Cn)
+    B, Cn, hw = _dims(logits)
     if sums.numel() < loss_sums_floats(Cn) or coef.numel() < loss_coef_floats(Cn) or loss4.numel() < 4:
         raise ValueError("lm_net_amd.segloss_ex_fwd: workspace too small for %d classes" % Cn)
     _check(load().lmn_segloss_ex_fwd(_p(logits), _pl(target), _p(w_ce), _p(w_dice), B, Cn, _i64(hw), C.byref(param), _p(sums), _p(coef),
@@ -1054,8 +1060,7 @@ def segloss_ex_fwd(logits, target, w_ce, w_dice, param, sums, coef, loss4):
 
 def segloss_ex_bwd(logits, target, w_ce, coef, gscale, param, dlogits):
     """dlogits = gscale[0] * d total / d logits (gscale None: 1) from the coef of segloss_ex_fwd (lmn_segloss_ex_bwd)."""
-    B, Cn = logits.shape[0], logits.shape[1]
-    hw = logits.numel() // (B * Cn)
+    B, Cn, hw = _dims(logits)
     if coef.numel() < loss_coef_floats(Cn) or dlogits.numel() != logits.numel():
         raise ValueError("lm_net_amd.segloss_ex_bwd: coef or dlogits does not match %d classes" % Cn)
     _check(load().lmn_segloss_ex_bwd(_p(logits), _pl(target), _p(w_ce), _p(coef), _p(gscale), B, Cn, _i64(hw), C.byref(param), _p(dlogits),
@@ -1207,6 +1212,8 @@ def confusion_labels(pred, target, counts):
     if target.numel() != pred.numel():
         raise ValueError("lm_net_amd.confusion_labels: pred %s does not match target %s" % (tuple(pred.shape), tuple(target.shape)))
     n = int(counts.shape[0])
+    if counts.numel() != n * n:
+        raise ValueError("lm_net_amd.confusion_labels: counts %s is not a square [C, C] matrix" % (tuple(counts.shape),))
     _check(load().lmn_confusion_labels(_raw(pred, torch.uint8, "confusion_labels"), _pl(target), B, n, _i64(hw), _p(counts), _stream()),
            "confusion_labels")
 

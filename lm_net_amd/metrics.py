@@ -25,6 +25,32 @@ import torch
 from . import hip
 
 
+def _prediction(pred, n_classes, what, label_dtype):
+    """The one input contract of the meters' predictions (pure: no device check).  Floating-point logits [B, C, H, W] with
+    C = n_classes come back contiguous fp32; an integer or bool label map [B, H, W] comes back contiguous as ``label_dtype``:
+    torch.uint8 (-1 and everything >= 255 become 255, "no class") or torch.int64."""
+    if pred.dim() == 4 and pred.is_floating_point():
+        if pred.shape[1] != n_classes:
+            raise ValueError("%s: logits with %d channels, n_classes = %d" % (what, pred.shape[1], n_classes))
+        return pred.contiguous().float()
+    if pred.dim() != 3 or pred.is_floating_point():
+        raise ValueError("%s: pred must be logits [B, C, H, W] or an INTEGER label map [B, H, W], got a %d-D %s tensor"
+                         % (what, pred.dim(), pred.dtype))
+    if label_dtype == torch.int64:
+        return pred.contiguous().long()
+    if pred.dtype not in (torch.uint8, torch.bool):
+        pred = pred.clamp(-1, 255)                               # (-1 -> 255: no class)
+    return pred.to(torch.uint8).contiguous()
+
+
+def _target(target, pred, what):
+    """The labels of a prediction as _prediction returns it: contiguous int64 [B, H, W] of the prediction's batch and image size."""
+    target = target.contiguous().long()
+    if target.dim() != 3 or target.shape[0] != pred.shape[0] or target.shape[-2:] != pred.shape[-2:]:
+        raise ValueError("%s: target %s does not match pred %s" % (what, tuple(target.shape), tuple(pred.shape)))
+    return target
+
+
 class ConfusionMeter:
     def __init__(self, n_classes=2, device="cuda"):
         if not 2 <= n_classes <= 64:
@@ -42,17 +68,9 @@ class ConfusionMeter:
         if not logits.is_cuda:
             raise RuntimeError("lm_net_amd.ConfusionMeter: device tensors required (the HIP path has no CPU fallback)")
         counts = torch.zeros(self.n, self.n, device=logits.device)      # exact: < 2^24 per cell and launch
-        if logits.dim() == 3 and logits.is_floating_point():
-            raise ValueError("ConfusionMeter: pred must be logits [B, C, H, W] or an INTEGER label map [B, H, W], got a 3-D %s tensor"
-                             % logits.dtype)
-        if logits.dim() == 3:
-            if logits.dtype in (torch.uint8, torch.bool):
-                pred = logits.to(torch.uint8)
-            else:
-                pred = logits.clamp(-1, 255).to(torch.uint8)      # (-1 -> 255: no class)
-            hip.confusion_labels(pred.contiguous(), target.contiguous().long(), counts)
-        else:
-            hip.confusion(logits.contiguous().float(), target.contiguous().long(), counts)
+        pred = _prediction(logits, self.n, "ConfusionMeter", torch.uint8)
+        target = _target(target, pred, "ConfusionMeter")
+        (hip.confusion if pred.dim() == 4 else hip.confusion_labels)(pred, target, counts)
         self.total += counts.double()
 
     def compute(self):
@@ -202,19 +220,8 @@ class ImageStatsMeter(_RawStatsMeter):
     def update(self, pred, target):
         if not pred.is_cuda or not target.is_cuda:
             raise RuntimeError("lm_net_amd.ImageStatsMeter: device tensors required (the HIP path has no CPU fallback)")
-        if pred.dim() == 4:
-            if pred.shape[1] != self.n:
-                raise ValueError("ImageStatsMeter: logits with %d channels, n_classes = %d" % (pred.shape[1], self.n))
-            pred = pred.contiguous().float()
-        elif pred.dim() == 3 and not pred.is_floating_point():
-            if pred.dtype not in (torch.uint8, torch.bool):
-                pred = pred.clamp(-1, 255)                       # (-1 -> 255: no class)
-            pred = pred.to(torch.uint8).contiguous()
-        else:
-            raise ValueError("ImageStatsMeter: pred must be logits [B, C, H, W] or an integer label map [B, H, W]")
-        target = target.contiguous().long()
-        if target.dim() != 3 or target.shape[0] != pred.shape[0] or target.shape[-2:] != pred.shape[-2:]:
-            raise ValueError("ImageStatsMeter: target %s does not match pred %s" % (tuple(target.shape), tuple(pred.shape)))
+        pred = _prediction(pred, self.n, "ImageStatsMeter", torch.uint8)
+        target = _target(target, pred, "ImageStatsMeter")
         stats = torch.empty(target.shape[0], self.n, 4, device=pred.device, dtype=torch.int64)
         hip.image_stats(pred, target, self.n, self.ignore_index, stats)
         self._stats.append(stats)
@@ -338,17 +345,8 @@ class SurfaceDistanceMeter:
     def update(self, pred, target):
         if not pred.is_cuda or not target.is_cuda:
             raise RuntimeError("lm_net_amd.SurfaceDistanceMeter: device tensors required (the HIP path has no CPU fallback)")
-        if pred.dim() == 4:
-            if pred.shape[1] != self.n:
-                raise ValueError("SurfaceDistanceMeter: logits with %d channels, n_classes = %d" % (pred.shape[1], self.n))
-            pred = pred.contiguous().float()
-        elif pred.dim() == 3 and not pred.is_floating_point():
-            pred = pred.contiguous().long()
-        else:
-            raise ValueError("SurfaceDistanceMeter: pred must be logits [B, C, H, W] or an integer label map [B, H, W]")
-        target = target.contiguous().long()
-        if target.dim() != 3 or target.shape[0] != pred.shape[0] or target.shape[-2:] != pred.shape[-2:]:
-            raise ValueError("SurfaceDistanceMeter: target %s does not match pred %s" % (tuple(target.shape), tuple(pred.shape)))
+        pred = _prediction(pred, self.n, "SurfaceDistanceMeter", torch.int64)
+        target = _target(target, pred, "SurfaceDistanceMeter")
         B, H, W = target.shape
         nk = len(self.classes)
         bs, ks = self.chunking(B, H, W)

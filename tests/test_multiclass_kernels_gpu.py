@@ -1,4 +1,4 @@
-"""GPU: the general-class-count kernels of csrc/rows.hip and the ABI 15 input pipeline entry.
+"""GPU: the general-class-count kernels of csrc/rows.hip (loss) and csrc/metrics.hip (confusion), and the ABI 15 input pipeline entry.
 
   * fused loss (lmn_segloss_fwd / _bwd) at C outside {2, 3, 4, 8}: loss and dlogits against a float64 torch restatement and against
     the reference DiceLoss + CrossEntropyLoss goldens (tests/golden/mc_loss_metrics.npz, tools/make_golden_multiclass.py);
