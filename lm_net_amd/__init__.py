@@ -6,7 +6,8 @@ Around the path (SURVEY.md section 8f "next" rows): ``lm_net_amd.loss.SegLoss`` 
 ``FocalLoss``), ``lm_net_amd.metrics.ImageStatsMeter`` (per-image tp / fp / fn / tn and the metric set built on them),
 ``lm_net_amd.loss.SigmoidSegLoss`` and ``lm_net_amd.metrics.SigmoidStatsMeter`` (BCE + Dice + focal and the thresholded statistics of
 one-logit and multi-label sigmoid heads),
-``lm_net_amd.optim.FusedAdamW`` (one-launch AdamW), ``lm_net_amd.metrics.ConfusionMeter`` (on-device Dice / IoU),
+``lm_net_amd.optim.FusedAdamW`` (one-launch AdamW; parameter groups, gradient clipping, the GradScaler skip and an EMA of the weights
+without a host decision; ``lm_net_amd.optim.decay_groups``), ``lm_net_amd.metrics.ConfusionMeter`` (on-device Dice / IoU),
 ``lm_net_amd.metrics.SurfaceDistanceMeter`` (on-device HD / HD95 / ASSD / RVD),
 ``lm_net_amd.post.DevicePostprocess`` (on-device arg-max, connected-component cleaning, resize back to the frame, overlay),
 ``lm_net_amd.ddp.DistributedLMNet`` (bucketed RCCL gradient all-reduce).

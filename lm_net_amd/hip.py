@@ -201,6 +201,30 @@ class PostParam(C.Structure):
     _fields_ = [("connectivity", C.c_int32), ("hole_limit", C.c_int32), ("class_mask", C.c_uint64), ("keep_largest_mask", C.c_uint64),
                 ("min_area", C.c_int32 * 64)]
 
+class OptimParam(C.Structure):
+    """Mirror of lmn_optim_param_t (include/optim/lmnet_optim.h): the scalar parameters of lmn_optim_prepare / lmn_adamw_step_ex."""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float), ("max_norm", C.c_float), ("ema_decay", C.c_float),
+                ("flags", C.c_int32), ("n_groups", C.c_int32), ("_pad", C.c_int32 * 7)]
+
+
+# LMN_OPTIM_* of include/optim/lmnet_optim.h
+OPTIM_MAX_GROUPS, OPTIM_GRID_CAP, OPTIM_PARAM_BYTES = 16, 1024, 64
+OPTIM_SKIP_NONFINITE, OPTIM_NORM = 1, 2
+OPTIM_CTRL_WORDS, OPTIM_GROUP_WORDS = 16, 64
+(OPTIM_SKIP, OPTIM_STEP, OPTIM_SKIPPED, OPTIM_GRAD_NORM, OPTIM_INV_SCALE, OPTIM_COEF, OPTIM_INV_BC1, OPTIM_INV_SQRT_BC2,
+ OPTIM_NONFINITE) = range(9)
+
+
+def optim_blocks(n):
+    """Blocks of the reduction of lmn_optim_prepare over n floats: the control block starts at word 2 * optim_blocks(n)."""
+    return max(1, min((int(n) // 4 + 255) // 256, OPTIM_GRID_CAP))
+
+
+def optim_workspace_words(n):
+    """lmn_optim_workspace restated (include/optim/lmnet_optim.h): block partials, block counts, control block, group table."""
+    return 2 * optim_blocks(n) + OPTIM_CTRL_WORDS + OPTIM_GROUP_WORDS if n > 0 else 0
+
+
 # The C ABI, one list per header: every symbol that header declares.  The headers stay apart, one per feature; HEADERS is the one
 # registry of them.  load() checks the library against it, tests/test_host_cpu.py checks it against the headers, and the guard manifest
 # (tests/guard.py) partitions EXPORTS, so that a new export in any header needs a guard test or a stated reason why none applies.
@@ -236,6 +260,12 @@ STRUCTS = [(ConvArgs, "lmn_sizeof_conv_args"), (SrcT, "lmn_sizeof_src"), (WgradA
            (PostParam, "lmn_sizeof_post_param"), (OneOfParam, "lmn_sizeof_oneof_param"), (LossParam, "lmn_sizeof_loss_param"),
            (SigParam, "lmn_sizeof_sig_param")]
 
+# include/optim/lmnet_optim.h: parameter groups, clipping, the loss-scale skip and EMA of the one-launch AdamW.  A list of its own
+# beside EXPORTS: HEADERS / STRUCTS and the guard manifest are pinned by tests/test_host_cpu.py and tests/guard.py as they stand.
+# load() checks these symbols and the struct size all the same; tests/test_optim_cpu.py checks the list against the header and
+# ties the entries that write device memory to tests/test_guard_optim_gpu.py.
+SYMBOLS_OPTIM = ["lmn_sizeof_optim_param", "lmn_optim_workspace", "lmn_optim_prepare", "lmn_adamw_step_ex"]
+
 _lib = None
 
 
@@ -249,7 +279,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS:
+    for name in EXPORTS + SYMBOLS_OPTIM:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -258,13 +288,14 @@ def load():
     lib.lmn_surface_workspace.restype = C.c_int64
     lib.lmn_post_workspace.restype = C.c_int64
     lib.lmn_oneof_workspace.restype = C.c_int64
+    lib.lmn_optim_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
     lib.lmn_prof_end.restype = C.c_int64
     if lib.lmn_abi_version() != ABI_VERSION:
         raise RuntimeError("lm_net_amd: ABI version mismatch")
-    for struct, sizeof in STRUCTS:
+    for struct, sizeof in STRUCTS + [(OptimParam, "lmn_sizeof_optim_param")]:
         n = getattr(lib, sizeof)()
         if n != C.sizeof(struct):
             raise RuntimeError("lm_net_amd: layout of %s differs between hip.py (%d bytes) and the library (%s() = %d)"
@@ -1403,6 +1434,52 @@ def augment_oneof_u8(images, masks, params, src_hw, params_dev, scratch, gray_su
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2):
     _check(load().lmn_adamw_step(_p(p), _p(g), _p(m), _p(v), _i64(p.numel()), _f(lr), _f(beta1), _f(beta2), _f(eps),
                                  _f(weight_decay), _f(bias_corr1), _f(bias_corr2), _stream()), "adamw_step")
+
+
+def optim_workspace(n):
+    """4-byte words of the workspace of optim_prepare / adamw_step_ex for n floats (lmn_optim_workspace)."""
+    return int(load().lmn_optim_workspace(_i64(n)))
+
+
+def optim_param(betas=(0.9, 0.999), eps=1e-8, max_norm=None, ema_decay=None, flags=0, n_groups=1):
+    """An OptimParam (lmn_optim_param_t) from Python values; max_norm None: no clipping, ema_decay None: no EMA.  Clipping and
+    OPTIM_SKIP_NONFINITE switch OPTIM_NORM on."""
+    p = OptimParam()
+    p.beta1, p.beta2, p.eps = float(betas[0]), float(betas[1]), float(eps)
+    p.max_norm = 0.0 if max_norm is None else float(max_norm)
+    p.ema_decay = -1.0 if ema_decay is None else float(ema_decay)
+    p.flags = int(flags) | (OPTIM_NORM if (p.max_norm > 0 or int(flags) & OPTIM_SKIP_NONFINITE) else 0)
+    p.n_groups = int(n_groups)
+    return p
+
+
+def _optim_dims(what, g, qgroup, ws):
+    n = g.numel()
+    if n % 4 or qgroup.numel() != n // 4:
+        raise ValueError("lm_net_amd.%s: %d floats need %d group bytes, got %d" % (what, n, n // 4, qgroup.numel()))
+    if ws.numel() < optim_workspace_words(n):
+        raise ValueError("lm_net_amd.%s: workspace of %d words, %d needed" % (what, ws.numel(), optim_workspace_words(n)))
+    return n
+
+
+def optim_prepare(g, qgroup, param, ws, grad_scale=None, found_inf=None):
+    """The control block of one step from the flat gradient g (lmn_optim_prepare): non-finite count, gradient norm, clip coefficient,
+    step count and bias corrections, left in ws for adamw_step_ex.  qgroup: uint8 [n / 4]; param: an OptimParam; ws: fp32 workspace
+    of at least optim_workspace(n) words whose group table the caller has filled; grad_scale / found_inf: the device scalars of
+    torch.amp.GradScaler, or None."""
+    n = _optim_dims("optim_prepare", g, qgroup, ws)
+    _check(load().lmn_optim_prepare(_p(g), _i64(n), _raw(qgroup, torch.uint8, "optim_prepare"), C.byref(param), _p(ws), _p(grad_scale),
+                                    _p(found_inf), _stream()), "optim_prepare")
+
+
+def adamw_step_ex(p, g, m, v, ema, qgroup, param, ws):
+    """One AdamW step over the flat buffers from the control block optim_prepare left in ws (lmn_adamw_step_ex); ema None: no EMA.
+    g is read-only: it is not unscaled or clipped in place."""
+    n = _optim_dims("adamw_step_ex", g, qgroup, ws)
+    if not (p.numel() == m.numel() == v.numel() == n) or (ema is not None and ema.numel() != n):
+        raise ValueError("lm_net_amd.adamw_step_ex: the flat buffers differ in size")
+    _check(load().lmn_adamw_step_ex(_p(p), _p(g), _p(m), _p(v), _p(ema), _i64(n), _raw(qgroup, torch.uint8, "adamw_step_ex"),
+                                    C.byref(param), _p(ws), _stream()), "adamw_step_ex")
 
 
 def reparam_fold(hstats, mean, rstd, A, count, batch_stats, w_expand, b_expand, w_shortcut, rows, cred, wpack, kbias, coef, dgamma,
