@@ -10,6 +10,7 @@ one-logit and multi-label sigmoid heads),
 without a host decision; ``lm_net_amd.optim.decay_groups``), ``lm_net_amd.metrics.ConfusionMeter`` (on-device Dice / IoU),
 ``lm_net_amd.metrics.SurfaceDistanceMeter`` (on-device HD / HD95 / ASSD / RVD),
 ``lm_net_amd.post.DevicePostprocess`` (on-device arg-max, connected-component cleaning, resize back to the frame, overlay),
+``lm_net_amd.infer.TiledPredictor`` (frames of any size: overlapping tiles, mirrored copies and one blend launch),
 ``lm_net_amd.ddp.DistributedLMNet`` (bucketed RCCL gradient all-reduce).
 """
 from .LM_Net import LM_Net  # noqa: F401

@@ -207,6 +207,26 @@ class OptimParam(C.Structure):
                 ("flags", C.c_int32), ("n_groups", C.c_int32), ("_pad", C.c_int32 * 7)]
 
 
+class TileParam(C.Structure):
+    """Mirror of lmn_tile_param_t (include/tiles/lmnet_tiles.h): the geometry shared by lmn_tile_gather / lmn_tile_blend."""
+    _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("tile_h", C.c_int32),
+                ("tile_w", C.c_int32), ("stride_h", C.c_int32), ("stride_w", C.c_int32), ("pad", C.c_int32), ("n_flip", C.c_int32),
+                ("flip", C.c_int32 * 4), ("average", C.c_int32), ("_pad", C.c_int32 * 9)]
+
+
+# LMN_TILE_* of include/tiles/lmnet_tiles.h
+TILE_MIN, TILE_MAX, TILE_MAX_LEN, TILE_MAX_CLASSES, TILE_MAX_FLIPS, TILE_PARAM_BYTES = 32, 1024, 8192, 64, 4, 96
+TILE_PADS = {"zero": 0, "reflect": 1}
+TILE_FLIPS = {"h": 1, "v": 2, "hv": 3}
+TILE_AVERAGES = {"logits": 0, "softmax": 1, "sigmoid": 2}
+
+
+def tile_axis(L, t, s):
+    """One axis of the tile geometry (include/tiles/lmnet_tiles.h) -> (virtual length, padding before, tiles)."""
+    V = max(int(L), int(t))
+    return V, (V - int(L)) // 2, -(-(V - int(t)) // max(int(s), 1)) + 1      # (a stride below 1 is the library's to reject)
+
+
 # LMN_OPTIM_* of include/optim/lmnet_optim.h
 OPTIM_MAX_GROUPS, OPTIM_GRID_CAP, OPTIM_PARAM_BYTES = 16, 1024, 64
 OPTIM_SKIP_NONFINITE, OPTIM_NORM = 1, 2
@@ -266,6 +286,10 @@ STRUCTS = [(ConvArgs, "lmn_sizeof_conv_args"), (SrcT, "lmn_sizeof_src"), (WgradA
 # ties the entries that write device memory to tests/test_guard_optim_gpu.py.
 SYMBOLS_OPTIM = ["lmn_sizeof_optim_param", "lmn_optim_workspace", "lmn_optim_prepare", "lmn_adamw_step_ex"]
 
+# include/tiles/lmnet_tiles.h: tiled and flip-averaged inference (lm_net_amd.infer.TiledPredictor).  A list of its own for the same
+# reason; tests/test_tiles_cpu.py checks it against the header and ties the two entries to tests/test_guard_tiles_gpu.py.
+SYMBOLS_TILES = ["lmn_sizeof_tile_param", "lmn_tile_gather", "lmn_tile_blend"]
+
 _lib = None
 
 
@@ -279,7 +303,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -295,7 +319,7 @@ def load():
     lib.lmn_prof_end.restype = C.c_int64
     if lib.lmn_abi_version() != ABI_VERSION:
         raise RuntimeError("lm_net_amd: ABI version mismatch")
-    for struct, sizeof in STRUCTS + [(OptimParam, "lmn_sizeof_optim_param")]:
+    for struct, sizeof in STRUCTS + [(OptimParam, "lmn_sizeof_optim_param"), (TileParam, "lmn_sizeof_tile_param")]:
         n = getattr(lib, sizeof)()
         if n != C.sizeof(struct):
             raise RuntimeError("lm_net_amd: layout of %s differs between hip.py (%d bytes) and the library (%s() = %d)"
@@ -1480,6 +1504,55 @@ def adamw_step_ex(p, g, m, v, ema, qgroup, param, ws):
         raise ValueError("lm_net_amd.adamw_step_ex: the flat buffers differ in size")
     _check(load().lmn_adamw_step_ex(_p(p), _p(g), _p(m), _p(v), _p(ema), _i64(n), _raw(qgroup, torch.uint8, "adamw_step_ex"),
                                     C.byref(param), _p(ws), _stream()), "adamw_step_ex")
+
+
+def tile_param(batch, channels, height, width, tile, stride, pad="reflect", flips=(), average="logits"):
+    """A TileParam (lmn_tile_param_t) from Python values.  tile / stride: (h, w) in pixels; flips: a subset of ("h", "v", "hv") in the
+    order of the entries after the identity; channels: of the source for tile_gather, of the tile outputs for tile_blend."""
+    for name, value, table in (("pad", pad, TILE_PADS), ("average", average, TILE_AVERAGES)):
+        if value not in table:
+            raise ValueError("lm_net_amd.tile_param: %s=%r, expected one of %s" % (name, value, sorted(table)))
+    flips = tuple(flips)
+    if any(f not in TILE_FLIPS for f in flips) or len(set(flips)) != len(flips):
+        raise ValueError("lm_net_amd.tile_param: flips=%r, expected distinct members of ('h', 'v', 'hv')" % (flips,))
+    p = TileParam()
+    p.batch, p.channels, p.height, p.width = int(batch), int(channels), int(height), int(width)
+    p.tile_h, p.tile_w, p.stride_h, p.stride_w = int(tile[0]), int(tile[1]), int(stride[0]), int(stride[1])
+    p.pad, p.average, p.n_flip = TILE_PADS[pad], TILE_AVERAGES[average], 1 + len(flips)
+    for k, f in enumerate(flips):
+        p.flip[1 + k] = TILE_FLIPS[f]
+    return p
+
+
+def tile_entries(param):
+    """Entries (tiles x mirrored copies) of ONE image of the geometry: n_y * n_x * n_flip."""
+    return (tile_axis(param.height, param.tile_h, param.stride_h)[2] * tile_axis(param.width, param.tile_w, param.stride_w)[2]
+            * param.n_flip)
+
+
+def tile_gather(src, param, first, count, tiles):
+    """tiles[count, channels, tile_h, tile_w] = the entries first .. first + count - 1 of src [batch, channels, H, W]: padded, cut and
+    mirrored, a bit-exact copy (lmn_tile_gather)."""
+    if (src.numel() != param.batch * param.channels * param.height * param.width
+            or tiles.numel() != int(count) * param.channels * param.tile_h * param.tile_w):
+        raise ValueError("lm_net_amd.tile_gather: tensor sizes do not match %d x %d x %dx%d -> %d tiles of %dx%d"
+                         % (param.batch, param.channels, param.height, param.width, count, param.tile_h, param.tile_w))
+    _check(load().lmn_tile_gather(_raw(src, torch.float32, "tile_gather"), C.byref(param), _i64(first), _i64(count),
+                                  _raw(tiles, torch.float32, "tile_gather"), _stream()), "tile_gather")
+
+
+def tile_blend(z, param, wy, wx, out, labels=None):
+    """out[batch, C, H, W] = the windowed, flip-averaged blend of the tile outputs z [batch * entries, C, tile_h, tile_w] in a fixed
+    order (lmn_tile_blend); wy / wx: the fp32 window tables; labels: uint8 [batch, H, W] for the arg-max, or None."""
+    n = param.batch * tile_entries(param)
+    if (z.numel() != n * param.channels * param.tile_h * param.tile_w or wy.numel() != param.tile_h or wx.numel() != param.tile_w
+            or out.numel() != param.batch * param.channels * param.height * param.width
+            or (labels is not None and labels.numel() != param.batch * param.height * param.width)):
+        raise ValueError("lm_net_amd.tile_blend: tensor sizes do not match %d entries of %d x %dx%d -> %d x %d x %dx%d"
+                         % (n, param.channels, param.tile_h, param.tile_w, param.batch, param.channels, param.height, param.width))
+    f32 = torch.float32
+    _check(load().lmn_tile_blend(_raw(z, f32, "tile_blend"), C.byref(param), _raw(wy, f32, "tile_blend"), _raw(wx, f32, "tile_blend"),
+                                 _raw(out, f32, "tile_blend"), _raw(labels, torch.uint8, "tile_blend"), _stream()), "tile_blend")
 
 
 def reparam_fold(hstats, mean, rstd, A, count, batch_stats, w_expand, b_expand, w_shortcut, rows, cred, wpack, kbias, coef, dgamma,
