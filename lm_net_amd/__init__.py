@@ -5,7 +5,8 @@
 Around the path (SURVEY.md section 8f "next" rows): ``lm_net_amd.loss.SegLoss`` (fused CE + Dice, void labels, focal term;
 ``FocalLoss``), ``lm_net_amd.metrics.ImageStatsMeter`` (per-image tp / fp / fn / tn and the metric set built on them),
 ``lm_net_amd.loss.SigmoidSegLoss`` and ``lm_net_amd.metrics.SigmoidStatsMeter`` (BCE + Dice + focal and the thresholded statistics of
-one-logit and multi-label sigmoid heads),
+one-logit and multi-label sigmoid heads), ``lm_net_amd.metrics.CurveMeter`` (ROC, precision-recall, AUROC, average precision and the
+best threshold of any thresholded metric from on-device score histograms),
 ``lm_net_amd.optim.FusedAdamW`` (one-launch AdamW; parameter groups, gradient clipping, the GradScaler skip and an EMA of the weights
 without a host decision; ``lm_net_amd.optim.decay_groups``), ``lm_net_amd.metrics.ConfusionMeter`` (on-device Dice / IoU),
 ``lm_net_amd.metrics.SurfaceDistanceMeter`` (on-device HD / HD95 / ASSD / RVD),
@@ -15,6 +16,6 @@ without a host decision; ``lm_net_amd.optim.decay_groups``), ``lm_net_amd.metric
 """
 from .LM_Net import LM_Net  # noqa: F401
 from .loss import FocalLoss, SegLoss, SigmoidSegLoss  # noqa: F401
-from .metrics import ImageStatsMeter, SigmoidStatsMeter  # noqa: F401
+from .metrics import CurveMeter, ImageStatsMeter, SigmoidStatsMeter  # noqa: F401
 
-__all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter"]
+__all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter"]

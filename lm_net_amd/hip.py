@@ -227,6 +227,13 @@ def tile_axis(L, t, s):
     return V, (V - int(L)) // 2, -(-(V - int(t)) // max(int(s), 1)) + 1      # (a stride below 1 is the library's to reject)
 
 
+# LMN_CURVE_* of include/curves/lmnet_curves.h
+CURVE_MAX_EDGES, CURVE_MAX_CLASSES = 1024, 64
+CURVE_RAW, CURVE_SOFTMAX = 0, 1
+CURVE_PLANES, CURVE_LABELS = 0, 1
+CURVE_T_U8, CURVE_T_I64 = 0, 1
+
+
 # LMN_OPTIM_* of include/optim/lmnet_optim.h
 OPTIM_MAX_GROUPS, OPTIM_GRID_CAP, OPTIM_PARAM_BYTES = 16, 1024, 64
 OPTIM_SKIP_NONFINITE, OPTIM_NORM = 1, 2
@@ -290,6 +297,11 @@ SYMBOLS_OPTIM = ["lmn_sizeof_optim_param", "lmn_optim_workspace", "lmn_optim_pre
 # reason; tests/test_tiles_cpu.py checks it against the header and ties the two entries to tests/test_guard_tiles_gpu.py.
 SYMBOLS_TILES = ["lmn_sizeof_tile_param", "lmn_tile_gather", "lmn_tile_blend"]
 
+# include/curves/lmnet_curves.h: score histograms over a threshold table (lm_net_amd.metrics.CurveMeter).  A list of its own for the
+# same reason, and no struct; tests/test_curves_cpu.py checks it against the header and ties lmn_curve_hist to
+# tests/test_guard_curves_gpu.py.
+SYMBOLS_CURVES = ["lmn_curve_workspace", "lmn_curve_hist"]
+
 _lib = None
 
 
@@ -303,7 +315,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -313,6 +325,7 @@ def load():
     lib.lmn_post_workspace.restype = C.c_int64
     lib.lmn_oneof_workspace.restype = C.c_int64
     lib.lmn_optim_workspace.restype = C.c_int64
+    lib.lmn_curve_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1158,12 +1171,18 @@ def sig_target_kind(target):
     raise ValueError("lm_net_amd: sigmoid targets are uint8 or int64, got %s" % target.dtype)
 
 
+def _logit_f32(thr):
+    """log(thr / (1 - thr)) of thr in [0, 1], in float64, rounded once to fp32: -inf at 0, exactly 0 at 0.5, +inf at 1."""
+    with np.errstate(divide="ignore"):
+        return float(np.float32(np.log(np.float64(thr) / (1.0 - np.float64(thr)))))
+
+
 def sig_logit_threshold(threshold):
     """log(thr / (1 - thr)) in float64, rounded to fp32: the logit at which sigmoid crosses thr (exactly 0 at 0.5)."""
     thr = float(threshold)
     if not 0.0 < thr < 1.0:
         raise ValueError("lm_net_amd: threshold = %g outside (0, 1)" % thr)
-    return float(np.float32(np.log(np.float64(thr) / (1.0 - np.float64(thr)))))
+    return _logit_f32(thr)
 
 
 def _sig_dims(logits, target, what):
@@ -1218,6 +1237,67 @@ def sigmoid_stats(logits, target, logit_threshold, stats=None, labels_out=None):
     _check(load().lmn_sigmoid_stats(_p(logits), None if target is None else C.c_void_p(target.data_ptr()), kind, _f(logit_threshold),
                                     B, Cn, _i64(hw), _raw(stats, torch.int64, "sigmoid_stats"),
                                     _raw(labels_out, torch.uint8, "sigmoid_stats"), _stream()), "sigmoid_stats")
+
+
+def curve_thresholds(thresholds):
+    """The thresholds of a curve as a float64 array.  An integer N in [2, 1024]: t_k = k / (N - 1), k = 0 .. N - 1 (torchmetrics'
+    binned thresholds); a sequence: 1 .. 1024 non-decreasing values inside [0, 1].  Anything else raises ValueError."""
+    if isinstance(thresholds, (int, np.integer)) and not isinstance(thresholds, bool):
+        n = int(thresholds)
+        if not 2 <= n <= CURVE_MAX_EDGES:
+            raise ValueError("lm_net_amd.curve_edges: %d thresholds, expected 2 .. %d" % (n, CURVE_MAX_EDGES))
+        return np.arange(n, dtype=np.float64) / np.float64(n - 1)
+    try:
+        t = np.array([float(v) for v in thresholds], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("lm_net_amd.curve_edges: thresholds must be an integer or a sequence of numbers, got %r" % (thresholds,))
+    if not 1 <= t.size <= CURVE_MAX_EDGES:
+        raise ValueError("lm_net_amd.curve_edges: %d thresholds, expected 1 .. %d" % (t.size, CURVE_MAX_EDGES))
+    if not bool(np.all((t >= 0.0) & (t <= 1.0))) or bool(np.any(np.diff(t) < 0)):       # (a NaN fails the first test)
+        raise ValueError("lm_net_amd.curve_edges: thresholds must be non-decreasing values inside [0, 1]")
+    return t
+
+
+def curve_edges(thresholds, kind):
+    """The fp32 edge table of lmn_curve_hist (numpy) from thresholds (curve_thresholds).  kind "logit": each threshold through the
+    arithmetic of sig_logit_threshold (0 -> -inf, 1 -> +inf), for logits scored as they are; kind "probability": np.float32(t)."""
+    if kind not in ("logit", "probability"):
+        raise ValueError("lm_net_amd.curve_edges: kind=%r, expected 'logit' or 'probability'" % (kind,))
+    t = curve_thresholds(thresholds)
+    if kind == "probability":
+        return t.astype(np.float32)
+    return np.array([_logit_f32(v) for v in t], dtype=np.float32)
+
+
+def curve_workspace(score_kind, B, hw):
+    """Bytes of scratch lmn_curve_hist needs: 0 for CURVE_RAW, 4 * B * hw for CURVE_SOFTMAX (host arithmetic, no GPU)."""
+    n = int(load().lmn_curve_workspace(int(score_kind), int(B), _i64(hw)))
+    if n < 0:
+        raise ValueError("lm_net_amd.curve_workspace: " + load().lmn_last_error().decode())
+    return n
+
+
+def curve_hist(values, target, target_form, score_kind, edges, hist, workspace=None):
+    """hist int64 [B, C, 2, n_edges + 1], overwritten: per (image, class) plane of fp32 values [B, C, ...] the histogram of the scores of
+    the negative ([.., 0, :]) and the positive ([.., 1, :]) valid elements over the bins of the fp32 device table `edges`
+    (lmn_curve_hist; bin = number of edges <= score).  target: uint8 or int64, of the values' size (CURVE_PLANES: 1 / 0 / void) or a
+    label map [B, ...] (CURVE_LABELS); score_kind CURVE_SOFTMAX needs a uint8 workspace of curve_workspace(...) bytes."""
+    B, Cn, hw = _sig_dims(values, None, "curve_hist")
+    if target_form not in (CURVE_PLANES, CURVE_LABELS) or score_kind not in (CURVE_RAW, CURVE_SOFTMAX):
+        raise ValueError("lm_net_amd.curve_hist: unknown target_form %r or score_kind %r" % (target_form, score_kind))
+    n = edges.numel()
+    if not 1 <= n <= CURVE_MAX_EDGES or hist.numel() != B * Cn * 2 * (n + 1):
+        raise ValueError("lm_net_amd.curve_hist: %d edges (1 .. %d) need hist [%d, %d, 2, %d] int64, got %s"
+                         % (n, CURVE_MAX_EDGES, B, Cn, n + 1, tuple(hist.shape)))
+    if not target.is_cuda or not target.is_contiguous() or target.numel() != (values.numel() if target_form == CURVE_PLANES else B * hw):
+        raise ValueError("lm_net_amd.curve_hist: target %s does not match values %s (contiguous device tensor, %s)"
+                         % (tuple(target.shape), tuple(values.shape), "planes" if target_form == CURVE_PLANES else "a label map"))
+    need = 4 * B * hw if score_kind == CURVE_SOFTMAX else 0
+    if need and (workspace is None or workspace.numel() < need):
+        raise ValueError("lm_net_amd.curve_hist: the softmax form needs a workspace of %d bytes" % need)
+    _check(load().lmn_curve_hist(_p(values), C.c_void_p(target.data_ptr()), sig_target_kind(target), int(target_form), int(score_kind),
+                                 _raw(edges, torch.float32, "curve_hist"), n, B, Cn, _i64(hw), _raw(workspace, torch.uint8, "curve_hist"),
+                                 _raw(hist, torch.int64, "curve_hist"), _stream()), "curve_hist")
 
 
 def surface_workspace(B, nk, H, W):

@@ -16,6 +16,11 @@ them into the metrics in float64 on the host.
 "multiclass", with ``ignore_index``) and scores them with the metric set and the reductions of that file (``:237-358``), among them
 the ``*-imagewise`` ones; ``per_image`` gives the per-case scores behind a "mean +/- std over cases" column, which a pooled
 confusion matrix cannot.
+
+``CurveMeter`` sweeps the threshold the other meters fix: per (image, class) histograms of the scores of positives and negatives over
+a threshold table (``lmn_curve_hist``, integer counting on the device), from which ROC, precision-recall, AUROC (the ``AUROC`` of the
+reference's torchmetrics collection, ``train.py:29``), average precision and the best threshold of any thresholded metric follow in
+float64 on the host.
 """
 import warnings
 
@@ -296,6 +301,153 @@ class SigmoidStatsMeter(_RawStatsMeter):
         out = torch.empty(logits.shape, device=logits.device, dtype=torch.uint8)
         hip.sigmoid_stats(logits, None, self.logit_threshold, None, out)
         return out
+
+
+def curve_counts(hist):
+    """tp, fp, fn, tn (int64 numpy, [..., N]) at every threshold from score histograms [..., 2, N + 1] (negatives, positives): an
+    element of bin b is predicted on at threshold k when b >= k + 1, so tp and fp are suffix sums."""
+    hist = np.asarray(hist, dtype=np.int64)
+    above = np.flip(np.cumsum(np.flip(hist, -1), -1), -1)           # above[..., b] = elements of bins >= b
+    fp, tp = above[..., 0, 1:], above[..., 1, 1:]
+    return tp, fp, above[..., 1, :1] - tp, above[..., 0, :1] - fp
+
+
+def _nan_div(a, b):
+    """a / b in float64, NaN where b == 0 (no warning)."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.where(b > 0, a / np.where(b > 0, b, 1.0), np.nan)
+
+
+def _nanmean_last(a):
+    """nanmean over the last axis; NaN (and no warning) where every entry is NaN."""
+    ok = ~np.isnan(a)
+    return _nan_div(np.where(ok, a, 0.0).sum(-1), ok.sum(-1))
+
+
+class CurveMeter:
+    """ROC and precision-recall curves, AUROC, average precision and the best threshold of any thresholded metric, per class, from
+    score histograms accumulated on the device (``lmn_curve_hist``: integer counting, exact, no synchronisation).  It stands in for
+    the ``AUROC`` of the reference's torchmetrics collection (``train.py:29``) with binned thresholds, and for one
+    ``SigmoidStatsMeter`` per threshold.
+
+    ``thresholds``: an integer N (t_k = k / (N - 1), torchmetrics' binned thresholds) or a non-decreasing sequence inside [0, 1], at
+    most 1024 either way.  An element is predicted on at threshold t_k when its score >= t_k, compared in fp32:
+      scores="sigmoid"      values are logits; compared as logit >= fp32(log(t / (1 - t))), the comparison of ``SigmoidStatsMeter``
+                            (0 -> -inf: always on unless NaN; 1 -> +inf)
+      scores="probability"  values are probabilities (``TiledPredictor(average="softmax" | "sigmoid").map``); compared as they are
+      scores="softmax"      values are logits of 2..64 classes; the score is expf(z_c - logsumexp(z)) in fp32
+    A NaN score is predicted off at every threshold.
+
+    update(values, target): values floating [B, C, H, W]; target [B, C, H, W] planes ([B, H, W] when C = 1; 1 positive, 0 negative,
+    anything else void: the contract of ``SigmoidStatsMeter``) or, for C >= 2, an integer label map [B, H, W] scored one-vs-rest (a
+    label outside [0, C) is void).  The [B, C, 2, N + 1] int64 histograms stay on the device.  All scores are float64 host arithmetic
+    on the integer counts."""
+
+    def __init__(self, n_classes, scores="sigmoid", thresholds=101, device="cuda"):
+        if scores not in ("sigmoid", "softmax", "probability"):
+            raise ValueError("CurveMeter: scores=%r, expected 'sigmoid', 'softmax' or 'probability'" % (scores,))
+        if not (2 if scores == "softmax" else 1) <= n_classes <= 64:
+            raise ValueError("CurveMeter: n_classes = %d outside [%d, 64]" % (n_classes, 2 if scores == "softmax" else 1))
+        self.n, self.scores, self.device = int(n_classes), scores, torch.device(device)
+        self.thresholds = hip.curve_thresholds(thresholds)
+        self.edges = hip.curve_edges(thresholds, "logit" if scores == "sigmoid" else "probability")
+        self.score_kind = hip.CURVE_SOFTMAX if scores == "softmax" else hip.CURVE_RAW
+        self._edges_dev, self._ws, self._hist = {}, {}, []
+
+    def reset(self):
+        self._hist = []
+
+    @torch.no_grad()
+    def update(self, values, target):
+        what = "CurveMeter"
+        labels = values.dim() == 4 and values.shape[1] >= 2 and target.dim() == 3 and not target.is_floating_point()
+        if labels:
+            values, _ = _sigmoid_inputs(values, None, self.n, what)
+            if not target.is_cuda:
+                raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % what)
+            if target.shape[0] != values.shape[0] or target.shape[-2:] != values.shape[-2:]:
+                raise ValueError("%s: label map %s does not match values %s" % (what, tuple(target.shape), tuple(values.shape)))
+            target = (target if target.dtype in (torch.uint8, torch.int64) else target.long()).contiguous()
+        else:
+            values, target = _sigmoid_inputs(values, target, self.n, what)
+            if target is None:
+                raise ValueError("%s: a target is required" % what)
+        B, Cn, H, W = values.shape
+        dev = values.device
+        if dev not in self._edges_dev:
+            self._edges_dev[dev] = torch.from_numpy(self.edges).to(dev)
+        ws = None
+        if self.score_kind == hip.CURVE_SOFTMAX:
+            key = (dev, B, H * W)
+            if key not in self._ws:                              # (one scratch per shape: a later launch on the stream reuses it)
+                self._ws[key] = torch.empty(hip.curve_workspace(self.score_kind, B, H * W), device=dev, dtype=torch.uint8)
+            ws = self._ws[key]
+        hist = torch.empty(B, Cn, 2, self.edges.size + 1, device=dev, dtype=torch.int64)
+        hip.curve_hist(values, target, hip.CURVE_LABELS if labels else hip.CURVE_PLANES, self.score_kind, self._edges_dev[dev], hist, ws)
+        self._hist.append(hist)
+
+    def add_raw(self, hist):
+        """Append raw histograms [N_images, C, 2, N + 1] int64, e.g. another rank's raw()."""
+        if hist.dim() != 4 or tuple(hist.shape[1:]) != (self.n, 2, self.edges.size + 1):
+            raise ValueError("CurveMeter.add_raw: shape %s" % (tuple(hist.shape),))
+        self._hist.append(hist.to(self.device, torch.int64))
+
+    def raw(self):
+        """The histograms so far, in update order: int64 [N_images, C, 2, N + 1] on the device."""
+        if not self._hist:
+            return torch.zeros(0, self.n, 2, self.edges.size + 1, device=self.device, dtype=torch.int64)
+        return torch.cat(self._hist)
+
+    def counts(self, per_image=False):
+        """tp, fp, fn, tn at every threshold: int64 numpy [C, N] pooled over the images, or [N_images, C, N] (synchronises)."""
+        h = self.raw().cpu().numpy()
+        return curve_counts(h if per_image else h.sum(0))
+
+    def roc(self):
+        """fpr, tpr ([C, N] float64, NaN for a class without negatives / positives) and the thresholds [N]."""
+        tp, fp, fn, tn = self.counts()
+        return _nan_div(fp, fp + tn), _nan_div(tp, tp + fn), self.thresholds.copy()
+
+    def pr(self):
+        """precision (1 where nothing is predicted on), recall ([C, N] float64, NaN for a class without positives), thresholds [N]."""
+        tp, fp, fn, tn = self.counts()
+        return np.where(tp + fp > 0, _nan_div(tp, tp + fp), 1.0), _nan_div(tp, tp + fn), self.thresholds.copy()
+
+    @staticmethod
+    def _average(v, average):
+        if average not in ("none", "macro"):
+            raise ValueError("CurveMeter: average=%r, expected 'none' or 'macro'" % (average,))
+        return v if average == "none" else _nanmean_last(v)
+
+    def auroc(self, average="none", per_image=False):
+        """The area under the binned ROC by the trapezoid rule, the end points (0, 0) and (1, 1) always added: float64 [C] (or
+        [N_images, C]); NaN without a positive or without a negative; "macro": the nanmean over the classes."""
+        tp, fp, fn, tn = self.counts(per_image)
+        fpr, tpr = _nan_div(fp, fp + tn), _nan_div(tp, tp + fn)
+        one, zero = np.ones(fpr.shape[:-1] + (1,)), np.zeros(fpr.shape[:-1] + (1,))
+        x, y = np.concatenate([one, fpr, zero], -1), np.concatenate([one, tpr, zero], -1)       # (thresholds ascend: x descends)
+        return self._average(((x[..., :-1] - x[..., 1:]) * (y[..., :-1] + y[..., 1:]) / 2).sum(-1), average)
+
+    def average_precision(self, average="none", per_image=False):
+        """sum_k (R_k - R_{k+1}) P_k with R_N = 0 (torchmetrics' binned average precision): float64 [C] (or [N_images, C]); NaN
+        without a positive."""
+        tp, fp, fn, tn = self.counts(per_image)
+        prec, rec = np.where(tp + fp > 0, _nan_div(tp, tp + fp), 1.0), _nan_div(tp, tp + fn)
+        nxt = np.concatenate([rec[..., 1:], np.zeros(rec.shape[:-1] + (1,))], -1)
+        return self._average(((rec - nxt) * prec).sum(-1), average)
+
+    def score(self, metric, zero_division=1.0, beta=1.0):
+        """Any entry of STATS_METRICS at every threshold, from the pooled counts: float64 [C, N] (0/0 -> zero_division)."""
+        tp, fp, fn, tn = (a.astype(np.float64) for a in self.counts())
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _zero_div(_metric_fn(metric, beta)(tp, fp, fn, tn), zero_division)
+
+    def best_threshold(self, metric="f1", zero_division=1.0, beta=1.0):
+        """Per class, the threshold of the highest score (the lowest such threshold on a tie) and that score: two float64 [C] arrays.
+        The first is the number to hand to ``SigmoidStatsMeter(threshold=...)``."""
+        s = self.score(metric, zero_division, beta)
+        k = np.argmax(s, -1)                                     # (the first maximum)
+        return self.thresholds[k], s[np.arange(s.shape[0]), k]
 
 
 class SurfaceDistanceMeter:
