@@ -235,7 +235,7 @@ float* lmn_det_slots(hipStream_t st, size_t floats) {
 
 void lmn_det_sum(hipStream_t st, const float* slots, int nslots, int64_t size, float* dst) {
   if (size <= 0 || nslots <= 0) return;
-  hipLaunchKernelGGL(det_sum_kernel, dim3((unsigned)((size + 7) / 8)), dim3(256), 0, st, slots, nslots, size, dst);
+  LMN_LAUNCH(det_sum_kernel, dim3((unsigned)((size + 7) / 8)), dim3(256), 0, st, slots, nslots, size, dst);
 }
 
 static struct { hipStream_t st; int level; } g_prio[8];   // (common.h (4); level 0 = free entry)

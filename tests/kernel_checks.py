@@ -3,12 +3,17 @@
 (name, rel_err, tol) rows; ``tests/test_kernels_gpu.py`` asserts them, ``tools/gpu_kernel_check.py``
 prints them all in one GPU run.  Tolerance for fp32 device arithmetic vs fp64: 1e-4 relative
 (north_star), atomically-reduced sums 2e-4.
+
+Which kernel instance a case runs is decided by host predicates, so every check is wrapped by kernel_forms.owner_check (its last
+row: the instances it owns in kernel_forms.OWNED were launched) and the dispatch claims of the comments ("M-split kernel", "halo
+instance", "two-stage reduction", LDS-DMA switch on / off) are rows of their own (kernel_forms.form_row around the call concerned).
 """
 import math
 
 import torch
 import torch.nn.functional as F
 
+from kernel_forms import form_row, launched, owner_check
 from lm_net_amd import hip
 from oracle import natten_ref
 
@@ -68,29 +73,36 @@ def gelu(x):
 
 
 # ------------------------------------------------------------------------------------------------ conv forward
+@owner_check
 def check_conv_fwd():
     rows = []
+    # the kernel each case must select (start of the instance name).  N = conv_tile_kernel<taps, cout tiles per block, ...>: the N-split
+    # kernel, up to 5 cout tiles (80 channels; 4-5 tiles run as two chunks of a 3-tile block); M = conv_tileM_kernel<taps, ...>: the
+    # M-split kernel, from 6 cout tiles (Cout > 80); D = the LDS-DMA form of the M-split 3x3 stride-1 calls (fp32 operands only:
+    # check_conv_bf16 re-runs these cases with bf16 operands, where they take conv_tileM_kernel)
+    N, M, D = "conv_tile_kernel<%d, %d,", "conv_tileM_kernel<%d,", "conv_dmaM_kernel<"
+    f32 = hip._MMA[0] == hip.F32
     cases = [
-        # name, B, H, W, [Cin...], Cout, k, s
-        ("1x1 12->24", 2, 9, 13, [12], 24, 1, 1),
-        ("1x1 4->24 (padded rgb)", 1, 8, 8, [4], 24, 1, 1),
-        ("1x1 96->192", 1, 7, 6, [96], 192, 1, 1),
-        ("1x1 372->1116", 1, 5, 5, [372], 1116, 1, 1),
-        ("1x1 two-src 24+12->12", 2, 6, 7, [24, 12], 12, 1, 1),
-        ("3x3 s1 12->12", 2, 10, 11, [12], 12, 3, 1),
-        ("3x3 s1 48->24", 1, 9, 9, [48], 24, 3, 1),
-        ("3x3 s2 12->24", 2, 12, 10, [12], 24, 3, 2),
-        ("3x3 s2 96->192", 1, 8, 8, [96], 192, 3, 2),
-        ("3x3 s1 cat 24+24+24->24", 1, 8, 9, [24, 24, 24], 24, 3, 1),
-        ("3x3 s1 100->112 (chunks)", 1, 6, 6, [100], 112, 3, 1),
-        ("3x3 s1 372->372", 1, 6, 6, [372], 372, 3, 1),
-        ("1x1 64->64 on 2x3 map", 1, 2, 3, [64], 64, 1, 1),
-        ("1x1 32->72 on 1x1 map", 2, 1, 1, [32], 72, 1, 1),
-        ("3x3 s1 64->80 on 2x3 map", 1, 2, 3, [64], 80, 3, 1),
-        ("3x3 s1 48->144 22x22", 2, 22, 22, [48], 144, 3, 1),
-        ("1x1 96->288 44x44", 1, 44, 44, [96], 288, 1, 1),
+        # name, B, H, W, [Cin...], Cout, k, s, kernel
+        ("1x1 12->24", 2, 9, 13, [12], 24, 1, 1, N % (1, 2)),
+        ("1x1 4->24 (padded rgb)", 1, 8, 8, [4], 24, 1, 1, N % (1, 2)),
+        ("1x1 96->192", 1, 7, 6, [96], 192, 1, 1, M % 1),
+        ("1x1 372->1116", 1, 5, 5, [372], 1116, 1, 1, M % 1),
+        ("1x1 two-src 24+12->12", 2, 6, 7, [24, 12], 12, 1, 1, N % (1, 1)),
+        ("3x3 s1 12->12", 2, 10, 11, [12], 12, 3, 1, N % (9, 1)),
+        ("3x3 s1 48->24", 1, 9, 9, [48], 24, 3, 1, N % (9, 2)),
+        ("3x3 s2 12->24", 2, 12, 10, [12], 24, 3, 2, N % (9, 2)),
+        ("3x3 s2 96->192", 1, 8, 8, [96], 192, 3, 2, M % 9),
+        ("3x3 s1 cat 24+24+24->24", 1, 8, 9, [24, 24, 24], 24, 3, 1, N % (9, 2)),
+        ("3x3 s1 100->112 (M-split, 7 cout tiles)", 1, 6, 6, [100], 112, 3, 1, D if f32 else M % 9),
+        ("3x3 s1 372->372", 1, 6, 6, [372], 372, 3, 1, D if f32 else M % 9),
+        ("1x1 64->64 on 2x3 map", 1, 2, 3, [64], 64, 1, 1, N % (1, 3)),
+        ("1x1 32->72 on 1x1 map", 2, 1, 1, [32], 72, 1, 1, N % (1, 3)),
+        ("3x3 s1 64->80 on 2x3 map (chunks: 5 cout tiles, 3 per block)", 1, 2, 3, [64], 80, 3, 1, N % (9, 3)),
+        ("3x3 s1 48->144 22x22", 2, 22, 22, [48], 144, 3, 1, D if f32 else M % 9),
+        ("1x1 96->288 44x44", 1, 44, 44, [96], 288, 1, 1, M % 1),
     ]
-    for name, B, H, W, cins, cout, k, s in cases:
+    for name, B, H, W, cins, cout, k, s, kern in cases:
         cin = sum(cins)
         x = R(B, cin, H, W, seed=1)
         w = R(cout, cin, k, k, seed=2, scale=1.0 / math.sqrt(cin * k * k))
@@ -103,8 +115,9 @@ def check_conv_fwd():
             off += c
         wp = hip.conv_pack(dev(w), k, cins)
         out = torch.full((B, Ho, Wo, cout), float("nan"), device=DEV)
-        hip.conv_fwd(xs, wp, out, B=B, Hin=H, Win=W, Hout=Ho, Wout=Wo, Cout=cout, ksize=k, stride=s, bias=dev(b))
+        _, names = launched(lambda: hip.conv_fwd(xs, wp, out, B=B, Hin=H, Win=W, Hout=Ho, Wout=Wo, Cout=cout, ksize=k, stride=s, bias=dev(b)))
         rows.append(("conv_fwd " + name, rel(nchw(out), ref), TOL))
+        rows.append(form_row("conv_fwd " + name, names, [kern], [p for p in ("conv_tile_kernel<", "conv_tileM_kernel<", D) if not kern.startswith(p)]))
 
     # sources that are slices of a wider buffer; output into a slice; residual; affine+hardswish; stats
     B, H, W = 2, 7, 9
@@ -152,16 +165,46 @@ def check_conv_fwd():
     hip.conv_fwd([dict(view=nhwc(pre), scale=dev(sc), flags=hip.SRC_GELU), nhwc(xin)], wp, out, B=B, Hin=H, Win=W,
                  Hout=H, Wout=W, Cout=12, bias=dev(b), bias2=dev(b2))
     rows.append(("conv_fwd two biases (pointwise + shortcut)", rel(nchw(out), ref + b2.view(1, -1, 1, 1)), TOL))
+    # weights re-packed by a recorded hip.PackPlan (ONE lmn_conv_pack_batch launch per pass, as the engine packs its parameters): the
+    # buffers are poisoned in between, so the convs below read what the batched kernel wrote
+    plan = hip.PackPlan()
+    hip._PLAN[0] = plan
+    try:
+        x = R(2, 36, 6, 7, seed=16)
+        w1, w3 = R(12, 36, 1, 1, seed=17, scale=0.2), R(24, 36, 3, 3, seed=18, scale=0.1)
+        p1, p3 = torch.nn.Parameter(dev(w1)), torch.nn.Parameter(dev(w3))
+        packed = [hip.conv_pack(p1, 1, [24, 12]), hip.conv_pack(p3, 3, [36]), hip.conv_pack_t(p3, 3)]
+        for t in packed:
+            t.view(torch.uint8).fill_(0xFF)
+        _, names = launched(plan.refresh)
+        rows.append(form_row("PackPlan.refresh: one batched pack launch", names, ["conv_pack_batch_kernel"], ["conv_pack_kernel"]))
+        wp1, wp3, wp3t = hip.conv_pack(p1, 1, [24, 12]), hip.conv_pack(p3, 3, [36]), hip.conv_pack_t(p3, 3)
+        o1, o3 = torch.full((2, 6, 7, 12), float("nan"), device=DEV), torch.full((2, 6, 7, 24), float("nan"), device=DEV)
+        hip.conv_fwd([nhwc(x[:, :24]), nhwc(x[:, 24:])], wp1, o1, B=2, Hin=6, Win=7, Hout=6, Wout=7, Cout=12)
+        hip.conv_fwd([nhwc(x)], wp3, o3, B=2, Hin=6, Win=7, Hout=6, Wout=7, Cout=24, ksize=3)
+        rows.append(("conv_fwd on batch-packed weights (1x1 two-source, 3x3)", max(rel(nchw(o1), F.conv2d(x, w1)), rel(nchw(o3), F.conv2d(x, w3, padding=1))), TOL))
+        dy = R(2, 24, 6, 7, seed=19)
+        dx = torch.full((2, 6, 7, 36), float("nan"), device=DEV)
+        hip.conv_fwd([nhwc(dy)], wp3t, dx, B=2, Hin=6, Win=7, Hout=6, Wout=7, Cout=36, ksize=3, transposed=1)
+        rows.append(("conv_bwd_data on batch-packed transposed weights", rel(nchw(dx), torch.nn.grad.conv2d_input((2, 36, 6, 7), w3, dy, padding=1)), TOL))
+    finally:
+        hip._PLAN[0] = None
     return rows
 
 
+@owner_check
 def check_conv_bwd_data():
     rows = []
-    cases = [("1x1 24->12", 2, 7, 6, 24, 12, 1, 1), ("3x3 s1 24->36", 2, 8, 9, 24, 36, 3, 1),
-             ("3x3 s2 12->24", 2, 12, 10, 12, 24, 3, 2), ("3x3 s2 48->96 odd", 1, 9, 7, 48, 96, 3, 2),
-             ("3x3 s1 96->96", 1, 6, 6, 96, 96, 3, 1), ("3x3 s2 12->24 multi-tile", 2, 64, 80, 12, 24, 3, 2),
-             ("3x3 s2 96->192 two cout chunks", 2, 22, 38, 96, 192, 3, 2), ("3x3 s2 24->48 odd wide", 1, 35, 71, 24, 48, 3, 2)]
-    for name, B, H, W, cin, cout, k, s in cases:
+    # last column: the kernel the call must select.  S2T = the stride-2 transposed (four-class) instances of the N-split kernel,
+    # conv_tile_kernel<9, cout tiles per block, 0, true, ...>; they also take the 96-channel gradient (six cout tiles: two chunks of a
+    # 3-tile block), which the M-split kernel does not implement
+    N, S2T = "conv_tile_kernel<%d, %d, 0, false,", "conv_tile_kernel<9, %d, 0, true,"
+    wide = "conv_dmaM_kernel<" if hip._MMA[0] == hip.F32 else "conv_tileM_kernel<9,"     # (the LDS-DMA form takes fp32 operands only)
+    cases = [("1x1 24->12", 2, 7, 6, 24, 12, 1, 1, N % (1, 2)), ("3x3 s1 24->36", 2, 8, 9, 24, 36, 3, 1, N % (9, 2)),
+             ("3x3 s2 12->24", 2, 12, 10, 12, 24, 3, 2, S2T % 1), ("3x3 s2 48->96 odd", 1, 9, 7, 48, 96, 3, 2, S2T % 3),
+             ("3x3 s1 96->96", 1, 6, 6, 96, 96, 3, 1, wide), ("3x3 s2 12->24 multi-tile", 2, 64, 80, 12, 24, 3, 2, S2T % 1),
+             ("3x3 s2 96->192 two cout chunks", 2, 22, 38, 96, 192, 3, 2, S2T % 3), ("3x3 s2 24->48 odd wide", 1, 35, 71, 24, 48, 3, 2, S2T % 2)]
+    for name, B, H, W, cin, cout, k, s, kern in cases:
         x = R(B, cin, H, W, seed=21).requires_grad_(True)
         w = R(cout, cin, k, k, seed=22, scale=0.1)
         y = F.conv2d(x, w, None, stride=s, padding=k // 2)
@@ -170,8 +213,9 @@ def check_conv_bwd_data():
         Ho, Wo = y.shape[2:]
         wpt = hip.conv_pack_t(dev(w), k)
         dx = torch.full((B, H, W, cin), float("nan"), device=DEV)
-        hip.conv_fwd([nhwc(dy)], wpt, dx, B=B, Hin=Ho, Win=Wo, Hout=H, Wout=W, Cout=cin, ksize=k, stride=s, transposed=1)
+        _, names = launched(lambda: hip.conv_fwd([nhwc(dy)], wpt, dx, B=B, Hin=Ho, Win=Wo, Hout=H, Wout=W, Cout=cin, ksize=k, stride=s, transposed=1))
         rows.append(("conv_bwd_data " + name, rel(nchw(dx), x.grad), TOL))
+        rows.append(form_row("conv_bwd_data " + name, names, [kern]))
     # gradient of one source slice of a cat conv (rows [12, 36) of 48 input channels)
     B, H, W = 1, 6, 7
     x = R(B, 48, H, W, seed=24).requires_grad_(True)
@@ -186,13 +230,18 @@ def check_conv_bwd_data():
     return rows
 
 
+@owner_check
 def check_conv_wgrad():
     rows = []
-    cases = [("1x1 12->24", 2, 9, 7, [12], 24, 1, 1), ("1x1 two-src 24+12->12", 2, 6, 7, [24, 12], 12, 1, 1),
-             ("3x3 s1 12->12", 2, 10, 11, [12], 12, 3, 1), ("3x3 s2 24->48", 2, 12, 10, [24], 48, 3, 2),
-             ("3x3 s1 cat 24+24->24", 1, 8, 9, [24, 24], 24, 3, 1), ("3x3 s1 96->96", 1, 7, 7, [96], 96, 3, 1),
-             ("1x1 372->744", 1, 6, 6, [372], 744, 1, 1)]
-    for name, B, H, W, cins, cout, k, s in cases:
+    # last column: the kernel (cout x cin tiles per block) the call must select -- the wave-staged direct 1x1 kernel or the LDS-staged
+    # 3x3 kernel of the maps narrower than 32; RED: the two-stage K-split reduction (block partials + wgrad_reduce_kernel), else atomics
+    RED = "wgrad_reduce_kernel<"
+    cases = [("1x1 12->24", 2, 9, 7, [12], 24, 1, 1, "wgrad_1x1w_kernel<2, 1,"), ("1x1 two-src 24+12->12", 2, 6, 7, [24, 12], 12, 1, 1, "wgrad_1x1w_kernel<1, 3,"),
+             ("3x3 s1 12->12", 2, 10, 11, [12], 12, 3, 1, "wgrad_lds_kernel<9, 1, 1,"), ("3x3 s2 24->48", 2, 12, 10, [24], 48, 3, 2, "wgrad_lds_kernel<9, 2, 2,"),
+             ("3x3 s1 cat 24+24->24", 1, 8, 9, [24, 24], 24, 3, 1, "wgrad_lds_kernel<9, 2, 2,"), ("3x3 s1 96->96", 1, 7, 7, [96], 96, 3, 1, "wgrad_lds_kernel<9, 2, 2,"),
+             ("1x1 372->744", 1, 6, 6, [372], 744, 1, 1, "wgrad_1x1w_kernel<2, 4,"),
+             ("1x1 12->4 (the head, padded to 4 classes)", 2, 9, 7, [12], 4, 1, 1, "wgrad_1x1w_kernel<1, 1,"), ("1x1 24->24", 2, 9, 7, [24], 24, 1, 1, "wgrad_1x1w_kernel<2, 2,")]
+    for name, B, H, W, cins, cout, k, s, kern in cases:
         cin = sum(cins)
         x = R(B, cin, H, W, seed=31)
         w = R(cout, cin, k, k, seed=32, scale=0.1).requires_grad_(True)
@@ -207,7 +256,9 @@ def check_conv_wgrad():
             off += c
         dW = torch.zeros(cout, cin, k, k, device=DEV)
         db = torch.zeros(cout, device=DEV)
-        hip.conv_wgrad(xs, nhwc(dy), dW, db, B=B, Hin=H, Win=W, Hout=Ho, Wout=Wo, Cout=cout, ksize=k, stride=s)
+        _, names = launched(lambda: hip.conv_wgrad(xs, nhwc(dy), dW, db, B=B, Hin=H, Win=W, Hout=Ho, Wout=Wo, Cout=cout, ksize=k, stride=s))
+        two = cout == 744      # (47 x 24 tile sets: the partials pass 256 K floats)
+        rows.append(form_row("conv_wgrad " + name + (": two-stage reduction" if two else ": atomics"), names, [kern] + ([RED] if two else []), [] if two else [RED]))
         rows.append(("conv_wgrad dW " + name, rel(dW, w.grad), 2e-4))
         rows.append(("conv_wgrad db " + name, rel(db, b.grad), 2e-4))
         if len(cins) > 1:  # per-source gradient tensors + second bias gradient (pointwise + shortcut in one pass)
@@ -220,20 +271,25 @@ def check_conv_wgrad():
                 rows.append(("conv_wgrad per-source dW[%d] %s" % (i, name), rel(parts[i], w.grad[:, off:off + c]), 2e-4))
                 off += c
             rows.append(("conv_wgrad db2 " + name, rel(db2, b.grad), 2e-4))
-    # large two-source 1x1 (two-stage reduction path) with per-source outputs
-    B, H, W, cins, cout = 2, 64, 48, [24, 12], 12
-    x = R(B, 36, H, W, seed=41)
-    w = R(cout, 36, 1, 1, seed=42, scale=0.1).requires_grad_(True)
-    y = F.conv2d(x, w)
-    dy = R(*y.shape, seed=43)
-    y.backward(dy)
-    parts = [torch.zeros(cout, c, 1, 1, device=DEV) for c in cins]
-    db1, db2 = torch.zeros(cout, device=DEV), torch.zeros(cout, device=DEV)
-    hip.conv_wgrad([nhwc(x[:, :24]), nhwc(x[:, 24:])], nhwc(dy), None, db1, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=cout,
-                   dW_src=parts, db2=db2)
-    rows.append(("conv_wgrad per-source large dW[0]", rel(parts[0], w.grad[:, :24]), 2e-4))
-    rows.append(("conv_wgrad per-source large dW[1]", rel(parts[1], w.grad[:, 24:]), 2e-4))
-    rows.append(("conv_wgrad per-source large db/db2", rel(db1 + db2, 2 * dy.sum((0, 2, 3))), 2e-4))
+    # large two-source 1x1 with per-source outputs: K-split over 24 blocks reduced with atomics (64 x 48), and over 50 blocks through
+    # the two-stage reduction (64 x 100: wgrad_two_stage in conv_wgrad.hip takes more than 48 blocks; one block walks 256 pixels)
+    for (B, H, W, two) in ((2, 64, 48, False), (2, 64, 100, True)):
+        cins, cout = [24, 12], 12
+        x = R(B, 36, H, W, seed=41)
+        w = R(cout, 36, 1, 1, seed=42, scale=0.1).requires_grad_(True)
+        y = F.conv2d(x, w)
+        dy = R(*y.shape, seed=43)
+        y.backward(dy)
+        parts = [torch.zeros(cout, c, 1, 1, device=DEV) for c in cins]
+        db1, db2 = torch.zeros(cout, device=DEV), torch.zeros(cout, device=DEV)
+        _, names = launched(lambda: hip.conv_wgrad([nhwc(x[:, :24]), nhwc(x[:, 24:])], nhwc(dy), None, db1, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=cout,
+                                                   dW_src=parts, db2=db2))
+        tag = " %dx%d" % (H, W)
+        rows.append(form_row("conv_wgrad per-source large" + tag + (": two-stage reduction" if two else ": atomics"), names,
+                             ["wgrad_1x1w_kernel<1, 3,"] + ([RED] if two else []), [] if two else [RED]))
+        rows.append(("conv_wgrad per-source large dW[0]" + tag, rel(parts[0], w.grad[:, :24]), 2e-4))
+        rows.append(("conv_wgrad per-source large dW[1]" + tag, rel(parts[1], w.grad[:, 24:]), 2e-4))
+        rows.append(("conv_wgrad per-source large db/db2" + tag, rel(db1 + db2, 2 * dy.sum((0, 2, 3))), 2e-4))
     # deferred K-split reductions that share a destination (a weight used by two calls): the batched reduce adds with plain
     # read-modify-writes, so hip.wgrad_reduce_flush must put such jobs into consecutive launches -- dW = sum of both calls
     B, H, W, cin, cout = 2, 64, 64, 24, 24
@@ -245,9 +301,11 @@ def check_conv_wgrad():
     (y1 * d1).sum().backward()
     (y2 * d2).sum().backward()
     dW, db = torch.zeros(cout, cin, 3, 3, device=DEV), torch.zeros(cout, device=DEV)
-    keep = [hip.conv_wgrad([nhwc(xx)], nhwc(dd), dW, db, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=cout, ksize=3, defer=True)
-            for xx, dd in ((x1, d1), (x2, d2))]
-    ntab = len(hip.wgrad_reduce_flush())
+    keep, names = launched(lambda: [hip.conv_wgrad([nhwc(xx)], nhwc(dd), dW, db, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=cout, ksize=3, defer=True)
+                                    for xx, dd in ((x1, d1), (x2, d2))])
+    rows.append(form_row("conv_wgrad deferred: the register-prefetch 3x3 kernel of the maps >= 32 wide, no reduction of its own", names, ["wgrad3_kernel<2, 2,"], [RED, "wgrad_reduce_batch"]))
+    ntab, names = launched(lambda: len(hip.wgrad_reduce_flush()))
+    rows.append(form_row("conv_wgrad deferred: the flush launches the batched reduction", names, ["wgrad_reduce_batch_kernel"]))
     torch.cuda.synchronize()
     if keep[0] is not None:   # (both calls really deferred a K-split reduction)
         rows.append(("conv_wgrad deferred, shared destination: launches", abs(ntab - 2), 0))
@@ -256,6 +314,7 @@ def check_conv_wgrad():
     return rows
 
 
+@owner_check
 def check_conv_dropout():
     """Epilogue dropout and its two backward uses regenerate the SAME mask; keep-rate ~ 1-p."""
     rows = []
@@ -293,6 +352,7 @@ def _dw_ref(x1, ws, gam, bet, train, rm=None, rv=None):
     return pre, ys
 
 
+@owner_check
 def check_dw():
     rows = []
     for (B, H, W, E) in [(2, 20, 19, 24), (1, 33, 17, 48), (2, 18, 21, 12), (1, 70, 130, 24), (1, 9, 61, 8),
@@ -375,7 +435,12 @@ def check_dw():
             rows.append(("dw_bwd_coef dbeta[%d]" % i + tag, rel(dbs[i], br[i].grad), 2e-4))
         dx1 = nanE(B, H, W, E)
         dws = [torch.zeros_like(dev(w)) for w in ws]
-        hip.dw_bwd(x1d, nhwcE(dpre_ref), dx1, *wd, cA, cC, cD, *dws)
+        dpre_d = nhwcE(dpre_ref)
+        _, names = launched(lambda: hip.dw_bwd(x1d, dpre_d, dx1, *wd, cA, cC, cD, *dws))
+        # (strips of 60 columns with the halo instance where that saves a strip over strips of 56: W in 57..60, 113..120, ...; the
+        #  number of strips and row segments is a launch parameter, not an instance)
+        halo = -(-W // 60) < -(-W // 56)
+        rows.append(form_row("dw_bwd" + tag + (": halo instance" if halo else ": 56-column strips"), names, ["dw_bwd_kernel<float, 0, %s, false, 2>" % ("true" if halo else "false")]))
         rows.append(("dw_bwd dx1" + tag, rel(nchwE(dx1), x1r.grad), TOL))
         for nm, got, ref in zip(("dW5", "dW3", "dWv", "dWh"), dws, wsr):
             rows.append(("dw_bwd " + nm + tag, rel(got, ref.grad), 2e-4))
@@ -417,12 +482,14 @@ def check_dw():
     return rows
 
 
+@owner_check
 def check_zpath():
     """z-path of ReparamConv (lmn_dw_pre_t, lmn_reparam_fold, lmn_affine2): the depthwise kernels fed z + (A, shift) must reproduce
     what they compute from x1 = Hardswish(A z + shift); the depthwise backward's drain must deliver dh and its sums; the folded
     three-source conv must equal the BatchNorm backward + both data gradients of the reference graph (fp64)."""
     rows = []
-    for (B, H, W, Cin, E, Cout) in [(2, 20, 19, 12, 24, 12), (1, 33, 17, 24, 48, 24), (2, 9, 61, 4, 8, 12), (1, 70, 130, 12, 24, 12)]:
+    for (B, H, W, Cin, E, Cout) in [(2, 20, 19, 12, 24, 12), (1, 33, 17, 24, 48, 24), (2, 9, 61, 4, 8, 12), (1, 70, 130, 12, 24, 12),
+                                    (1, 12, 57, 4, 8, 12)]:   # (57 columns: the halo instance of the depthwise backward, as on the 352 and 176 wide maps of the step)
         tag = " Cin=%d E=%d %dx%d" % (Cin, E, H, W)
         N = B * H * W
         x = R(B, Cin, H, W, seed=201)
@@ -449,8 +516,10 @@ def check_zpath():
         # ---- forward-side kernels: z + transform == x1
         st_a, st_b = torch.zeros(4, 2, E, device=DEV), torch.zeros(4, 2, E, device=DEV)
         hip.dw_stats(x1d, *wd, st_a)
-        hip.dw_stats(zd, *wd, st_b, zpre=zp)
+        _, names = launched(lambda: hip.dw_stats(zd, *wd, st_b, zpre=zp))
+        rows.append(form_row("dw_stats z-path" + tag, names, ["dw_stats0_kernel<float, true>"]))
         rows.append(("dw_stats z-path" + tag, rel(st_b, st_a), 2e-5))
+        rows.append(("dw_stats z-path vs fp64" + tag, rel(st_b, torch.stack([torch.stack([y_.sum((0, 2, 3)), (y_ * y_).sum((0, 2, 3))]) for y_ in _dw_ref(x1.detach(), ws, [ga] * 4, [bt] * 4, True)[1]])), 2e-4))
         # ... with the BatchNorm finalised inside (fin): sums of z about a shift, 3 slices
         about = dev(R(E, seed=209) * 0.1)
         zc = z.detach() - about.double().cpu().view(1, E, 1, 1)
@@ -474,13 +543,15 @@ def check_zpath():
         pa, pb = nanE(B, H, W, E), nanE(B, H, W, E)
         ga_, gb_ = torch.zeros(B, E, device=DEV), torch.zeros(B, E, device=DEV)
         hip.dw_fwd(x1d, pa, ga_, keff, beff)
-        hip.dw_fwd(zd, pb, gb_, keff, beff, zpre=zp)
+        _, names = launched(lambda: hip.dw_fwd(zd, pb, gb_, keff, beff, zpre=zp))
+        rows.append(form_row("dw_fwd z-path" + tag, names, ["dw_fwd_kernel<float, true>"]))
         rows.append(("dw_fwd z-path" + tag, max(rel(pb, pa), rel(gb_, ga_)), 2e-5))
         u, sg, dm = nhwcE(R(B, E, H, W, seed=214)), dev(R(B, E, seed=215).abs()), dev(R(B, E, seed=216) * 0.01)
         da_, db_ = nanE(B, H, W, E), nanE(B, H, W, E)
         ba_, bb_ = torch.zeros(5, E, device=DEV), torch.zeros(5, E, device=DEV)
         hip.dw_bwd_stats(x1d, pa, u, sg, dm, da_, *wd, ba_)
-        hip.dw_bwd_stats(zd, pa, u, sg, dm, db_, *wd, bb_, zpre=zp)
+        _, names = launched(lambda: hip.dw_bwd_stats(zd, pa, u, sg, dm, db_, *wd, bb_, zpre=zp))
+        rows.append(form_row("dw_bwd_stats z-path" + tag, names, ["dw_stats1_kernel<float, true>"]))
         rows.append(("dw_bwd_stats z-path" + tag, max(rel(db_, da_), rel(bb_, ba_)), 2e-5))
         # ---- depthwise backward: dx1 from x1 (old) vs dh + sums from z (new)
         bm, br_, bA = dev(R(4, E, seed=217) * 0.1), dev(R(4, E, seed=218).abs() + 0.5), dev(R(4, E, seed=219).abs() + 0.3)
@@ -492,7 +563,8 @@ def check_zpath():
         dgs2, dbs2 = [torch.zeros(E, device=DEV) for _ in range(4)], [torch.zeros(E, device=DEV) for _ in range(4)]
         dws2 = [torch.zeros_like(w) for w in wd]
         dhz, hst = nanE(B, H, W, E), torch.zeros(2, E, device=DEV)
-        hip.dw_bwd_bn(zd, da_, dhz, *wd, bst, bm, br_, bA, N, True, dgs2, dbs2, *dws2, zpre=zp, hstats=hst)
+        _, names = launched(lambda: hip.dw_bwd_bn(zd, da_, dhz, *wd, bst, bm, br_, bA, N, True, dgs2, dbs2, *dws2, zpre=zp, hstats=hst))
+        rows.append(form_row("dw_bwd_bn z-path" + tag, names, ["dw_bwd_kernel<float, 0, %s, true, 2>" % ("true" if -(-W // 60) < -(-W // 56) else "false")]))
         hd = nhwc(h.detach()).double().cpu()
         dhs = torch.where(hd < -3, torch.zeros_like(hd), torch.where(hd <= 3, hd / 3 + 0.5, torch.ones_like(hd)))
         dh_ref = hip.rp4_to_nhwc(dxo).double().cpu() * dhs
@@ -533,39 +605,59 @@ def check_zpath():
     return rows
 
 
+@owner_check
 def check_conv_rp():
     """Row-planar (RP4) operands of the 1x1 conv family: every role a ReparamConv block uses -- out (expand conv), source with
     on-load GELU x gate (pointwise conv), out + aux (SE-gradient epilogue), source / dy of the weight gradients, first source of the
-    three-source data gradient -- against the SAME call on NHWC tensors holding the same values (equal up to the order of the
-    atomics), at map sizes from 4x4 to 20x52, both conv kernels (Cout <= 80 / > 80) and both storage types."""
+    three-source data gradient -- against fp64 F.conv2d / einsum references AND against the SAME call on NHWC tensors holding the same
+    values (equal up to the order of the atomics), at map sizes from 4x4 to 64x80 (5120 pixels: the smallest map on which the M-split
+    kernel gives a wave two cout tiles at Cout = 96), both conv kernels (Cout <= 80 / > 80) and both storage types.  The bf16 rows draw
+    bf16-representable activations and weights, so only the on-load GELU x gate and the stored outputs are rounded: 1e-2, the rounding
+    tolerance of check_conv_bf16."""
     rows = []
     to_rp, to_nhwc = hip.nhwc_to_rp4, hip.rp4_to_nhwc
-    for (B, H, W, Cin, E, Cout, dt) in [(2, 20, 52, 12, 24, 12, torch.float32), (2, 4, 4, 96, 192, 96, torch.float32), (3, 9, 13, 24, 48, 24, torch.float32),
-                                        (1, 12, 16, 48, 96, 48, torch.float32), (2, 8, 12, 12, 24, 12, torch.bfloat16)]:
-        tag = " Cin=%d E=%d %dx%d %s" % (Cin, E, H, W, "bf16" if dt == torch.bfloat16 else "fp32")
-        tol = 1e-6 if dt == torch.float32 else 2e-2
+    f32, b16 = torch.float32, torch.bfloat16
+    for (B, H, W, Cin, E, Cout, dt) in [(2, 20, 52, 12, 24, 12, f32), (2, 4, 4, 96, 192, 96, f32), (3, 9, 13, 24, 48, 24, f32), (1, 12, 16, 48, 96, 48, f32),
+                                        (1, 64, 80, 48, 96, 48, f32), (1, 64, 80, 96, 192, 96, f32),
+                                        (2, 8, 12, 12, 24, 12, b16), (3, 9, 13, 24, 48, 24, b16), (2, 4, 4, 96, 192, 96, b16), (1, 64, 80, 48, 96, 48, b16),
+                                        (1, 64, 80, 96, 192, 96, b16)]:
+        tag = " Cin=%d E=%d %dx%d %s" % (Cin, E, H, W, "bf16" if dt == b16 else "fp32")
+        tol = 1e-6 if dt == f32 else 2e-2
+        t64, s64 = (TOL, 2e-4) if dt == f32 else (1e-2, 1e-2)
+        q = (lambda t: t) if dt == f32 else (lambda t: t.to(b16).double())
         prev = hip._MMA[0]
-        hip._MMA[0] = hip.BF16 if dt == torch.bfloat16 else hip.F32
+        hip._MMA[0] = hip.BF16 if dt == b16 else hip.F32
         try:
             cast = lambda t: t.to(dt).contiguous()
-            x, pre, dy = cast(nhwc(R(B, Cin, H, W, seed=301))), cast(nhwc(R(B, E, H, W, seed=302))), cast(nhwc(R(B, Cout, H, W, seed=303)))
-            dh = cast(nhwc(R(B, E, H, W, seed=304)))
-            we, be = dev(R(E, Cin, seed=305, scale=0.3)), dev(R(E, seed=306))
-            wpw, wsc = dev(R(Cout, E, seed=307, scale=0.2)), dev(R(Cout, Cin, seed=308, scale=0.3))
-            gate = dev(R(B, E, seed=309).abs())
+            xr, prer, dyr, dhr = q(R(B, Cin, H, W, seed=301)), q(R(B, E, H, W, seed=302)), q(R(B, Cout, H, W, seed=303)), q(R(B, E, H, W, seed=304))
+            x, pre, dy, dh = cast(nhwc(xr)), cast(nhwc(prer)), cast(nhwc(dyr)), cast(nhwc(dhr))
+            wer, ber = q(R(E, Cin, seed=305, scale=0.3)), R(E, seed=306)
+            wpwr, wscr = q(R(Cout, E, seed=307, scale=0.2)), q(R(Cout, Cin, seed=308, scale=0.3))
+            we, be, wpw, wsc = dev(wer), dev(ber), dev(wpwr), dev(wscr)
+            gater = R(B, E, seed=309).abs()
+            gate = dev(gater)
             pre_r, dh_r = to_rp(pre), to_rp(dh)
             mk = lambda *sh: torch.full(sh, float("nan"), device=DEV, dtype=dt)
+            big = "conv_tileM_kernel<1," if E > 80 else "conv_tile_kernel<1,"
             # expand conv: out row-planar (+ batch sums)
             wpe = hip.conv_pack(we, 1, [Cin])
             za, zb = mk(B, H, W, E), hip.rp4(mk(B, H, W, E))
             sa, sb = torch.zeros(2, E, device=DEV), torch.zeros(2, E, device=DEV)
             kw = dict(B=B, Hin=H, Win=W, Hout=H, Wout=W)
-            hip.conv_fwd([x], wpe, za, Cout=E, bias=be, stats=sa, stats_mode=hip.STATS_SUM_SQ, **kw)
-            hip.conv_fwd([x], wpe, zb, Cout=E, bias=be, stats=sb, stats_mode=hip.STATS_SUM_SQ, **kw)
+            _, na = launched(lambda: hip.conv_fwd([x], wpe, za, Cout=E, bias=be, stats=sa, stats_mode=hip.STATS_SUM_SQ, **kw))
+            _, nb = launched(lambda: hip.conv_fwd([x], wpe, zb, Cout=E, bias=be, stats=sb, stats_mode=hip.STATS_SUM_SQ, **kw))
+            rows.append(form_row("expand conv, Cout = %d: the %s kernel, NHWC and row-planar instance" % (E, "M-split" if E > 80 else "N-split") + tag,
+                                 na | nb, [big], ["conv_tile_kernel<" if E > 80 else "conv_tileM_kernel<", "conv_dma"]))
+            rows.append(form_row("expand conv: the row-planar call runs another instance than the NHWC call" + tag, nb - na, [big]))
             rows.append(("conv out row-planar" + tag, max(rel(to_nhwc(zb), za), rel(sb, sa) * 1e-2), tol))
+            z_ref = F.conv2d(xr, wer.view(E, Cin, 1, 1), ber)
+            s_ref = torch.stack([z_ref.sum((0, 2, 3)), (z_ref * z_ref).sum((0, 2, 3))])
+            rows.append(("conv out NHWC vs fp64" + tag, rel(nchw(za), z_ref), t64))
+            rows.append(("conv out row-planar vs fp64" + tag, rel(nchw(to_nhwc(zb)), z_ref), t64))
+            rows.append(("conv out NHWC / row-planar: batch sums vs fp64" + tag, max(rel(sa, s_ref), rel(sb, s_ref)), s64))
             # pointwise + shortcut: first source row-planar with GELU x gate
             n0, n1 = hip.conv_pack_size(1, Cout, [E]), hip.conv_pack_size(1, Cout, [Cin])
-            h2 = 2 if dt == torch.bfloat16 else 1
+            h2 = 2 if dt == b16 else 1
             wp2 = torch.empty(n0 + n1, device=DEV)
             hip.conv_pack(wpw, 1, [E], out=wp2[:n0 // h2])
             hip.conv_pack(wsc, 1, [Cin], out=wp2[n0 // h2:(n0 + n1) // h2])
@@ -573,31 +665,48 @@ def check_conv_rp():
             hip.conv_fwd([dict(view=pre, scale=gate, flags=hip.SRC_GELU), x], wp2, ya, Cout=Cout, **kw)
             hip.conv_fwd([dict(view=pre_r, scale=gate, flags=hip.SRC_GELU), x], wp2, yb, Cout=Cout, **kw)
             rows.append(("conv source row-planar (GELU x gate)" + tag, rel(yb, ya), tol))
+            gx = gelu(prer) * gater.view(B, E, 1, 1)
+            y_ref = F.conv2d(gx, wpwr.view(Cout, E, 1, 1)) + F.conv2d(xr, wscr.view(Cout, Cin, 1, 1))
+            rows.append(("conv source NHWC / row-planar (GELU x gate) vs fp64" + tag, max(rel(nchw(ya), y_ref), rel(nchw(yb), y_ref)), t64))
             # data gradient of the pointwise conv with the SE-gradient epilogue: out and aux row-planar
             wpt = hip.conv_pack_t(wpw, 1, 0, E, cred=Cout)
             ua, ub = mk(B, H, W, E), hip.rp4(mk(B, H, W, E))
             da, db_ = torch.zeros(B, E, device=DEV), torch.zeros(B, E, device=DEV)
             hip.conv_fwd([dy], wpt, ua, Cout=E, transposed=1, epilogue=hip.EP_SE_BWD, aux=pre, stats=da, stats_mode=hip.STATS_EP, **kw)
             hip.conv_fwd([dy], wpt, ub, Cout=E, transposed=1, epilogue=hip.EP_SE_BWD, aux=pre_r, stats=db_, stats_mode=hip.STATS_EP, **kw)
-            rows.append(("conv out + aux row-planar (SE gradient)" + tag, max(rel(to_nhwc(ub), ua), rel(db_, da) * (1e-2 if dt == torch.float32 else 1.0)), tol))
+            rows.append(("conv out + aux row-planar (SE gradient)" + tag, max(rel(to_nhwc(ub), ua), rel(db_, da) * (1e-2 if dt == f32 else 1.0)), tol))
+            u_ref = F.conv2d(dyr, wpwr.t().reshape(E, Cout, 1, 1))
+            ds_ref = (u_ref * gelu(prer)).sum((2, 3))
+            rows.append(("conv out + aux NHWC / row-planar (SE gradient): u vs fp64" + tag, max(rel(nchw(ua), u_ref), rel(nchw(to_nhwc(ub)), u_ref)), t64))
+            rows.append(("conv out + aux NHWC / row-planar (SE gradient): per-image sums vs fp64" + tag, max(rel(da, ds_ref), rel(db_, ds_ref)), s64))
             # weight gradients: row-planar source (GELU x gate) / row-planar dy
-            for nm, srcs_a, srcs_b, dya, dyb, co, ci in [
-                    ("wgrad source row-planar", [dict(view=pre, scale=gate, flags=hip.SRC_GELU), x], [dict(view=pre_r, scale=gate, flags=hip.SRC_GELU), x], dy, dy, Cout, E + Cin),
-                    ("wgrad dy row-planar", [x], [x], dh, dh_r, E, Cin)]:
+            for nm, srcs_a, srcs_b, dya, dyb, co, ci, gw_ref, gb_ref in [
+                    ("wgrad source row-planar", [dict(view=pre, scale=gate, flags=hip.SRC_GELU), x], [dict(view=pre_r, scale=gate, flags=hip.SRC_GELU), x], dy, dy, Cout, E + Cin,
+                     torch.einsum("bchw,bihw->ci", dyr, torch.cat([gx, xr], 1)), dyr.sum((0, 2, 3))),
+                    ("wgrad single source row-planar", [dict(view=pre, scale=gate, flags=hip.SRC_GELU)], [dict(view=pre_r, scale=gate, flags=hip.SRC_GELU)], dy, dy, Cout, E,
+                     torch.einsum("bchw,bihw->ci", dyr, gx), dyr.sum((0, 2, 3))),
+                    ("wgrad dy row-planar", [x], [x], dh, dh_r, E, Cin, torch.einsum("bchw,bihw->ci", dhr, xr), dhr.sum((0, 2, 3)))]:
                 ga_, gb_ = torch.zeros(co, ci, device=DEV), torch.zeros(co, ci, device=DEV)
                 ba_, bb_ = torch.zeros(co, device=DEV), torch.zeros(co, device=DEV)
                 hip.conv_wgrad(srcs_a, dya, ga_, ba_, Cout=co, **kw)
                 hip.conv_wgrad(srcs_b, dyb, gb_, bb_, Cout=co, **kw)
-                rows.append((nm + tag, max(rel(gb_, ga_), rel(bb_, ba_)), 2e-5 if dt == torch.float32 else tol))
+                rows.append((nm + tag, max(rel(gb_, ga_), rel(bb_, ba_)), 2e-5 if dt == f32 else tol))
+                rows.append((nm + " and NHWC vs fp64" + tag, max(rel(ga_, gw_ref), rel(gb_, gw_ref), rel(ba_, gb_ref), rel(bb_, gb_ref)), s64))
         finally:
             hip._MMA[0] = prev
     return rows
 
 
+@owner_check
 def check_se():
     rows = []
-    for cfg in ((3, 24, 6, 35), (8, 192, 48, 121), (30, 192, 48, 64)):   # the last one: the per-image kernel (batch too large for one block)
-        rows += _check_se(*cfg)
+    # every entry of the family is ONE kernel at every batch size (lmn_se_fwd / lmn_se_bwd: one block per image, rows.hip) -- pinned, so
+    # that a second form for large batches cannot arrive unowned
+    for cfg in ((3, 24, 6, 35), (8, 192, 48, 121), (30, 192, 48, 64)):
+        r, names = launched(lambda: _check_se(*cfg))
+        rows += r
+        rows.append(form_row("se B=%d: one kernel per entry" % cfg[0], names, ["se_fwd_kernel", "se_bwd_kernel", "se_bwd_dm_kernel", "se_bwd_params_kernel", "reparam_wfin_kernel"]))
+        rows.append(("se B=%d: no other kernel" % cfg[0], float(len(names) - 5), 0.0))
     return rows
 
 
@@ -647,6 +756,7 @@ def _check_se(B, E, Rr, HW):
 
 
 # ------------------------------------------------------------------------------------------------ attention
+@owner_check
 def check_na():
     """K = 3: the LDS-tiled kernels and (direct=True) the run-time-K direct kernels; K = 5, 7: the direct kernels (natten kernel_size;
     core/LM_Net.py:81-84 carries [3, 5]).  Oracle: oracle/natten_ref.py for every K (test_oracle_na.py pins its K = 5 form)."""
@@ -672,16 +782,30 @@ def check_na():
         for direct in ((False, True) if K == 3 else (False,)):
             t2 = tag + (" direct" if direct else "")
             out = torch.full((B, H, W, Cn), float("nan"), device=DEV)
-            hip.na_fwd(dev(qkv), dev(rpb), out, heads, direct=direct)
+            _, nf = launched(lambda: hip.na_fwd(dev(qkv), dev(rpb), out, heads, direct=direct))
             rows.append(("na_fwd" + t2, rel(out, o_ref), TOL))
             dqkv = torch.full((B, H, W, 3 * Cn), float("nan"), device=DEV)
             drpb = torch.zeros(heads, 2 * K - 1, 2 * K - 1, device=DEV)
-            hip.na_bwd(dev(qkv), dev(rpb), dev(do), dqkv, drpb, heads, direct=direct)
+            _, nb = launched(lambda: hip.na_bwd(dev(qkv), dev(rpb), dev(do), dqkv, drpb, heads, direct=direct))
+            # which kernels: K = 3 takes the LDS-tiled kernels of na.hip -- the backward in one pass where a block's tile fits (hd <= 2
+            # on maps of 16 or more rows and columns), else as the q pass + the k/v pass; direct=True and K = 5, 7 take the general-K
+            # kernels of na_gen.hip
+            if K == 3 and not direct:
+                fused = hd <= 2 and min(H, W) >= 16
+                rows.append(form_row("na_fwd" + t2 + ": LDS-tiled kernel", nf, ["na_fwd_kernel<%d, float>" % hd], ["na_fwd_gen"]))
+                rows.append(form_row("na_bwd" + t2 + (": one-pass backward" if fused else ": q pass + k/v pass"), nb,
+                                     ["na_bwd_fused_kernel<%d, %d, float>" % (hd, 3 * hd)] if fused else ["na_bwd_q_kernel<%d, float>" % hd, "na_bwd_kv_kernel<%d, float>" % hd],
+                                     ["na_bwd_q_kernel<", "na_bwd_kv_kernel<", "na_bwd_q_gen", "na_bwd_kv_gen"] if fused else ["na_bwd_fused", "na_bwd_q_gen", "na_bwd_kv_gen"]))
+            else:
+                rows.append(form_row("na_fwd / na_bwd" + t2 + ": general-K kernels", nf | nb,
+                                     ["na_fwd_gen_kernel<%d, float>" % hd, "na_bwd_q_gen_kernel<%d, float>" % hd, "na_bwd_kv_gen_kernel<%d, float>" % hd],
+                                     ["na_fwd_kernel<", "na_bwd_fused", "na_bwd_q_kernel<", "na_bwd_kv_kernel<"]))
             rows.append(("na_bwd dqkv" + t2, rel(dqkv, qkv.grad), 2e-4))
             rows.append(("na_bwd drpb" + t2, rel(drpb, rpb.grad), 2e-4))
     return rows
 
 
+@owner_check
 def check_gattn():
     rows = []
     for (B, N, heads, hd) in [(2, 70, 12, 31), (1, 484, 12, 31), (1, 130, 3, 8), (1, 1024, 12, 31), (1, 2500, 2, 8)]:   # (512x512 / 800x800 inputs)
@@ -705,6 +829,7 @@ def check_gattn():
 
 
 # ------------------------------------------------------------------------------------------------ norms
+@owner_check
 def check_ln():
     rows = []
     for Cn in (12, 24, 48, 96, 372):
@@ -719,13 +844,15 @@ def check_ln():
         rows.append(("ln_fwd C=%d" % Cn, rel(y, y_ref), TOL))
         dx = torch.full((n, Cn), float("nan"), device=DEV)
         dg, db = torch.zeros(Cn, device=DEV), torch.zeros(Cn, device=DEV)
-        hip.ln_bwd(dev(x), dev(g), dev(dy), dev(dres), dx, dg, db)
+        _, names = launched(lambda: hip.ln_bwd(dev(x), dev(g), dev(dy), dev(dres), dx, dg, db))
+        rows.append(form_row("ln_bwd C=%d: lanes per row" % Cn, names, ["ln_bwd_kernel<%d, float>" % {12: 4, 24: 8, 48: 16, 96: 32, 372: 64}[Cn]]))
         rows.append(("ln_bwd dx(+res) C=%d" % Cn, rel(dx, x.grad + dres), TOL))
         rows.append(("ln_bwd dgamma C=%d" % Cn, rel(dg, g.grad), 2e-4))
         rows.append(("ln_bwd dbeta C=%d" % Cn, rel(db, b.grad), 2e-4))
     return rows
 
 
+@owner_check
 def check_ln_linear():
     """LMN_SRC_LN: LayerNorm fused into the consuming Linear (norm1 -> qkv, norm2 -> fc1; /root/reference/core/modules.py:516-518,
     343-344, 50-56): y = W . LN(x) + b (+ residual) in ONE conv launch vs fp64 F.layer_norm + F.linear, the (mean, rstd) table the
@@ -734,7 +861,8 @@ def check_ln_linear():
     outputs, which reach the pre-pass through the `wide LayerNorm source` rule; pixel counts that leave partial tiles / chunks."""
     rows = []
     for Cn, Co, n in ((12, 36, 1043), (12, 24, 300), (24, 72, 777), (24, 48, 130), (48, 144, 333), (48, 96, 257), (96, 288, 203),
-                      (96, 192, 64), (372, 1116, 99), (372, 744, 50), (36, 24, 145), (72, 12, 77), (20, 8, 35), (12, 36, 24), (24, 48, 7)):
+                      (96, 192, 64), (372, 1116, 99), (372, 744, 50), (36, 24, 145), (72, 12, 77), (20, 8, 35), (12, 36, 24), (24, 48, 7),
+                      (48, 96, 5120)):   # (5120 rows: the smallest count at which the M-split kernel gives a wave two cout tiles at Cout = 96 -- the instance of the 88 x 88 level)
         x = (R(n, Cn, seed=131) * 1.7 + 0.6).requires_grad_(True)
         g, b = (R(Cn, seed=132).abs() + 0.5).requires_grad_(True), (R(Cn, seed=133) * 0.3).requires_grad_(True)
         w, bias = R(Co, Cn, seed=134, scale=0.2).requires_grad_(True), R(Co, seed=135).requires_grad_(True)
@@ -784,6 +912,7 @@ def check_ln_linear():
     return rows
 
 
+@owner_check
 def check_conv_up2():
     """LMN_SRC_UP2: bilinear x2 (align_corners=True) sampled where the 3x3 conv stages its window (up1..4, the `convs` branch of
     the skip fusers; /root/reference/core/LM_Net.py:58-74,117-120, core/modules.py:94,129) vs fp64 F.interpolate + F.conv2d, and
@@ -802,8 +931,12 @@ def check_conv_up2():
         xd = nhwc(x)
         wp = hip.conv_pack(dev(wt), 3, [Cin])
         y = torch.full((B, 2 * h, 2 * w, Cout), float("nan"), device=DEV)
-        hip.conv_fwd([dict(view=xd, flags=hip.SRC_UP2)], wp, y, B=B, Hin=2 * h, Win=2 * w, Hout=2 * h, Wout=2 * w, Cout=Cout, ksize=3,
-                     bias=dev(bias), residual=nhwc(res))
+        _, names = launched(lambda: hip.conv_fwd([dict(view=xd, flags=hip.SRC_UP2)], wp, y, B=B, Hin=2 * h, Win=2 * w, Hout=2 * h, Wout=2 * w, Cout=Cout, ksize=3,
+                                                 bias=dev(bias), residual=nhwc(res)))
+        # (the instance that samples on load carries UP = true as its last bool; the M-split kernel from Cout = 96)
+        rows.append(form_row("conv3x3(up2 on load)" + tag + ": %s-split kernel" % ("M" if Cout > 80 else "N"), names,
+                             ["conv_tileM_kernel<9," if Cout > 80 else "conv_tile_kernel<9, %d," % ((Cout + 15) // 16)], ["conv_dma", "up2_fwd"]))
+        rows.append(("form: conv3x3(up2 on load)" + tag + ": the UP instance", 0.0 if any(n.endswith("true>" if Cout > 80 else "true, 2>") for n in names) else 1.0, 0.5))
         rows.append(("conv3x3(up2 on load)" + tag, rel(nchw(y), y_ref), TOL))
         upd = torch.full((B, 2 * h, 2 * w, Cin), float("nan"), device=DEV)
         hip.up2_fwd(xd, upd)
@@ -820,13 +953,16 @@ def check_conv_up2():
         dy = R(*yr.shape, seed=154)
         yr.backward(dy)
         dW, db = torch.zeros(Cout, Cin, 3, 3, device=DEV), torch.zeros(Cout, device=DEV)
-        hip.conv_wgrad([dict(view=nhwc(x), flags=hip.SRC_UP2)], nhwc(dy), dW, db, B=B, Hin=2 * h, Win=2 * w, Hout=2 * h, Wout=2 * w, Cout=Cout, ksize=3)
+        _, names = launched(lambda: hip.conv_wgrad([dict(view=nhwc(x), flags=hip.SRC_UP2)], nhwc(dy), dW, db, B=B, Hin=2 * h, Win=2 * w, Hout=2 * h, Wout=2 * w, Cout=Cout, ksize=3))
         tag = " %dx%d %d->%d" % (h, w, Cin, Cout)
+        rows.append(form_row("wgrad3x3(up2 on load)" + tag + ": wgrad3_kernel<..., UP = true>", names, [("wgrad3_kernel<1, 1, 0, true>" if Cin <= 32 and Cout <= 16 else "wgrad3_kernel<2, 2, 0, true>")],
+                             ["wgrad_lds", "up2_fwd"]))
         rows.append(("wgrad3x3(up2 on load) dW" + tag, rel(dW, wt.grad), 2e-4))
         rows.append(("wgrad3x3(up2 on load) db" + tag, rel(db, bias.grad), 2e-4))
     return rows
 
 
+@owner_check
 def check_fused_sources_modes():
     """the on-load / epilogue fusions of round 5 (LMN_SRC_LN, LMN_SRC_UP2, LMN_EP_LN_BWD) in the modes that only the
     end-to-end tests reached -- bf16 STORAGE (PM = 2 instances) and deterministic mode (slot path of the epilogue statistics) --
@@ -855,7 +991,7 @@ def check_fused_sources_modes():
     mma0 = hip._MMA[0]
     hip._MMA[0] = hip.BF16
     try:
-        for Cn, Co, n in ((12, 36, 1043), (24, 72, 300), (48, 96, 257), (96, 192, 64), (372, 744, 50)):
+        for Cn, Co, n in ((12, 36, 1043), (24, 72, 300), (48, 96, 257), (96, 192, 64), (372, 744, 50), (12, 24, 300), (48, 96, 5120)):
             x = bf(dev(R(n, Cn, seed=171) * 1.7 + 0.6))
             g, b = dev(R(Cn, seed=172).abs() + 0.5), dev(R(Cn, seed=173) * 0.3)
             w, bias = dev(R(Co, Cn, seed=174, scale=0.2)), dev(R(Co, seed=175))
@@ -877,6 +1013,42 @@ def check_fused_sources_modes():
             dWu, dbu = torch.zeros(Co, Cn, 1, 1, device=DEV), torch.zeros(Co, device=DEV)
             hip.conv_wgrad([nrm.view(1, 1, n, Cn)], dy.view(1, 1, n, Co), dWu, dbu, B=1, Hin=1, Win=n, Hout=1, Wout=n, Cout=Co)
             rows.append(("bf16 storage LN+linear wgrad vs wgrad over ln_fwd" + tag, max(rel(dWf, dWu), rel(dbf, dbu)), 5e-3))
+            # ... and against fp64 (the bf16-stored x IS the input; LN(x) and the weights are rounded to bf16 operands, y is stored as
+            # bf16: the 1.2e-2 of the row above; weight gradients: two rounded operands, 1e-2 as in check_conv_bf16)
+            x64 = x.double().cpu().requires_grad_(True)
+            g64, b64 = g.double().cpu().requires_grad_(True), b.double().cpu().requires_grad_(True)
+            w64 = w.double().cpu().requires_grad_(True)
+            y64 = F.linear(F.layer_norm(x64, (Cn,), g64, b64, 1e-5), w64, bias.double().cpu())
+            dy64 = dy.double().cpu()
+            y64.backward(dy64)
+            rows.append(("bf16 storage LN+linear fwd vs fp64" + tag, rel(yf.view(n, Co), y64), 1.2e-2))
+            rows.append(("bf16 storage LN+linear wgrad vs fp64" + tag, max(rel(dWf.view(Co, Cn), w64.grad), rel(dbf, dy64.sum(0))), 1e-2))
+            if Cn <= 48:   # LayerNorm backward in the data-gradient conv's epilogue, bf16 storage (dx and the residual gradient stored as bf16)
+                dres = bf(dev(R(n, Cn, seed=177)))
+                gpair = torch.zeros(2, Cn, device=DEV)
+                dx2 = torch.full((1, 1, n, Cn), float("nan"), device=DEV, dtype=torch.bfloat16)
+                wpt = hip.conv_pack_t(w.view(Co, Cn, 1, 1), 1, 0, Cn, cred=Co)
+                _, names = launched(lambda: hip.conv_fwd([dy.view(1, 1, n, Co)], wpt, dx2, B=1, Hin=1, Win=n, Hout=1, Wout=n, Cout=Cn, transposed=1, epilogue=hip.EP_LN_BWD, act=0,
+                                                         aux=x.view(1, 1, n, Cn), p=(g, None, None, None, None, None, stats), residual=dres.view(1, 1, n, Cn), stats=gpair,
+                                                         stats_mode=hip.STATS_EP))
+                rows.append(form_row("bf16 storage LN backward in the conv epilogue" + tag, names, ["conv_tile_kernel<1, %d, 6, false, 2," % ((Cn + 15) // 16)]))
+                rows.append(("bf16 storage LN backward in the conv epilogue: dx vs fp64" + tag, rel(dx2.view(n, Cn), x64.grad + dres.double().cpu()), 1.2e-2))
+                rows.append(("bf16 storage LN backward in the conv epilogue: dgamma / dbeta vs fp64" + tag, max(rel(gpair[1], g64.grad), rel(gpair[0], b64.grad)), 1e-2))
+        # GELU on load in the weight gradient (fc2 of the transformer MLPs), bf16 storage, against fp64
+        n, Cn, Co = 300, 24, 12
+        hx, dy = bf(dev(R(n, Cn, seed=178))), bf(dev(R(n, Co, seed=179)))
+        dWg, dbg = torch.zeros(Co, Cn, 1, 1, device=DEV), torch.zeros(Co, device=DEV)
+        _, names = launched(lambda: hip.conv_wgrad([dict(view=hx.view(1, 1, n, Cn), flags=hip.SRC_GELU)], dy.view(1, 1, n, Co), dWg, dbg, B=1, Hin=1, Win=n, Hout=1, Wout=n, Cout=Co))
+        rows.append(form_row("bf16 storage wgrad with GELU on load: the wave-staged kernel", names, ["wgrad_1x1w_kernel<1, 2, 2>"]))
+        rows.append(("bf16 storage wgrad with GELU on load vs fp64", max(rel(dWg.view(Co, Cn), dy.double().cpu().t() @ gelu(hx.double().cpu())), rel(dbg, dy.double().cpu().sum(0))), 1e-2))
+        # plain 1x1 weight gradients over bf16-stored operands: the direct kernel (one 2-byte load per lane and MFMA operand) instead of
+        # the wave-staged one; bf16 products are exact in fp32 and the gradients stay fp32: 2e-4, as in check_bf16_storage_rows
+        for Cn, Co, kern in ((12, 4, "wgrad_1x1_kernel<1, 1, 2>"), (24, 24, "wgrad_1x1_kernel<2, 2, 2>"), (12, 24, "wgrad_1x1_kernel<2, 1, 2>")):
+            hx, dy = bf(dev(R(n, Cn, seed=180))), bf(dev(R(n, Co, seed=181)))
+            dWp, dbp = torch.zeros(Co, Cn, 1, 1, device=DEV), torch.zeros(Co, device=DEV)
+            _, names = launched(lambda: hip.conv_wgrad([hx.view(1, 1, n, Cn)], dy.view(1, 1, n, Co), dWp, dbp, B=1, Hin=1, Win=n, Hout=1, Wout=n, Cout=Co))
+            rows.append(form_row("bf16 storage 1x1 wgrad %d->%d: the direct kernel" % (Cn, Co), names, [kern], ["wgrad_1x1w"]))
+            rows.append(("bf16 storage 1x1 wgrad %d->%d vs fp64" % (Cn, Co), max(rel(dWp.view(Co, Cn), dy.double().cpu().t() @ hx.double().cpu()), rel(dbp, dy.double().cpu().sum(0))), 2e-4))
         for (B, h, w_, Cin, Cout) in ((2, 9, 11, 24, 12), (1, 22, 13, 48, 24), (1, 8, 7, 192, 96), (2, 16, 16, 24, 12), (1, 22, 37, 48, 24)):
             x = bf(nhwc(R(B, Cin, h, w_, seed=181)))
             wt, bias = dev(R(Cout, Cin, 3, 3, seed=182, scale=0.15)), dev(R(Cout, seed=183))
@@ -940,14 +1112,22 @@ def check_fused_sources_modes():
     return rows
 
 
+@owner_check
 def check_conv_dma3():
     """conv_dma3_kernel (round 6): the LDS-DMA double-buffered 3x3 stride-1 kernel of the small-channel layers (skip-fuser convs, `nat`
     patch embedding and their data gradients at levels 0-1; /root/reference/core/modules.py:22-39,83-143, core/LM_Net.py:58-74) vs fp64
     F.conv2d / its autograd, and against the LDS-tiled kernel on the same call (lmn_conv_dma_config A/B).  Shapes: 12 / 24 source
     channels x one / two cout tiles, maps that are not multiples of the 8 x 16 tile (zero padding and partial tiles come from the
     DMA's bounds check), a one-tile-per-block and a many-tiles-per-block grid (prologue-only and steady-state pipeline), source / output
-    slices of wider buffers, residual, SUM_SQ statistics about a shift (4 slices), deterministic slots, the transposed (data-gradient) form."""
+    slices of wider buffers, residual, SUM_SQ statistics about a shift (4 slices), deterministic slots, the transposed (data-gradient) form.
+    Every call is recorded: with bit 0 of lmn_conv_dma_config set it must launch conv_dma3_kernel and no conv_tile*_kernel, with the bit
+    clear the reverse -- an A/B row of a shape the predicate rejects would compare the LDS-tiled kernel with itself.  The LDS-tiled
+    runs are compared with fp64 as well, so both sides of the switch are owned here.  (The predicate -- `dma_ok` in conv_fwd.hip -- takes
+    every listed shape, the 5 x 7 map with Cout = 8 included: there is no FALLS_BACK list here.)"""
     rows = []
+    DMA, TILE = "conv_dma3_kernel<", "conv_tile_kernel<9,"
+    on = lambda what, names: rows.append(form_row("conv_dma3 " + what + ": LDS-DMA kernel, no LDS-tiled kernel", names, [DMA], ["conv_tile_kernel<", "conv_tileM_kernel<"]))
+    off = lambda what, names: rows.append(form_row("conv_dma3 " + what + ": LDS-tiled kernel, no LDS-DMA kernel", names, [TILE], ["conv_dma"]))
     prev = hip.conv_dma_config(1, 1)
     try:
         for (B, H, W, Cin, Cout) in ((2, 40, 50, 12, 12), (1, 33, 37, 24, 12), (2, 24, 32, 12, 24), (1, 17, 64, 24, 24), (3, 96, 112, 24, 12),
@@ -968,23 +1148,28 @@ def check_conv_dma3():
                 hip.conv_dma_config(mode, 1)
                 outb = torch.full((B, H, W, Cout + 12), float("nan"), device=DEV)
                 srep = torch.zeros(4, 2, Cout, device=DEV)
-                hip.conv_fwd([hip.V(xb, 4, Cin)], wp, hip.V(outb, 8, Cout), B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b),
-                             residual=nhwc(res), stats=srep, stats_mode=hip.STATS_SUM_SQ, stats_rep=4, p=(None, None, None, None, dev(shift)))
+                _, names = launched(lambda: hip.conv_fwd([hip.V(xb, 4, Cin)], wp, hip.V(outb, 8, Cout), B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b),
+                                                         residual=nhwc(res), stats=srep, stats_mode=hip.STATS_SUM_SQ, stats_rep=4, p=(None, None, None, None, dev(shift))))
                 got[mode] = (outb, srep.sum(0))
+                (on if mode else off)("fwd (slices, bias, residual), mode %d" % mode + tag, names)
             hip.conv_dma_config(1, 1)
+            rows.append(("conv_dma3 switched off: LDS-tiled fwd (slices, bias, residual) vs fp64" + tag, rel(nchw(got[0][0][..., 8:8 + Cout]), y_ref), TOL))
             rows.append(("conv_dma3 fwd (slices, bias, residual)" + tag, rel(nchw(got[1][0][..., 8:8 + Cout]), y_ref), TOL))
             rows.append(("conv_dma3 fwd vs LDS-tiled kernel" + tag, rel(got[1][0][..., 8:8 + Cout], got[0][0][..., 8:8 + Cout]), 2e-6))
             rows.append(("conv_dma3 untouched slices stay NaN" + tag, 0.0 if bool(torch.isnan(got[1][0][..., :8]).all() and torch.isnan(got[1][0][..., 8 + Cout:]).all()) else 1.0, 0.5))
             zd = (z - shift.view(1, -1, 1, 1)).detach()
             sref = torch.stack([zd.sum((0, 2, 3)), (zd * zd).sum((0, 2, 3))])
             rows.append(("conv_dma3 SUM_SQ statistics about a shift" + tag, rel(got[1][1], sref), 2e-4))
+            rows.append(("conv_dma3 switched off: LDS-tiled SUM_SQ statistics about a shift vs fp64" + tag, rel(got[0][1], sref), 2e-4))
             # plain call (no residual, no statistics, whole tensors), and statistics only (out = None)
             xw = nhwc(xs.detach())
             y1 = torch.full((B, H, W, Cout), float("nan"), device=DEV)
-            hip.conv_fwd([xw], wp, y1, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b))
+            _, names = launched(lambda: hip.conv_fwd([xw], wp, y1, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b)))
+            on("fwd plain" + tag, names)
             rows.append(("conv_dma3 fwd plain" + tag, rel(nchw(y1), z), TOL))
             s1 = torch.zeros(2, Cout, device=DEV)
-            hip.conv_fwd([xw], wp, None, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b), stats=s1, stats_mode=hip.STATS_SUM_SQ)
+            _, names = launched(lambda: hip.conv_fwd([xw], wp, None, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b), stats=s1, stats_mode=hip.STATS_SUM_SQ))
+            on("statistics only" + tag, names)
             zz = z.detach()
             rows.append(("conv_dma3 statistics only" + tag, rel(s1, torch.stack([zz.sum((0, 2, 3)), (zz * zz).sum((0, 2, 3))])), 2e-4))
             # data gradient (transposed form: taps flipped, weights from conv_pack_t): dy has Cout channels -> only when the kernel takes them
@@ -994,12 +1179,15 @@ def check_conv_dma3():
                 wpt = hip.conv_pack_t(dev(w.detach()), 3)
                 acc = R(B, Cin, H, W, seed=407)
                 dx = torch.full((B, H, W, Cin), float("nan"), device=DEV)
-                hip.conv_fwd([nhwc(dy)], wpt, dx, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cin, ksize=3, transposed=1, residual=nhwc(acc))
+                _, names = launched(lambda: hip.conv_fwd([nhwc(dy)], wpt, dx, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cin, ksize=3, transposed=1, residual=nhwc(acc)))
+                on("data gradient" + tag, names)
                 rows.append(("conv_dma3 data gradient (+ accumulate)" + tag, rel(nchw(dx), xs.grad + acc), TOL))
                 hip.conv_dma_config(0, 1)
                 dx0 = torch.full((B, H, W, Cin), float("nan"), device=DEV)
-                hip.conv_fwd([nhwc(dy)], wpt, dx0, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cin, ksize=3, transposed=1, residual=nhwc(acc))
+                _, names = launched(lambda: hip.conv_fwd([nhwc(dy)], wpt, dx0, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cin, ksize=3, transposed=1, residual=nhwc(acc)))
+                off("data gradient, switched off" + tag, names)
                 hip.conv_dma_config(1, 1)
+                rows.append(("conv_dma3 switched off: LDS-tiled data gradient vs fp64" + tag, rel(nchw(dx0), xs.grad + acc), TOL))
                 rows.append(("conv_dma3 data gradient vs LDS-tiled kernel" + tag, rel(dx, dx0), 2e-6))
         # deterministic mode: statistics through the per-block slots, two launches bit-identical
         det0 = hip.get_deterministic()
@@ -1012,8 +1200,10 @@ def check_conv_dma3():
             for rep in range(2):
                 y = torch.full((B, H, W, Cout), float("nan"), device=DEV)
                 st = torch.zeros(2, Cout, device=DEV)
-                hip.conv_fwd([x], wp, y, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=b, stats=st, stats_mode=hip.STATS_SUM_SQ)
+                _, names = launched(lambda: hip.conv_fwd([x], wp, y, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=b, stats=st, stats_mode=hip.STATS_SUM_SQ))
                 outs.append((y, st))
+                on("deterministic statistics", names)
+                rows.append(form_row("conv_dma3 deterministic statistics: the slots are folded by det_sum_kernel", names, ["det_sum_kernel"]))
             zr = F.conv2d(nchw(x), w, b.double().cpu(), padding=1)
             rows.append(("conv_dma3 deterministic statistics", rel(outs[0][1], torch.stack([zr.sum((0, 2, 3)), (zr * zr).sum((0, 2, 3))])), 2e-4))
             rows.append(("conv_dma3 deterministic: two launches bit-identical", 0.0 if (torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])) else 1.0, 0.5))
@@ -1024,6 +1214,7 @@ def check_conv_dma3():
     return rows
 
 
+@owner_check
 def check_conv_dmaM():
     """conv_dmaM_kernel (round 6): the M-split tile of the WIDE 3x3 stride-1 convs with window and weights by LDS-DMA (skip-fuser /
     bottleneck / decoder convs at 88^2 / 44^2 / 22^2 and their data gradients; /root/reference/core/modules.py:83-143, core/LM_Net.py:14-39)
@@ -1031,12 +1222,24 @@ def check_conv_dmaM():
     (48 -> 96 / 144, 96 -> 96 / 192, 372 -> 372 on their maps: a last K16 block of 4 channels), one- and two-stage layers (the counted
     waits of the weight ring run out differently there), maps that are not multiples of the tile, a grid whose blocks walk two tiles (the
     drain at a tile's start), source / output slices of wider buffers, residual, SUM_SQ statistics about a shift (4 slices), deterministic
-    slots, the transposed (data-gradient) form."""
+    slots, the transposed (data-gradient) form.
+    Every call is recorded: with bit 2 of lmn_conv_dma_config set it must launch conv_dmaM_kernel and no conv_tile*_kernel, with the bit
+    clear conv_tileM_kernel -- except the calls of FALLS_BACK, which both settings give to the N-split kernel.  The runs with the bit
+    clear are compared with fp64 as well, so conv_tileM_kernel's 3x3 instances are owned here."""
     rows = []
+    # data gradients the predicate never sees: the transposed call's OUTPUT has Cin channels, and `P.NCTT >= msplit_min` (conv_fwd.hip:
+    # six cout tiles, i.e. more than 80 output channels) sends only wider outputs to the M-split branch that holds the dmaM predicate
+    FALLS_BACK = {(B_, H_, W_, Cin_, Cout_): "P.NCTT >= msplit_min (the data gradient has %d <= 80 output channels)" % Cin_
+                  for (B_, H_, W_, Cin_, Cout_) in ((2, 88, 88, 48, 144), (1, 88, 88, 48, 96), (1, 19, 37, 52, 100), (9, 30, 41, 20, 112), (1, 5, 7, 36, 96), (2, 20, 20, 16, 96),
+                                                     (1, 12, 12, 8, 96), (40, 64, 64, 16, 100))}
+    on = lambda what, names: rows.append(form_row("conv_dmaM " + what + ": LDS-DMA kernel, no LDS-tiled kernel", names, ["conv_dmaM_kernel<"], ["conv_tile_kernel<", "conv_tileM_kernel<"]))
+    off = lambda what, names: rows.append(form_row("conv_dmaM " + what + ": conv_tileM_kernel, no LDS-DMA kernel", names, ["conv_tileM_kernel<9,"], ["conv_dma", "conv_tile_kernel<"]))
+    back = lambda what, names: rows.append(form_row("conv_dmaM " + what + ": falls back to the N-split kernel", names, ["conv_tile_kernel<9,"], ["conv_dma", "conv_tileM_kernel<"]))
     prev = hip.conv_dma_config(7, 1)
     try:
         for (B, H, W, Cin, Cout) in ((2, 22, 22, 372, 372), (2, 44, 44, 96, 192), (1, 44, 44, 96, 96), (2, 88, 88, 48, 144), (1, 88, 88, 48, 96),
-                                     (1, 19, 37, 52, 100), (9, 30, 41, 20, 112), (1, 5, 7, 36, 96), (2, 20, 20, 16, 96), (1, 12, 12, 8, 96), (40, 64, 64, 16, 100)):
+                                     (1, 19, 37, 52, 100), (9, 30, 41, 20, 112), (1, 5, 7, 36, 96), (2, 20, 20, 16, 96), (1, 12, 12, 8, 96), (40, 64, 64, 16, 100),
+                                     (1, 19, 37, 100, 112)):   # (the last one: a map of partial tiles whose DATA GRADIENT the LDS-DMA kernel takes too -- 100 output channels; see FALLS_BACK)
             tag = " %dx%dx%d %d->%d" % (B, H, W, Cin, Cout)
             x = R(B, Cin + 8, H, W, seed=501)
             w = R(Cout, Cin, 3, 3, seed=502, scale=0.05).requires_grad_(True)
@@ -1053,19 +1256,23 @@ def check_conv_dmaM():
                 hip.conv_dma_config(mode, 1)
                 outb = torch.full((B, H, W, Cout + 12), float("nan"), device=DEV)
                 srep = torch.zeros(4, 2, Cout, device=DEV)
-                hip.conv_fwd([hip.V(xb, 4, Cin)], wp, hip.V(outb, 8, Cout), B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b),
-                             residual=nhwc(res), stats=srep, stats_mode=hip.STATS_SUM_SQ, stats_rep=4, p=(None, None, None, None, dev(shift)))
+                _, names = launched(lambda: hip.conv_fwd([hip.V(xb, 4, Cin)], wp, hip.V(outb, 8, Cout), B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b),
+                                                         residual=nhwc(res), stats=srep, stats_mode=hip.STATS_SUM_SQ, stats_rep=4, p=(None, None, None, None, dev(shift))))
                 got[mode] = (outb, srep.sum(0))
+                (on if mode == 7 else off)("fwd (slices, bias, residual), mode %d" % mode + tag, names)
             hip.conv_dma_config(7, 1)
+            rows.append(("conv_dmaM switched off: conv_tileM_kernel fwd (slices, bias, residual) vs fp64" + tag, rel(nchw(got[3][0][..., 8:8 + Cout]), y_ref), TOL))
             rows.append(("conv_dmaM fwd (slices, bias, residual)" + tag, rel(nchw(got[7][0][..., 8:8 + Cout]), y_ref), TOL))
             rows.append(("conv_dmaM fwd vs conv_tileM_kernel" + tag, rel(got[7][0][..., 8:8 + Cout], got[3][0][..., 8:8 + Cout]), 4e-6))
             rows.append(("conv_dmaM untouched slices stay NaN" + tag, 0.0 if bool(torch.isnan(got[7][0][..., :8]).all() and torch.isnan(got[7][0][..., 8 + Cout:]).all()) else 1.0, 0.5))
             zd = (z - shift.view(1, -1, 1, 1)).detach()
             sref = torch.stack([zd.sum((0, 2, 3)), (zd * zd).sum((0, 2, 3))])
             rows.append(("conv_dmaM SUM_SQ statistics about a shift" + tag, rel(got[7][1], sref), 2e-4))
+            rows.append(("conv_dmaM switched off: conv_tileM_kernel SUM_SQ statistics about a shift vs fp64" + tag, rel(got[3][1], sref), 2e-4))
             xw = nhwc(xs.detach())
             y1 = torch.full((B, H, W, Cout), float("nan"), device=DEV)
-            hip.conv_fwd([xw], wp, y1, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b))
+            _, names = launched(lambda: hip.conv_fwd([xw], wp, y1, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=dev(b)))
+            on("fwd plain" + tag, names)
             rows.append(("conv_dmaM fwd plain" + tag, rel(nchw(y1), z), TOL))
             # data gradient (transposed form: taps flipped, weights from conv_pack_t) when ITS output (Cin channels) is wide enough for the M-split
             dy = R(B, Cout, H, W, seed=506)
@@ -1073,12 +1280,16 @@ def check_conv_dmaM():
             wpt = hip.conv_pack_t(dev(w.detach()), 3)
             acc = R(B, Cin, H, W, seed=507)
             dx = torch.full((B, H, W, Cin), float("nan"), device=DEV)
-            hip.conv_fwd([nhwc(dy)], wpt, dx, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cin, ksize=3, transposed=1, residual=nhwc(acc))
+            fb = (B, H, W, Cin, Cout) in FALLS_BACK
+            _, names = launched(lambda: hip.conv_fwd([nhwc(dy)], wpt, dx, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cin, ksize=3, transposed=1, residual=nhwc(acc)))
+            (back if fb else on)("data gradient" + tag, names)
             rows.append(("conv_dmaM data gradient (+ accumulate)" + tag, rel(nchw(dx), xs.grad + acc), TOL))
             hip.conv_dma_config(3, 1)
             dx0 = torch.full((B, H, W, Cin), float("nan"), device=DEV)
-            hip.conv_fwd([nhwc(dy)], wpt, dx0, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cin, ksize=3, transposed=1, residual=nhwc(acc))
+            _, names = launched(lambda: hip.conv_fwd([nhwc(dy)], wpt, dx0, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cin, ksize=3, transposed=1, residual=nhwc(acc)))
+            (back if fb else off)("data gradient, switched off" + tag, names)
             hip.conv_dma_config(7, 1)
+            rows.append(("conv_dmaM switched off: data gradient vs fp64" + tag, rel(nchw(dx0), xs.grad + acc), TOL))
             rows.append(("conv_dmaM data gradient vs the LDS-tiled kernels" + tag, rel(dx, dx0), 4e-6))
         # deterministic mode: statistics through the per-block slots, two launches bit-identical
         det0 = hip.get_deterministic()
@@ -1091,8 +1302,9 @@ def check_conv_dmaM():
             for rep in range(2):
                 y = torch.full((B, H, W, Cout), float("nan"), device=DEV)
                 st = torch.zeros(2, Cout, device=DEV)
-                hip.conv_fwd([x], wp, y, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=b, stats=st, stats_mode=hip.STATS_SUM_SQ)
+                _, names = launched(lambda: hip.conv_fwd([x], wp, y, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=Cout, ksize=3, bias=b, stats=st, stats_mode=hip.STATS_SUM_SQ))
                 outs.append((y, st))
+                on("deterministic statistics", names)
             zr = F.conv2d(nchw(x), w, b.double().cpu(), padding=1)
             rows.append(("conv_dmaM deterministic statistics", rel(outs[0][1], torch.stack([zr.sum((0, 2, 3)), (zr * zr).sum((0, 2, 3))])), 2e-4))
             rows.append(("conv_dmaM deterministic: two launches bit-identical", 0.0 if (torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])) else 1.0, 0.5))
@@ -1103,6 +1315,7 @@ def check_conv_dmaM():
     return rows
 
 
+@owner_check
 def check_conv_dma1():
     """conv_dma1_kernel (round 6): the LDS-DMA streaming form of ReparamConv's 1x1 convs at levels 0-1 (/root/reference/core/modules.py:
     537-539, 576-599) -- expand conv (row-planar out + SUM_SQ statistics about a shift, in slices), pointwise + shortcut (row-planar
@@ -1110,8 +1323,15 @@ def check_conv_dma1():
     gradient -- against the LDS-tiled kernel on the SAME call (lmn_conv_dma_config A/B; that kernel is pinned to fp64 by check_conv_fwd /
     check_zpath / check_conv_rp) and against fp64 directly for the expand conv and the pointwise pair.  Channel sets of level 0 (12 / 24),
     level 1 (24 / 48) and the RGB stem (4 -> 24); one tile per block, many tiles per block, several images per block (gate / SE-sum
-    hand-over at the image change), deterministic mode."""
+    hand-over at the image change), deterministic mode.
+    Every call is recorded: with bit 1 of lmn_conv_dma_config set it must launch conv_dma1_kernel and no conv_tile*_kernel, with the bit
+    clear conv_tile_kernel -- except the calls of FALLS_BACK.  All four calls are compared with fp64 under both settings."""
     rows = []
+    # calls dma1_select (conv_fwd.hip) rejects: (call, Cin, E) -> clause
+    FALLS_BACK = {("dx", 24, 48): "S.tp <= 0: lmn_conv_dma1_tp leaves row 8 of its instance table (the level-1 three-source data gradient) out of "
+                                  "the default LMN_CONV_DMA1_MASK 0xeff"}
+    on = lambda what, names: rows.append(form_row("conv_dma1 " + what + ": LDS-DMA kernel, no LDS-tiled kernel", names, ["conv_dma1_kernel<"], ["conv_tile_kernel<", "conv_tileM_kernel<"]))
+    off = lambda what, names: rows.append(form_row("conv_dma1 " + what + ": LDS-tiled kernel, no LDS-DMA kernel", names, ["conv_tile_kernel<1,"], ["conv_dma"]))
     to_rp, to_nhwc = hip.nhwc_to_rp4, hip.rp4_to_nhwc
     prev = hip.conv_dma_config(3, 1)
     mk = lambda *sh: torch.full(sh, float("nan"), device=DEV)
@@ -1138,7 +1358,8 @@ def check_conv_dma1():
                 wpe = hip.conv_pack(we, 1, [Cin])
                 z = hip.rp4(mk(B, H, W, E))
                 st = torch.zeros(4, 2, E, device=DEV)
-                hip.conv_fwd([x], wpe, z, Cout=E, bias=be, stats=st, stats_mode=hip.STATS_SUM_SQ, stats_rep=4, p=(None, None, None, None, shift), **kw)
+                nm = {}
+                _, nm["z"] = launched(lambda: hip.conv_fwd([x], wpe, z, Cout=E, bias=be, stats=st, stats_mode=hip.STATS_SUM_SQ, stats_rep=4, p=(None, None, None, None, shift), **kw))
                 r["z"], r["zst"] = to_nhwc(z), st.sum(0)
                 if Cin != 4:
                     # F2: pointwise + shortcut
@@ -1147,13 +1368,13 @@ def check_conv_dma1():
                     hip.conv_pack(wpw, 1, [E], out=wp2[:n0])
                     hip.conv_pack(wsc, 1, [Cin], out=wp2[n0:n0 + n1])
                     y = mk(B, H, W, Cout)
-                    hip.conv_fwd([dict(view=pre_r, scale=gate, flags=hip.SRC_GELU), x], wp2, y, Cout=Cout, bias=dev(b2r), **kw)
+                    _, nm["y"] = launched(lambda: hip.conv_fwd([dict(view=pre_r, scale=gate, flags=hip.SRC_GELU), x], wp2, y, Cout=Cout, bias=dev(b2r), **kw))
                     r["y"] = y
                     # B1: SE-gradient conv
                     wpt = hip.conv_pack_t(wpw, 1, 0, E, cred=Cout)
                     u = hip.rp4(mk(B, H, W, E))
                     ds = torch.zeros(B, E, device=DEV)
-                    hip.conv_fwd([dy], wpt, u, Cout=E, transposed=1, epilogue=hip.EP_SE_BWD, aux=pre_r, stats=ds, stats_mode=hip.STATS_EP, **kw)
+                    _, nm["u"] = launched(lambda: hip.conv_fwd([dy], wpt, u, Cout=E, transposed=1, epilogue=hip.EP_SE_BWD, aux=pre_r, stats=ds, stats_mode=hip.STATS_EP, **kw))
                     r["u"], r["ds"] = to_nhwc(u), ds
                     # B2: three-source data gradient (any packed operator of that shape: expand^T | square | shortcut^T)
                     wa, wb, wc = dev(R(Cin, E, seed=512, scale=0.2)), dev(R(Cin, Cin, seed=513, scale=0.3)), dev(R(Cin, Cout, seed=514, scale=0.3))
@@ -1161,20 +1382,33 @@ def check_conv_dma1():
                     wp3 = torch.empty(m0 + m1 + m2, device=DEV)
                     hip.conv_pack(wa, 1, [E], out=wp3[:m0]); hip.conv_pack(wb, 1, [Cin], out=wp3[m0:m0 + m1]); hip.conv_pack(wc, 1, [Cout], out=wp3[m0 + m1:])
                     dx = mk(B, H, W, Cin)
-                    hip.conv_fwd([dh_r, x, dy], wp3, dx, Cout=Cin, bias=dev(R(Cin, seed=515)), **kw)
+                    _, nm["dx"] = launched(lambda: hip.conv_fwd([dh_r, x, dy], wp3, dx, Cout=Cin, bias=dev(R(Cin, seed=515)), **kw))
                     r["dx"] = dx
+                for k_, names in nm.items():
+                    (on if mode and (k_, Cin, E) not in FALLS_BACK else off)("call %s, mode %d" % (k_, mode) + tag, names)
                 res[mode] = r
             hip.conv_dma_config(3, 1)
             for k_ in res[3]:
                 scale_ = 1e-2 if k_ in ("zst", "ds") else 1.0       # (sums: float-atomic order)
                 rows.append(("conv_dma1 vs LDS-tiled kernel: %s%s" % (k_, tag), rel(res[3][k_], res[0][k_]) * scale_, 2e-6))
             zref = F.conv2d(xr, wer.view(E, Cin, 1, 1), ber)
-            rows.append(("conv_dma1 expand conv vs fp64" + tag, rel(nchw(res[3]["z"]), zref), TOL))
             zd = zref - shift.double().cpu().view(1, -1, 1, 1)
-            rows.append(("conv_dma1 expand statistics vs fp64" + tag, rel(res[3]["zst"], torch.stack([zd.sum((0, 2, 3)), (zd * zd).sum((0, 2, 3))])), 2e-4))
+            zsref = torch.stack([zd.sum((0, 2, 3)), (zd * zd).sum((0, 2, 3))])
+            for mode, what in ((3, "conv_dma1"), (0, "conv_dma1 switched off: LDS-tiled")):
+                rows.append(("%s expand conv vs fp64" % what + tag, rel(nchw(res[mode]["z"]), zref), TOL))
+                rows.append(("%s expand statistics vs fp64" % what + tag, rel(res[mode]["zst"], zsref), 2e-4))
             if Cin != 4:
                 yref = F.conv2d(gelu(prer) * gater.view(B, E, 1, 1), wpwr.view(Cout, E, 1, 1)) + F.conv2d(xr, wscr.view(Cout, Cin, 1, 1), b2r)
-                rows.append(("conv_dma1 pointwise + shortcut vs fp64" + tag, rel(nchw(res[3]["y"]), yref), TOL))
+                dyr, dhr = nchw(dy), nchw(dh)
+                uref = F.conv2d(dyr, wpwr.t().reshape(E, Cout, 1, 1))
+                dsref = (uref * gelu(prer)).sum((2, 3))
+                w3r = torch.cat([R(Cin, E, seed=512, scale=0.2), R(Cin, Cin, seed=513, scale=0.3), R(Cin, Cout, seed=514, scale=0.3)], 1)
+                dxref = F.conv2d(torch.cat([dhr, xr, dyr], 1), w3r.view(Cin, E + Cin + Cout, 1, 1), R(Cin, seed=515))
+                for mode, what in ((3, "conv_dma1"), (0, "conv_dma1 switched off: LDS-tiled")):
+                    rows.append(("%s pointwise + shortcut vs fp64" % what + tag, rel(nchw(res[mode]["y"]), yref), TOL))
+                    rows.append(("%s SE-gradient conv vs fp64" % what + tag, rel(nchw(res[mode]["u"]), uref), TOL))
+                    rows.append(("%s SE-gradient per-image sums vs fp64" % what + tag, rel(res[mode]["ds"], dsref), 2e-4))
+                    rows.append(("%s three-source data gradient vs fp64" % what + tag, rel(nchw(res[mode]["dx"]), dxref), TOL))
         # chained pairs (lmn_conv_chain_t): pointwise + shortcut of block A -> expand conv of block B (statistics about a shift, slices,
         # snapshot), folded data gradient of block B -> SE-gradient conv of block A, against the two launches they replace
         for (B, H, W, Cin, E) in [(2, 16, 24, 12, 24), (3, 8, 16, 24, 48), (2, 32, 64, 12, 24), (9, 16, 8, 12, 24), (1, 64, 128, 24, 48)]:
@@ -1201,7 +1435,17 @@ def check_conv_dma1():
                 ok = hip.conv_fwd(srcs, wp2, y1, Cout=Cin, bias=bpw, bias2=bsc, chain=ch, query_chain=True, **kw)
                 rows.append(("conv chain F2 -> F1': accepted" + tag, 0.0 if ok else 1.0, 0.5))
                 if ok:
-                    hip.conv_fwd(srcs, wp2, y1, Cout=Cin, bias=bpw, bias2=bsc, chain=ch, **kw)
+                    _, names = launched(lambda: hip.conv_fwd(srcs, wp2, y1, Cout=Cin, bias=bpw, bias2=bsc, chain=ch, **kw))
+                    rows.append(form_row("conv chain F2 -> F1': ONE launch of the LDS-DMA kernel" + tag, names, ["conv_dma1_kernel<"], ["conv_tile"]))
+                    rows.append(("conv chain F2 -> F1': one launch", float(len(names) - 1), 0.0))
+                    f64 = lambda t: t.double().cpu()
+                    yr_ = (F.conv2d(gelu(nchw(to_nhwc(pre_r))) * f64(gate).view(B, E, 1, 1), f64(wpw).view(Cin, E, 1, 1), f64(bpw))
+                           + F.conv2d(nchw(x), f64(wsc).view(Cin, Cin, 1, 1), f64(bsc)))
+                    zr_ = F.conv2d(yr_, f64(weB).view(E, Cin, 1, 1), f64(beB))
+                    rows.append(("conv chain F2 -> F1': first output vs fp64" + tag, rel(nchw(y1), yr_), TOL))
+                    rows.append(("conv chain F2 -> F1': chained output vs fp64" + tag, rel(nchw(to_nhwc(z1)), zr_), TOL))
+                    zd_ = zr_ - f64(shift).view(1, -1, 1, 1)
+                    rows.append(("conv chain F2 -> F1': statistics vs fp64" + tag, rel(st1_[:4].sum(0), torch.stack([zd_.sum((0, 2, 3)), (zd_ * zd_).sum((0, 2, 3))])), 2e-4))
                     rows.append(("conv chain F2 -> F1': first output" + tag, rel(y1, y0), 1e-7))
                     rows.append(("conv chain F2 -> F1': chained output" + tag, rel(to_nhwc(z1), to_nhwc(z0)), 2e-6))
                     rows.append(("conv chain F2 -> F1': statistics slices + snapshot" + tag, max(rel(st1_[:4].sum(0), st0_[:4].sum(0)) * 1e-2, rel(st1_[4, 0], st0_[4, 0])), 2e-6))
@@ -1220,7 +1464,16 @@ def check_conv_dma1():
                 ok = hip.conv_fwd([dh_r, x, dy], wp3, dx1, Cout=Cin, bias=kb, chain=ch, query_chain=True, **kw)
                 rows.append(("conv chain B2 -> B1': accepted" + tag, 0.0 if ok else 1.0, 0.5))
                 if ok:
-                    hip.conv_fwd([dh_r, x, dy], wp3, dx1, Cout=Cin, bias=kb, chain=ch, **kw)
+                    _, names = launched(lambda: hip.conv_fwd([dh_r, x, dy], wp3, dx1, Cout=Cin, bias=kb, chain=ch, **kw))
+                    rows.append(form_row("conv chain B2 -> B1': ONE launch of the LDS-DMA kernel" + tag, names, ["conv_dma1_kernel<"], ["conv_tile"]))
+                    rows.append(("conv chain B2 -> B1': one launch", float(len(names) - 1), 0.0))
+                    f64 = lambda t: t.double().cpu()
+                    dxr_ = F.conv2d(torch.cat([nchw(to_nhwc(dh_r)), nchw(x), nchw(dy)], 1), torch.cat([f64(wa), f64(wb), f64(wc)], 1).view(Cin, E + 2 * Cin, 1, 1), f64(kb))
+                    ur_ = F.conv2d(dxr_, R(Cin, E, seed=547, scale=0.2).t().reshape(E, Cin, 1, 1))
+                    dsr_ = (ur_ * gelu(nchw(to_nhwc(preA_r)))).sum((2, 3))
+                    rows.append(("conv chain B2 -> B1': first output vs fp64" + tag, rel(nchw(dx1), dxr_), TOL))
+                    rows.append(("conv chain B2 -> B1': chained output vs fp64" + tag, rel(nchw(to_nhwc(u1)), ur_), TOL))
+                    rows.append(("conv chain B2 -> B1': per-image sums vs fp64" + tag, rel(ds1, dsr_), 2e-4))
                     rows.append(("conv chain B2 -> B1': first output" + tag, rel(dx1, dx0), 1e-7))
                     rows.append(("conv chain B2 -> B1': chained output" + tag, rel(to_nhwc(u1), to_nhwc(u0)), 2e-6))
                     rows.append(("conv chain B2 -> B1': per-image sums" + tag, rel(ds1, ds0) * 1e-2, 2e-6))
@@ -1240,12 +1493,18 @@ def check_conv_dma1():
             for mode in (3, 3, 0):
                 hip.conv_dma_config(mode, 1)
                 z, st = hip.rp4(mk(B, H, W, E)), torch.zeros(2, E, device=DEV)
-                hip.conv_fwd([x], hip.conv_pack(we, 1, [Cin]), z, Cout=E, stats=st, stats_mode=hip.STATS_SUM_SQ, **kw)
+                wpe_, wpt_ = hip.conv_pack(we, 1, [Cin]), hip.conv_pack_t(wpw, 1, 0, E, cred=Cin)
+                _, n1 = launched(lambda: hip.conv_fwd([x], wpe_, z, Cout=E, stats=st, stats_mode=hip.STATS_SUM_SQ, **kw))
                 u, ds = hip.rp4(mk(B, H, W, E)), torch.zeros(B, E, device=DEV)
-                hip.conv_fwd([dy], hip.conv_pack_t(wpw, 1, 0, E, cred=Cin), u, Cout=E, transposed=1, epilogue=hip.EP_SE_BWD, aux=pre_r, stats=ds, stats_mode=hip.STATS_EP, **kw)
+                _, n2 = launched(lambda: hip.conv_fwd([dy], wpt_, u, Cout=E, transposed=1, epilogue=hip.EP_SE_BWD, aux=pre_r, stats=ds, stats_mode=hip.STATS_EP, **kw))
+                for names in (n1, n2):
+                    (on if mode else off)("deterministic, mode %d" % mode, names)
+                    rows.append(form_row("conv_dma1 deterministic, mode %d: the slots are folded by det_sum_kernel" % mode, names, ["det_sum_kernel"]))
                 outs.setdefault(mode, []).append((z.clone(), st.clone(), u.clone(), ds.clone()))
             a, b_, c = outs[3][0], outs[3][1], outs[0][0]
             rows.append(("conv_dma1 deterministic: two launches bit-identical", 0.0 if all(torch.equal(p_, q_) for p_, q_ in zip(a, b_)) else 1.0, 0.5))
+            zr_ = F.conv2d(nchw(x), we.double().cpu().view(E, Cin, 1, 1))
+            rows.append(("conv_dma1 deterministic statistics vs fp64", rel(a[1], torch.stack([zr_.sum((0, 2, 3)), (zr_ * zr_).sum((0, 2, 3))])), 2e-4))
             rows.append(("conv_dma1 deterministic vs LDS-tiled kernel", max(rel(a[0], c[0]), rel(a[1], c[1]) * 1e-2, rel(a[2], c[2]), rel(a[3], c[3]) * 1e-2), 2e-6))
         finally:
             hip.set_deterministic(det0)
@@ -1254,6 +1513,7 @@ def check_conv_dma1():
     return rows
 
 
+@owner_check
 def check_bn_tail():
     """BatchNorm(batch stats)+GELU tail: bn_finalize, bnact_fwd, bnact_bwd_stats, bn_bwd_coef, bnact_bwd, colsum."""
     rows = []
@@ -1313,9 +1573,15 @@ def check_bn_tail():
                                                                          Ain=A, dgamma=dg2, dbeta=db2), dz2, hip.ACT_GELU)
         rows.append(("bnact_bwd_fin dz == bn_bwd_coef + bnact_bwd (bitwise) C=%d" % Cn, 0.0 if torch.equal(dz2, dz) else 1.0, 0.5))
         rows.append(("bnact_bwd_fin dgamma / dbeta C=%d" % Cn, max(rel(dg2, g.grad), rel(db2, b.grad)), 2e-4))
+        # eval mode: the running statistics folded into (mean, rstd, A, shift) (lmn_bn_fold)
+        fm, fr, fA, fs = (torch.full((Cn,), float("nan"), device=DEV) for _ in range(4))
+        hip.bn_fold(dev(rm), dev(rv), dev(g), dev(b), 1e-5, fm, fr, fA, fs)
+        r64 = 1.0 / torch.sqrt(rv + 1e-5)
+        rows.append(("bn_fold mean / rstd / A / shift C=%d" % Cn, max(rel(fm, rm), rel(fr, r64), rel(fA, g.detach() * r64), rel(fs, b.detach() - rm * g.detach() * r64)), TOL))
     return rows
 
 
+@owner_check
 def check_conv_bn_epilogues(B=2, H=9, W=8, tag=""):
     """expand_conv (1x1 + batch-stat BN + Hardswish) backward through the conv epilogues BN_BWD1/BN_BWD2,
     and the SE_BWD / DGELU epilogues."""
@@ -1415,6 +1681,36 @@ def check_conv_bn_epilogues(B=2, H=9, W=8, tag=""):
     pl = pre.clone().requires_grad_(True)
     gelu(pl).backward(u_ref)
     rows.append(("conv DGELU" + tag, rel(nchw(o), pl.grad), TOL))
+    if tag == "" and hip._MMA[0] == hip.F32:
+        rows += _dgelu_widths()
+    return rows
+
+
+def _dgelu_widths():
+    """The DGELU epilogue (fc2's data gradient in the transformer MLPs) at every output width of the model, in both storage types:
+    24 / 48 channels (N-split, two / three cout tiles), 96 on a small map and on 5120 pixels (M-split with one / two cout tiles per
+    wave: the smallest map where the tile cost model of conv_fwd.hip picks two), 192.  bf16 storage: bf16-representable operands, so
+    only the stored output is rounded (8e-3, as in check_bf16_storage_rows)."""
+    rows = []
+    for dt in (torch.float32, torch.bfloat16):
+        q = (lambda t: t) if dt == torch.float32 else (lambda t: t.to(torch.bfloat16).double())
+        hip._MMA[0] = hip.F32 if dt == torch.float32 else hip.BF16
+        try:
+            for (B, H, W, Cin, E, kern) in [(1, 6, 8, 12, 24, "conv_tile_kernel<1, 2, 1,"), (1, 6, 8, 24, 48, "conv_tile_kernel<1, 3, 1,"),
+                                            (1, 16, 48, 48, 96, "conv_tileM_kernel<1, 1, 1,"), (1, 64, 80, 48, 96, "conv_tileM_kernel<1, 2, 1,"),
+                                            (1, 6, 8, 96, 192, "conv_tileM_kernel<1, 1, 1,")]:
+                pre, dy = q(R(B, E, H, W, seed=171)), q(R(B, Cin, H, W, seed=172))
+                wpw = q(R(Cin, E, 1, 1, seed=173, scale=0.3))
+                pl = pre.clone().requires_grad_(True)
+                gelu(pl).backward(F.conv_transpose2d(dy, wpw))
+                o = torch.full((B, H, W, E), float("nan"), device=DEV, dtype=dt)
+                _, names = launched(lambda: hip.conv_fwd([dict(view=nhwc(dy).to(dt), flags=0)], hip.conv_pack_t(dev(wpw), 1), o, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=E,
+                                                         transposed=1, epilogue=hip.EP_DGELU, aux=nhwc(pre).to(dt)))
+                tg = " %d->%d %dx%d %s" % (Cin, E, H, W, "bf16" if dt == torch.bfloat16 else "fp32")
+                rows.append(("conv DGELU" + tg, rel(nchw(o), pl.grad), TOL if dt == torch.float32 else 8e-3))
+                rows.append(form_row("conv DGELU" + tg, names, [kern]))
+        finally:
+            hip._MMA[0] = hip.F32
     return rows
 
 
@@ -1429,6 +1725,7 @@ def _dh_ref(z, g, be, dx1):
 
 
 # ------------------------------------------------------------------------------------------------ resampling / layout
+@owner_check
 def check_resample():
     rows = []
     for (B, H, W, Cn) in [(2, 5, 7, 12), (1, 11, 11, 24), (1, 22, 22, 48)]:
@@ -1459,6 +1756,7 @@ def check_resample():
     return rows
 
 
+@owner_check
 def check_layout_utils():
     rows = []
     x = R(2, 3, 6, 5, seed=151)
@@ -1480,6 +1778,10 @@ def check_layout_utils():
     dst = torch.zeros(50, 32, device=DEV)
     hip.copy_slice(hip.V(dev(src), 4, 12), hip.V(dst, 8, 12))
     rows.append(("copy_slice", rel(dst[:, 8:20], src[:, 4:16]) + float(dst[:, :8].abs().max() + dst[:, 20:].abs().max()), 1e-7))
+    for rows_, cols in ((1, 2), (50, 7)):      # (1 x 2: the head's bias into its padded copy, as the step calls it)
+        dst2 = torch.zeros(rows_, 11, device=DEV)
+        hip.copy2d(dev(src).view(-1)[3:], dst2, rows_, cols, 20, 11)
+        rows.append(("copy2d %dx%d" % (rows_, cols), rel(dst2[:, :cols], src[:rows_, 3:3 + cols]) + float(dst2[:, cols:].abs().max()), 1e-7))
     return rows
 
 
@@ -1487,6 +1789,7 @@ ALL_CHECKS = [check_conv_fwd, check_conv_bwd_data, check_conv_wgrad, check_conv_
               check_dw, check_se, check_na, check_gattn, check_ln, check_bn_tail, check_resample, check_layout_utils]
 
 
+@owner_check
 def check_conv_large():
     """Full-size feature maps: many tiles per block, several images per block range, K-split reductions."""
     rows = []
@@ -1508,13 +1811,19 @@ def check_conv_large():
         wd = dev(w)
         out = torch.full((B, Ho, Wo, cout), float("nan"), device=DEV)
         stats = torch.zeros(2, cout, device=DEV)
-        hip.conv_fwd(xs, hip.conv_pack(wd, k, cins), out, B=B, Hin=H, Win=W, Hout=Ho, Wout=Wo, Cout=cout, ksize=k, stride=s,
-                     bias=dev(b), stats=stats, stats_mode=hip.STATS_SUM_SQ)
+        wpk = hip.conv_pack(wd, k, cins)
+        _, names = launched(lambda: hip.conv_fwd(xs, wpk, out, B=B, Hin=H, Win=W, Hout=Ho, Wout=Wo, Cout=cout, ksize=k, stride=s,
+                                                 bias=dev(b), stats=stats, stats_mode=hip.STATS_SUM_SQ))
+        # (at this size the default thresholds of lmn_conv_dma_config hand the single-source stride-1 calls to the LDS-DMA kernels)
+        rows.append(form_row("large conv_fwd " + name, names, [{"1x1 12->24": "conv_dma1_kernel<", "3x3 12->12": "conv_dma3_kernel<"}.get(name, "conv_tile_kernel<9, 2, 2,")]))
         rows.append(("large conv_fwd " + name, rel(nchw(out), y), TOL))
         yd = y.detach()
         rows.append(("large conv_fwd stats " + name, rel(stats, torch.stack([yd.sum((0, 2, 3)), (yd * yd).sum((0, 2, 3))])), 2e-4))
         dW, db = torch.zeros_like(wd), torch.zeros(cout, device=DEV)
-        hip.conv_wgrad(xs, nhwc(dy), dW, db, B=B, Hin=H, Win=W, Hout=Ho, Wout=Wo, Cout=cout, ksize=k, stride=s)
+        _, names = launched(lambda: hip.conv_wgrad(xs, nhwc(dy), dW, db, B=B, Hin=H, Win=W, Hout=Ho, Wout=Wo, Cout=cout, ksize=k, stride=s))
+        rows.append(form_row("large conv_wgrad " + name + ": K-split with the two-stage reduction", names,
+                             [{"1x1 12->24": "wgrad_1x1w_kernel<2, 1,", "3x3 12->12": "wgrad3_kernel<1, 1, 0, false>", "3x3 s2 12->24": "wgrad_lds_kernel<9, 1, 1,"}.get(name, "wgrad3_kernel<2, 2, 0, false>"),
+                              "wgrad_reduce_kernel<"]))
         rows.append(("large conv_wgrad dW " + name, rel(dW, w.grad), 2e-4))
         rows.append(("large conv_wgrad db " + name, rel(db, b.grad), 2e-4))
         if len(cins) == 1:
@@ -1542,6 +1851,7 @@ ALL_CHECKS.append(check_conv_large)
 
 
 # ------------------------------------------------------------------------------------------------ bf16 matrix-core operands
+@owner_check
 def check_conv_bf16():
     """Mixed-precision form of the dense contractions (LMN_BF16: operands rounded to bf16 when staged / packed,
     v_mfma_f32_16x16x16_bf16, fp32 accumulation and epilogues).
@@ -1557,7 +1867,7 @@ def check_conv_bf16():
         cases = [("1x1 12->24", 2, 9, 13, [12], 24, 1, 1), ("1x1 4->24 (padded rgb)", 1, 8, 8, [4], 24, 1, 1),
                  ("1x1 two-src 24+12->12", 2, 6, 7, [24, 12], 12, 1, 1), ("1x1 372->1116", 1, 5, 5, [372], 1116, 1, 1),
                  ("3x3 s1 12->12", 2, 10, 11, [12], 12, 3, 1), ("3x3 s2 12->24", 2, 12, 10, [12], 24, 3, 2),
-                 ("3x3 s1 cat 24+24+24->24", 1, 8, 9, [24, 24, 24], 24, 3, 1), ("3x3 s1 100->112 (chunks)", 1, 6, 6, [100], 112, 3, 1),
+                 ("3x3 s1 cat 24+24+24->24", 1, 8, 9, [24, 24, 24], 24, 3, 1), ("3x3 s1 100->112 (M-split, 7 cout tiles)", 1, 6, 6, [100], 112, 3, 1),
                  ("3x3 s1 48->144 22x22", 2, 22, 22, [48], 144, 3, 1), ("1x1 96->288 44x44", 1, 44, 44, [96], 288, 1, 1)]
         for name, B, H, W, cins, cout, k, s in cases:
             cin = sum(cins)
@@ -1598,6 +1908,7 @@ def check_conv_bf16():
     return rows
 
 
+@owner_check
 def check_bf16_storage_rows():
     """bf16 activation STORAGE in the kernels that are not dense contractions (the conv family has check_conv_bf16): the depthwise
     passes and the neighborhood-attention kernels templated on the storage type.  On bf16-representable inputs the bf16-storage
@@ -1662,9 +1973,136 @@ def check_bf16_storage_rows():
         hip.na_bwd(bf(qkv), rpb, bf(do), g16, r16, heads)
         rows.append(("bf16 storage na_bwd dqkv" + tag, rel(g16.float(), g32), 8e-3))
         rows.append(("bf16 storage na_bwd drpb" + tag, rel(r16, r32), 2e-4))
+    # ---- depthwise passes fed z + (A, shift) (the z-path of check_zpath), bf16 storage: strips with and without the halo columns (57)
+    for (B, H, W, E) in [(2, 20, 19, 24), (1, 12, 57, 8)]:
+        tag = " z-path E=%d %dx%d" % (E, H, W)
+        z32 = nhwcE(R(B, E, H, W, seed=331).to(torch.bfloat16).double())
+        z16 = hip.rp4(bf(z32))
+        wd = [dev(R(E, 1, 5, 5, seed=332, scale=0.2)), dev(R(E, 1, 3, 3, seed=333, scale=0.3)), dev(R(E, 1, 3, 1, seed=334, scale=0.5)), dev(R(E, 1, 1, 3, seed=335, scale=0.5))]
+        zp = dict(A=dev(R(E, seed=336).abs() + 0.5), shift=dev(R(E, seed=337) * 0.3))
+        mk32 = lambda: hip.rp4(torch.full((B, H, W, E), float("nan"), device=DEV))
+        mk16 = lambda: hip.rp4(torch.full((B, H, W, E), float("nan"), device=DEV, dtype=torch.bfloat16))
+        st32, st16 = torch.zeros(4, 2, E, device=DEV), torch.zeros(4, 2, E, device=DEV)
+        hip.dw_stats(z32, *wd, st32, zpre=zp)
+        _, names = launched(lambda: hip.dw_stats(z16, *wd, st16, zpre=zp))
+        rows.append(form_row("bf16 storage dw_stats" + tag, names, ["dw_stats0_kernel<__bf16, true>"]))
+        rows.append(("bf16 storage dw_stats" + tag, rel(st16, st32), 2e-4))
+        keff, beff = dev(R(E, 25, seed=338, scale=0.2)), dev(R(E, seed=339))
+        p32, p16 = mk32(), mk16()
+        g32, g16 = torch.zeros(B, E, device=DEV), torch.zeros(B, E, device=DEV)
+        hip.dw_fwd(z32, p32, g32, keff, beff, zpre=zp)
+        _, names = launched(lambda: hip.dw_fwd(z16, p16, g16, keff, beff, zpre=zp))
+        rows.append(form_row("bf16 storage dw_fwd" + tag, names, ["dw_fwd_kernel<__bf16, true>"]))
+        rows.append(("bf16 storage dw_fwd pre" + tag, rel(p16.float(), p32), 8e-3))
+        rows.append(("bf16 storage dw_fwd gsum" + tag, rel(g16, g32), 2e-4))
+        u = nhwcE(R(B, E, H, W, seed=340).to(torch.bfloat16).double())
+        sg, dm = dev(torch.rand(B, E, dtype=torch.float64) * 0.8 + 0.1), dev(R(B, E, seed=341) * 0.01)
+        d32, d16 = mk32(), mk16()
+        b32, b16_ = torch.zeros(5, E, device=DEV), torch.zeros(5, E, device=DEV)
+        hip.dw_bwd_stats(z32, hip.rp4(p16.float().contiguous()), u, sg, dm, d32, *wd, b32, zpre=zp)
+        _, names = launched(lambda: hip.dw_bwd_stats(z16, p16, hip.rp4(bf(u)), sg, dm, d16, *wd, b16_, zpre=zp))
+        rows.append(form_row("bf16 storage dw_bwd_stats" + tag, names, ["dw_stats1_kernel<__bf16, true>"]))
+        rows.append(("bf16 storage dw_bwd_stats dpre" + tag, rel(d16.float(), d32), 8e-3))
+        rows.append(("bf16 storage dw_bwd_stats sums" + tag, rel(b16_, b32), 5e-3))
+        N = B * H * W
+        bst, bm, br_, bA = dev(R(5, E, seed=342)), dev(R(4, E, seed=343) * 0.1), dev(R(4, E, seed=344).abs() + 0.5), dev(R(4, E, seed=345).abs() + 0.3)
+        dq = hip.rp4(d16.float().contiguous())
+        outs = []
+        for zin, din, mk in ((z32, dq, mk32), (z16, d16, mk16)):
+            dh, hst = mk(), torch.zeros(2, E, device=DEV)
+            gw = [torch.zeros_like(w) for w in wd]
+            dgs, dbs = [torch.zeros(E, device=DEV) for _ in range(4)], [torch.zeros(E, device=DEV) for _ in range(4)]
+            _, names = launched(lambda: hip.dw_bwd_bn(zin, din, dh, *wd, bst, bm, br_, bA, N, True, dgs, dbs, *gw, zpre=zp, hstats=hst))
+            outs.append((dh.float(), hst, gw, names))
+        halo = "true" if -(-W // 60) < -(-W // 56) else "false"
+        rows.append(form_row("bf16 storage dw_bwd_bn" + tag, outs[1][3], ["dw_bwd_kernel<__bf16, 0, %s, true, 2>" % halo]))
+        rows.append(("bf16 storage dw_bwd_bn dh" + tag, rel(outs[1][0], outs[0][0]), 8e-3))
+        rows.append(("bf16 storage dw_bwd_bn sums (dh, dh z)" + tag, rel(outs[1][1], outs[0][1]), 5e-3))
+        for i, nm in enumerate(("w5", "w3", "wv", "wh")):
+            rows.append(("bf16 storage dw_bwd_bn d%s%s" % (nm, tag), rel(outs[1][2][i], outs[0][2][i]), 2e-4))
+    # ---- the row kernels of the step that are templated on the storage type: each on bf16-representable inputs against its own
+    #      fp32-storage launch (outputs rounded to bf16: 8e-3; channel sums and parameter gradients stay fp32: 2e-4)
+    r16 = lambda *sh, seed: R(*sh, seed=seed).to(torch.bfloat16).double()
+    x = nhwc(r16(2, 48, 8, 12, seed=351))
+    for f in (2, 4):
+        o32, o16 = torch.zeros(2, 8 // f, 12 // f, 56, device=DEV), torch.zeros(2, 8 // f, 12 // f, 56, device=DEV, dtype=torch.bfloat16)
+        hip.avgpool_fwd(x, hip.V(o32, 4, 48), f)
+        hip.avgpool_fwd(bf(x), hip.V(o16, 4, 48), f)
+        rows.append(("bf16 storage avgpool_fwd f=%d" % f, rel(o16.float(), o32), 8e-3))
+        dyb = torch.zeros(2, 8 // f, 12 // f, 56, device=DEV)
+        dyb[..., 4:52] = nhwc(r16(2, 48, 8 // f, 12 // f, seed=352))
+        base = nhwc(r16(2, 48, 8, 12, seed=353))
+        a32, a16 = base.clone(), bf(base)
+        hip.avgpool_bwd(hip.V(dyb, 4, 48), a32, f, True)
+        hip.avgpool_bwd(hip.V(bf(dyb), 4, 48), a16, f, True)
+        rows.append(("bf16 storage avgpool_bwd f=%d accumulate" % f, rel(a16.float(), a32), 8e-3))
+    dy = nhwc(r16(2, 48, 16, 24, seed=354))
+    u32, u16 = torch.full((2, 8, 12, 48), float("nan"), device=DEV), torch.full((2, 8, 12, 48), float("nan"), device=DEV, dtype=torch.bfloat16)
+    hip.up2_bwd(dy, u32)
+    hip.up2_bwd(bf(dy), u16)
+    rows.append(("bf16 storage up2_bwd", rel(u16.float(), u32), 8e-3))
+    xc = dev(r16(2, 3, 6, 5, seed=355))
+    y32, y16 = torch.full((2, 6, 5, 4), float("nan"), device=DEV), torch.full((2, 6, 5, 4), float("nan"), device=DEV, dtype=torch.bfloat16)
+    hip.nchw_to_nhwc(xc, y32)
+    hip.nchw_to_nhwc(xc, y16)
+    rows.append(("bf16 storage nchw_to_nhwc (pad to 4)", 0.0 if torch.equal(y16.float(), y32) else 1.0, 0.5))
+    c32, c16 = torch.full((2, 2, 6, 5), float("nan"), device=DEV), torch.full((2, 2, 6, 5), float("nan"), device=DEV)
+    hip.nhwc_to_nchw(y32, c32)
+    hip.nhwc_to_nchw(y16, c16)
+    rows.append(("bf16 storage nhwc_to_nchw (first 2 ch)", 0.0 if torch.equal(c16, c32) else 1.0, 0.5))
+    for Cn, n in ((96, 203), (372, 77)):
+        xl, dyl, drl = dev(r16(n, Cn, seed=356)), dev(r16(n, Cn, seed=357)), dev(r16(n, Cn, seed=358))
+        gl = dev(R(Cn, seed=359).abs() + 0.5)
+        outs = []
+        for cv, dt_ in ((lambda t: t, torch.float32), (bf, torch.bfloat16)):
+            dxl, dg, db = torch.full((n, Cn), float("nan"), device=DEV, dtype=dt_), torch.zeros(Cn, device=DEV), torch.zeros(Cn, device=DEV)
+            hip.ln_bwd(cv(xl), gl, cv(dyl), cv(drl), dxl, dg, db)
+            outs.append((dxl.float(), dg, db))
+        rows.append(("bf16 storage ln_bwd dx(+res) C=%d" % Cn, rel(outs[1][0], outs[0][0]), 8e-3))
+        rows.append(("bf16 storage ln_bwd dgamma / dbeta C=%d" % Cn, max(rel(outs[1][1], outs[0][1]), rel(outs[1][2], outs[0][2])), 2e-4))
+    # BatchNorm + GELU tail of the skip fusers (bnact_fwd_fin, bnact_bwd_stats = chan_kernel<0>, bnact_bwd_fin = chan_kernel<1>)
+    Cn, n = 48, 403
+    zt, dyt = dev(r16(n, Cn, seed=361) * 1.3 + 0.2), dev(r16(n, Cn, seed=362))
+    zt = bf(zt).float()          # (the scaled values, made bf16-representable again)
+    gt, bt = dev(R(Cn, seed=363).abs() + 0.5), dev(R(Cn, seed=364))
+    sums = torch.zeros(2, 2, Cn, device=DEV)
+    hip.colsum(zt, sums[0, 0])
+    hip.colsum((zt * zt).contiguous(), sums[0, 1])
+    outs = []
+    for cv, dt_ in ((lambda t: t, torch.float32), (bf, torch.bfloat16)):
+        mean, rstd, A, shift = (torch.full((Cn,), float("nan"), device=DEV) for _ in range(4))
+        rm, rv = torch.zeros(Cn, device=DEV), torch.ones(Cn, device=DEV)
+        yt = torch.full((n, Cn), float("nan"), device=DEV, dtype=dt_)
+        hip.bnact_fwd_fin(cv(zt), dict(mode=hip.FIN_BN, sums=sums, nrep=1, count=n, gamma=gt, beta=bt, eps=1e-5, momentum=0.1, about=sums[1, 0], mean=mean, rstd=rstd, A=A,
+                                       shift=shift, rmean=rm, rvar=rv), yt, hip.ACT_GELU)
+        bst = torch.zeros(2, Cn, device=DEV)
+        hip.bnact_bwd_stats(cv(zt), cv(dyt), mean, rstd, gt, bt, bst, hip.ACT_GELU)
+        dg, db = torch.zeros(Cn, device=DEV), torch.zeros(Cn, device=DEV)
+        dz = torch.full((n, Cn), float("nan"), device=DEV, dtype=dt_)
+        hip.bnact_bwd_fin(cv(zt), cv(dyt), mean, rstd, gt, bt, dict(mode=hip.FIN_BN_BWD, sums=bst, nrep=1, count=n, batch_stats=1, Ain=A, dgamma=dg, dbeta=db), dz, hip.ACT_GELU)
+        outs.append((yt.float(), bst, dz.float(), dg, db))
+    rows.append(("bf16 storage bnact_fwd_fin y", rel(outs[1][0], outs[0][0]), 8e-3))
+    rows.append(("bf16 storage bnact_bwd_stats sums", rel(outs[1][1], outs[0][1]), 2e-4))
+    rows.append(("bf16 storage bnact_bwd_fin dz", rel(outs[1][2], outs[0][2]), 8e-3))
+    rows.append(("bf16 storage bnact_bwd_fin dgamma / dbeta", max(rel(outs[1][3], outs[0][3]), rel(outs[1][4], outs[0][4])), 2e-4))
+    # global attention of the bottleneck (MFMA kernels), hd = 31
+    Bq, Nq, heads, hd = 1, 130, 12, 31
+    qkv, do = dev(r16(Bq, Nq, 3 * heads * hd, seed=371) * 0.7), dev(r16(Bq, Nq, heads * hd, seed=372))
+    qkv = bf(qkv).float()
+    outs = []
+    for cv, dt_ in ((lambda t: t, torch.float32), (bf, torch.bfloat16)):
+        out, lse = torch.full((Bq, Nq, heads * hd), float("nan"), device=DEV, dtype=dt_), torch.empty(Bq, heads, Nq, device=DEV)
+        hip.gattn_fwd(cv(qkv), out, lse, heads)
+        dqkv, delta = torch.full((Bq, Nq, 3 * heads * hd), float("nan"), device=DEV, dtype=dt_), torch.empty(Bq, heads, Nq, device=DEV)
+        hip.gattn_bwd(cv(qkv), out, cv(do), lse, dqkv, delta, heads)
+        outs.append((out.float(), dqkv.float()))
+    # (the bf16-storage instances feed the matrix cores bf16 operands -- q, k, v and the probabilities: 1e-2, the rounding tolerance of check_conv_bf16)
+    rows.append(("bf16 storage gattn_fwd", rel(outs[1][0], outs[0][0]), 1e-2))
+    rows.append(("bf16 storage gattn_bwd dqkv", rel(outs[1][1], outs[0][1]), 1e-2))
     return rows
 
 
+@owner_check
 def check_bn_shifted_stats():
     """Batch variance when |mean| >> std (a large conv bias: |mean| / std ~ 1e3).  The conv epilogue sums about the
     BatchNorm's running mean (lmn_conv_fwd p4 / lmn_bn_finalize `about`), so E[d^2] - E[d]^2 does not cancel the squared
@@ -1699,3 +2137,79 @@ ALL_CHECKS.append(check_conv_bf16)
 ALL_CHECKS.append(check_ln_linear)
 ALL_CHECKS.append(check_conv_up2)
 ALL_CHECKS.append(check_bn_shifted_stats)
+
+
+@owner_check
+def check_conv3_storage():
+    """The 3x3 conv family -- forward (+ SUM_SQ statistics, bilinear x2 on load, residual), data gradient (stride 1 and the stride-2
+    transposed form), weight gradient -- at the channel pairs of every level of the model, in fp32 storage and in bf16 STORAGE (bf16
+    activations, bf16 MFMA operands: the `PM = 2` instances, which check_conv_bf16 -- fp32 storage -- does not select), against fp64
+    F.conv2d / F.interpolate / autograd.  The bf16 runs draw bf16-representable activations and weights: every product is exact, fp32
+    accumulation, so stored outputs carry their rounding to bf16 alone (8e-3, as in check_bf16_storage_rows), statistics and weight
+    gradients stay fp32 (2e-4); with the bilinear x2 on load the sampled operand is rounded as well (1e-2, the rounding tolerance of
+    check_conv_bf16).  The LDS-DMA forms are switched off: their fp32 instances belong to check_conv_dma3 / check_conv_dmaM.  Maps:
+    the smallest that select the step's instances -- 40 wide for the kernels that want 32-wide tiles (wgrad3), 44 x 44 for the M-split
+    kernel with two cout tiles per wave at Cout = 96."""
+    rows = []
+    f32, b16 = torch.float32, torch.bfloat16
+    prev = hip.conv_dma_config(0, 1)
+    mma0 = hip._MMA[0]
+    try:
+        for dt in (f32, b16):
+            hip._MMA[0] = hip.F32 if dt == f32 else hip.BF16
+            q = (lambda t: t) if dt == f32 else (lambda t: t.to(b16).double())
+            to, tsum = (TOL, 2e-4) if dt == f32 else (8e-3, 2e-4)
+            for (B, H, W, Cin, Cout, st, up, stats) in [
+                    (1, 9, 40, 12, 12, 1, 0, 0), (1, 9, 40, 24, 12, 1, 0, 1), (1, 18, 40, 12, 24, 2, 0, 0), (1, 9, 20, 48, 24, 1, 0, 0), (1, 9, 20, 72, 24, 1, 0, 1),
+                    (1, 18, 40, 24, 48, 2, 0, 0), (1, 9, 20, 48, 48, 1, 0, 0), (2, 16, 24, 144, 48, 1, 0, 1), (1, 18, 36, 48, 96, 2, 0, 0), (1, 44, 44, 96, 96, 1, 0, 0),
+                    (1, 44, 44, 192, 96, 1, 0, 1), (1, 8, 8, 96, 192, 1, 0, 0),
+                    (1, 9, 20, 24, 12, 1, 1, 0), (1, 9, 20, 48, 24, 1, 1, 0), (1, 10, 12, 96, 48, 1, 1, 0), (1, 22, 22, 192, 96, 1, 1, 0)]:   # (up: H x W is the source map)
+                Hi, Wi = (2 * H, 2 * W) if up else (H, W)
+                tag = " %dx%dx%d %d->%d s%d%s %s" % (B, Hi, Wi, Cin, Cout, st, " up2" if up else "", "bf16" if dt == b16 else "fp32")
+                xr = q(R(B, Cin, H, W, seed=601)).requires_grad_(True)
+                wr = q(R(Cout, Cin, 3, 3, seed=602, scale=1.0 / math.sqrt(9 * Cin))).requires_grad_(True)
+                br = R(Cout, seed=603).requires_grad_(True)
+                xin = F.interpolate(xr, scale_factor=2, mode="bilinear", align_corners=True) if up else xr
+                z = F.conv2d(xin, wr, br, stride=st, padding=1)
+                Ho, Wo = z.shape[2:]
+                resr, dyr = q(R(B, Cout, Ho, Wo, seed=604)), q(R(B, Cout, Ho, Wo, seed=605))
+                z.backward(dyr)
+                t_out = max(to, 1e-2) if up and dt == b16 else to
+                xd = nhwc(xr.detach()).to(dt)
+                src = dict(view=xd, flags=hip.SRC_UP2) if up else xd
+                wp = hip.conv_pack(dev(wr.detach()), 3, [Cin])
+                kw = dict(B=B, Hin=Hi, Win=Wi, Hout=Ho, Wout=Wo, Cout=Cout, ksize=3, stride=st)
+                y = torch.full((B, Ho, Wo, Cout), float("nan"), device=DEV, dtype=dt)
+                if stats:      # as the skip fusers call it: sums about a shift, one slice, the shift's snapshot behind it
+                    shift = R(Cout, seed=606) * 0.3
+                    sb = torch.zeros(2, 2, Cout, device=DEV)
+                    hip.conv_fwd([src], wp, y, bias=dev(br.detach()), stats=sb, stats_mode=hip.STATS_SUM_SQ, stats_rep=1, stats_snap=True, p=(None, None, None, None, dev(shift)), **kw)
+                    zd = z.detach() - shift.view(1, -1, 1, 1)
+                    rows.append(("conv3 fwd" + tag, rel(nchw(y), z), t_out))
+                    rows.append(("conv3 SUM_SQ statistics about a shift" + tag, rel(sb[0], torch.stack([zd.sum((0, 2, 3)), (zd * zd).sum((0, 2, 3))])), tsum))
+                    rows.append(("conv3 statistics: shift snapshot" + tag, rel(sb[1, 0], shift), 1e-7))
+                else:
+                    hip.conv_fwd([src], wp, y, bias=dev(br.detach()), residual=nhwc(resr).to(dt), **kw)
+                    rows.append(("conv3 fwd (+ residual)" + tag, rel(nchw(y), z.detach() + resr), t_out))
+                if not up:     # data gradient: the transposed operator (stride 2: the four-class form), accumulating into a residual
+                    accr = q(R(B, Cin, H, W, seed=607))
+                    dx = torch.full((B, H, W, Cin), float("nan"), device=DEV, dtype=dt)
+                    hip.conv_fwd([nhwc(dyr).to(dt)], hip.conv_pack_t(dev(wr.detach()), 3), dx, B=B, Hin=Ho, Win=Wo, Hout=H, Wout=W, Cout=Cin, ksize=3, stride=st, transposed=1,
+                                 residual=nhwc(accr).to(dt))
+                    rows.append(("conv3 data gradient (+ accumulate)" + tag, rel(nchw(dx), xr.grad + accr), to))
+                # weight gradient (with the same sampling on load where the library takes it: upsampled maps >= 32 wide)
+                dW, db = torch.zeros(Cout, Cin, 3, 3, device=DEV), torch.zeros(Cout, device=DEV)
+                dyd = nhwc(dyr).to(dt)
+                if up and hip.conv_wgrad_up2_ok(xd, dyd, B=B, Hin=Hi, Win=Wi, Cout=Cout):
+                    hip.conv_wgrad([src], dyd, dW, db, **kw)
+                    rows.append(("conv3 weight gradient (up2 on load)" + tag, max(rel(dW, wr.grad), rel(db, br.grad)), tsum if dt == f32 else 1e-2))
+                elif not up:
+                    hip.conv_wgrad([xd], dyd, dW, db, **kw)
+                    rows.append(("conv3 weight gradient" + tag, max(rel(dW, wr.grad), rel(db, br.grad)), tsum))
+    finally:
+        hip._MMA[0] = mma0
+        hip.conv_dma_config(prev if prev >= 0 else 7, 512)
+    return rows
+
+
+ALL_CHECKS.append(check_conv3_storage)

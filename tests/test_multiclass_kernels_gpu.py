@@ -74,6 +74,28 @@ def test_general_c_loss_vs_f64(C):
             assert err < 1e-4 * float(expect.abs().max()), (C, eps, gs, err)
 
 
+def test_two_class_loss_vs_f64_owns_the_step_kernels():
+    """C = 2, the class count of the training step and of bench.py: the kernels templated on C against the same float64 restatement,
+    at the tolerances of the general-C test above, and (tests/kernel_forms.py) proof that this test launches the instances it owns."""
+    from kernel_forms import launched, owned_by
+    C, B, H, W = 2, 2, 37, 45
+    for eps in (0.0, 1e-3):
+        key = "mc_k/2/%g" % eps
+        lg = (det_input((B, C, H, W), key + "/lg") * 2.5).cuda()
+        y = _labels(B, H, W, C, key + "/y").cuda()
+        wce = torch.from_numpy(0.25 + 2 * uniform(key + "/wce", C)).float().cuda()
+        wdice = torch.from_numpy(0.25 + 2 * uniform(key + "/wdice", C)).float().cuda()
+        l64 = lg.double().requires_grad_(True)
+        ref = _loss_f64(l64, y, wce.double(), wdice.double(), eps)
+        ref.backward()
+        gst = torch.tensor([0.37], device="cuda")
+        (loss, d), names = launched(lambda: _run_loss(lg, y, wce, wdice, eps, gst))
+        assert owned_by("tests/test_multiclass_kernels_gpu.py::test_two_class_loss_vs_f64_owns_the_step_kernels") <= names, names
+        assert abs(float(loss) - float(ref)) < 1e-5 * abs(float(ref)), (eps, float(loss), float(ref))
+        expect = l64.grad * 0.37
+        assert float((d.double() - expect).abs().max()) < 1e-4 * float(expect.abs().max()), eps
+
+
 @pytest.mark.parametrize("tag", ["k9", "k33"])
 def test_general_c_loss_vs_reference_golden(tag):
     """SegLoss at C = 9 / 33 with the golden's class weights against the reference DiceLoss + CrossEntropyLoss (float64)."""

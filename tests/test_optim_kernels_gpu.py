@@ -178,3 +178,24 @@ def test_one_step_against_the_restatement(n, kind):
     if bool(live.any()):
         for k, ref in (("p", st.p), ("m", st.m), ("v", st.v)):
             assert rel_err(d[k].cpu()[live], ref[live]) < 2e-6, k
+
+
+@pytest.mark.parametrize("n", [4, 4 * 256 * 3 + 4])
+def test_plain_adamw_step_vs_f64_owns_the_step_kernel(n):
+    """lmn_adamw_step -- the one launch FusedAdamW issues per step when no group table, clipping or EMA is asked for -- against
+    torch.optim.AdamW's update written out in float64, and (tests/kernel_forms.py) proof that this test launches the instance it owns."""
+    from kernel_forms import launched, owned_by
+    from lm_net_amd import hip
+    lr, b1, b2, eps, wd, step = 1e-2, 0.9, 0.99, 1e-8, 0.1, 3
+    p, g, m, v = R.seeded(n, 11), R.seeded(n, 12), R.seeded(n, 13, 0.1), R.seeded(n, 14).abs()
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    p64, g64 = p.double() * (1.0 - lr * wd), g.double()
+    m64 = b1 * m.double() + (1.0 - b1) * g64
+    v64 = b2 * v.double() + (1.0 - b2) * g64 * g64
+    p64 = p64 - (lr / bc1) * m64 / (torch.sqrt(v64) / bc2 ** 0.5 + eps)
+    d = [t.to(DEV) for t in (p, g, m, v)]
+    _, names = launched(lambda: hip.adamw_step(*d, lr, b1, b2, eps, wd, bc1, bc2))
+    assert owned_by("tests/test_optim_kernels_gpu.py::test_plain_adamw_step_vs_f64_owns_the_step_kernel") <= names, names
+    for got, ref, what in ((d[0], p64, "p"), (d[2], m64, "m"), (d[3], v64, "v")):
+        assert rel_err(got, ref) < 2e-6, (what, n, rel_err(got, ref))      # (the bound of test_one_step_against_the_restatement)
+    assert torch.equal(d[1].cpu(), g)
