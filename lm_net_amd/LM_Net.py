@@ -291,6 +291,8 @@ class LM_Net(nn.Module):
         params = self._param_list()
         if params and not params[0].is_cuda:
             raise RuntimeError("lm_net_amd.LM_Net: parameters are on %s; call model.to('cuda')" % params[0].device)
+        if self._plans or self._graphs:
+            self._follow_param_storage(params)
         x = x.float().contiguous() if x.dtype != torch.float32 or not x.is_contiguous() else x
         self._engine.mma, self._engine.act_dtype = self._precision()
         self._save_tape = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
@@ -344,7 +346,8 @@ class LM_Net(nn.Module):
         first two passes of a (shape, mode) run launch by launch and size the arena, the third is recorded while it runs,
         later ones are `lmn_plan_run` replays -- same kernels, same four HIP streams and cross-stream events as the
         host-launched schedule (unlike a hipGraph capture, which cannot carry the stream forks), ~2 ms of host time per
-        step instead of 16-20.  Contract while enabled: fixed parameter storage; the returned gradients are views of one
+        step instead of 16-20.  Contract while enabled: fixed parameter storage (a parameter that moved drops the plans: its shapes warm
+        up and are recorded again, _follow_param_storage); the returned gradients are views of one
         static buffer (as `zero_grad(set_to_none=True)` expects; a `.grad` that still aliases it is accumulated into
         correctly); data-parallel buckets are reported between plan segments; dropout draws from a device-side counter.
         direct_grads=True: the backward node writes `.grad` itself instead of returning ~510 gradients to the autograd engine
@@ -508,7 +511,7 @@ class LM_Net(nn.Module):
         (and eval / no-grad forwards as one replay, see _infer_replay):
         the step at batch 8 / 352x352 carries ~8 ms of per-launch cost.  The first two steps of a shape run eagerly
         (warm-up: workspaces, pack plans, allocator), the third is captured.  Contract while enabled: fixed parameter
-        storage, `zero_grad(set_to_none=True)` semantics (returned gradients are views of one static buffer; they
+        storage (a parameter that moved drops the graphs, _follow_param_storage), `zero_grad(set_to_none=True)` semantics (returned gradients are views of one static buffer; they
         are cloned if a `.grad` still aliases it), data-parallel gradients are all-reduced after the backward
         replay instead of bucket by bucket inside it.  Dropout draws a new mask per replay from a device-side
         counter."""
@@ -591,6 +594,19 @@ class LM_Net(nn.Module):
         if c is None:
             c = self.__dict__["_param_cache"] = list(self.parameters())
         return c
+
+    def _follow_param_storage(self, params):
+        """Recorded plans and captured graphs carry the parameters' ADDRESSES.  When one of them changed since the last pass
+        (`p.data = ...`, `model.to()`, a flattening optimizer built after the first passes) they are dropped: the shape warms up and
+        is recorded again on the new storage instead of computing with the old one.  ~30 us per pass, only while a plan
+        or a graph exists."""
+        ptrs = list(map(torch.Tensor.data_ptr, params))
+        old = self.__dict__.get("_param_ptrs")
+        if ptrs != old:
+            self.__dict__["_param_ptrs"] = ptrs
+            if old is not None:
+                self._plans = {}
+                self._graphs = {}
 
     # ------------------------------------------------------------------ forward schedule (core/LM_Net.py:95-123)
     def _step_bookkeeping(self):
