@@ -10,12 +10,13 @@ best threshold of any thresholded metric from on-device score histograms),
 ``lm_net_amd.optim.FusedAdamW`` (one-launch AdamW; parameter groups, gradient clipping, the GradScaler skip and an EMA of the weights
 without a host decision; ``lm_net_amd.optim.decay_groups``), ``lm_net_amd.metrics.ConfusionMeter`` (on-device Dice / IoU),
 ``lm_net_amd.metrics.SurfaceDistanceMeter`` (on-device HD / HD95 / ASSD / RVD),
+``lm_net_amd.metrics.VolumeSurfaceMeter`` (per-case 3D Dice / HD / HD95 / ASSD / RVD of a label volume with integer voxel pitches),
 ``lm_net_amd.post.DevicePostprocess`` (on-device arg-max, connected-component cleaning, resize back to the frame, overlay),
 ``lm_net_amd.infer.TiledPredictor`` (frames of any size: overlapping tiles, mirrored copies and one blend launch),
 ``lm_net_amd.ddp.DistributedLMNet`` (bucketed RCCL gradient all-reduce).
 """
 from .LM_Net import LM_Net  # noqa: F401
 from .loss import FocalLoss, SegLoss, SigmoidSegLoss  # noqa: F401
-from .metrics import CurveMeter, ImageStatsMeter, SigmoidStatsMeter  # noqa: F401
+from .metrics import CurveMeter, ImageStatsMeter, SigmoidStatsMeter, VolumeSurfaceMeter  # noqa: F401
 
-__all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter"]
+__all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter", "VolumeSurfaceMeter"]

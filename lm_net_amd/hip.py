@@ -302,6 +302,14 @@ SYMBOLS_TILES = ["lmn_sizeof_tile_param", "lmn_tile_gather", "lmn_tile_blend"]
 # tests/test_guard_curves_gpu.py.
 SYMBOLS_CURVES = ["lmn_curve_workspace", "lmn_curve_hist"]
 
+# include/volume/lmnet_volume.h: per-case 3D surface distances and overlap (lm_net_amd.metrics.VolumeSurfaceMeter).  A list of its own
+# for the same reason, and no struct; tests/test_volume_cpu.py checks it against the header and ties the two entries that write device
+# memory to tests/test_guard_volume_gpu.py.
+SYMBOLS_VOLUME = ["lmn_volume_workspace", "lmn_volume_labels", "lmn_volume_dist"]
+VOLUME_MAX_SIDE = 1024       # LMN_VOLUME_* of the header
+VOLUME_NSTAT_I = 9
+VOLUME_NSTAT_F = 2
+
 _lib = None
 
 
@@ -315,7 +323,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -326,6 +334,7 @@ def load():
     lib.lmn_oneof_workspace.restype = C.c_int64
     lib.lmn_optim_workspace.restype = C.c_int64
     lib.lmn_curve_workspace.restype = C.c_int64
+    lib.lmn_volume_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1329,6 +1338,65 @@ def surface_dist(pred, target, n_classes, classes, workspace, stats_i, stats_f):
     _check(load().lmn_surface_dist(_p(logits), _pl(labels), _pl(target), B, int(n_classes), H, W, ids, nk,
                                    C.c_void_p(workspace.data_ptr()), _i64(workspace.numel()), C.c_void_p(stats_i.data_ptr()),
                                    C.c_void_p(stats_f.data_ptr()), _stream()), "surface_dist")
+
+
+def volume_workspace(D, H, W, nk):
+    """Bytes of scratch lmn_volume_dist needs for nk classes of a D x H x W volume, exactly (host arithmetic, no GPU)."""
+    n = int(load().lmn_volume_workspace(int(D), int(H), int(W), int(nk)))
+    if n < 0:
+        raise ValueError("lm_net_amd.volume_workspace: " + load().lmn_last_error().decode())
+    return n
+
+
+def volume_span(shape, spacing):
+    """(kz (D-1))^2 + (ky (H-1))^2 + (kx (W-1))^2 of a volume [D, H, W] with integer pitches: the largest squared distance, which
+    lmn_volume_dist requires below 2^31 (Python integers: no overflow)."""
+    return sum((int(k) * (int(n) - 1)) ** 2 for k, n in zip(spacing, shape))
+
+
+def _volume_case(lab_pred, lab_target, what):
+    if lab_pred.dim() != 3 or lab_pred.shape != lab_target.shape:
+        raise ValueError("lm_net_amd.%s: case buffers %s, %s: two uint8 volumes [D, H, W] of one shape required"
+                         % (what, tuple(lab_pred.shape), tuple(lab_target.shape)))
+    return tuple(int(d) for d in lab_pred.shape)
+
+
+def volume_labels(pred, target, n_classes, lab_pred, lab_target, z0=0):
+    """Narrow n slices of a case to uint8 class ids (255: no class) into slices [z0, z0 + n) of the case buffers lab_pred / lab_target
+    (uint8 [D_cap, H, W] device tensors; lmn_volume_labels).  pred: fp32 logits [n, C, H, W] or int64 labels [n, H, W]; target int64
+    [n, H, W]."""
+    cap, H, W = _volume_case(lab_pred, lab_target, "volume_labels")
+    logits = pred if pred.dim() == 4 else None
+    labels = pred if pred.dim() == 3 else None
+    n = int(target.shape[0])
+    if (logits is None) == (labels is None) or target.dim() != 3 or tuple(pred.shape[-2:]) != (H, W) or tuple(target.shape[1:]) != (H, W) \
+            or pred.shape[0] != n:
+        raise ValueError("lm_net_amd.volume_labels: pred %s, target %s do not match case buffers of %dx%d slices"
+                         % (tuple(pred.shape), tuple(target.shape), H, W))
+    if logits is not None and (logits.shape[1] != n_classes or not logits.is_contiguous()):
+        raise ValueError("lm_net_amd.volume_labels: contiguous logits with %d channels required" % n_classes)
+    if n < 1 or z0 < 0 or z0 + n > cap:
+        raise ValueError("lm_net_amd.volume_labels: slices [%d, %d) outside the case buffer of %d slices" % (z0, z0 + n, cap))
+    _check(load().lmn_volume_labels(_p(logits), _pl(labels), _pl(target), n, int(n_classes), H, W, _raw(lab_pred, torch.uint8, "volume_labels"),
+                                    _raw(lab_target, torch.uint8, "volume_labels"), cap, int(z0), _stream()), "volume_labels")
+
+
+def volume_dist(lab_pred, lab_target, n_classes, classes, spacing, workspace, stats_i, stats_f):
+    """Raw 3D surface-distance and overlap statistics of one case (lmn_volume_dist).  lab_pred / lab_target: uint8 [D, H, W] device
+    tensors as volume_labels writes them; classes: the class ids scored (host list); spacing: integer pitches (kz, ky, kx); workspace:
+    uint8 device tensor of at least volume_workspace(D, H, W, len(classes)) bytes; stats_i int64 [nk, 9] and stats_f float64 [nk, 2]
+    device tensors."""
+    D, H, W = _volume_case(lab_pred, lab_target, "volume_dist")
+    nk = len(classes)
+    if stats_i.numel() != nk * VOLUME_NSTAT_I or stats_f.numel() != nk * VOLUME_NSTAT_F:
+        raise ValueError("lm_net_amd.volume_dist: statistics buffers do not match %d classes" % nk)
+    if len(spacing) != 3 or any(int(k) != k or k < 1 for k in spacing):
+        raise ValueError("lm_net_amd.volume_dist: spacing %r: three positive integers (kz, ky, kx) required" % (spacing,))
+    ids = (C.c_int32 * nk)(*[int(k) for k in classes])
+    _check(load().lmn_volume_dist(_raw(lab_pred, torch.uint8, "volume_dist"), _raw(lab_target, torch.uint8, "volume_dist"), D, H, W,
+                                  int(n_classes), ids, nk, int(spacing[0]), int(spacing[1]), int(spacing[2]),
+                                  _raw(workspace, torch.uint8, "volume_dist"), _i64(workspace.numel()), _raw(stats_i, torch.int64, "volume_dist"),
+                                  _raw(stats_f, torch.float64, "volume_dist"), _stream()), "volume_dist")
 
 
 def _raw(t, dt, what):

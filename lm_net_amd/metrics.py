@@ -21,6 +21,10 @@ confusion matrix cannot.
 a threshold table (``lmn_curve_hist``, integer counting on the device), from which ROC, precision-recall, AUROC (the ``AUROC`` of the
 reference's torchmetrics collection, ``train.py:29``), average precision and the best threshold of any thresholded metric follow in
 float64 on the host.
+
+``VolumeSurfaceMeter`` scores a whole 3D case: Dice, Jaccard, HD, HD95, ASSD and RVD of the ``[D, H, W]`` label volume with integer
+voxel pitches (``medpy.metric.binary`` ``dc`` / ``jc`` / ``hd`` / ``hd95`` / ``assd`` / ``ravd`` per case), from the eleven exact raw
+statistics per (case, class) of ``lmn_volume_dist``; slices arrive batch by batch from a 2D validation loop (``push`` / ``close_case``).
 """
 import warnings
 
@@ -576,6 +580,167 @@ def surface_metrics(si, sf, classes, spacing=1.0):
            "per_sample": {"hd": hd, "hd95": hd95, "assd": assd, "rvd": rvd}}
     for k in ("hd", "hd95", "assd"):
         out["mean_" + k] = mean_all(out[k])
+    return out
+
+
+class VolumeSurfaceMeter:
+    """Per-case 3D Dice, Jaccard, HD, HD95, ASSD and RVD per class of a label VOLUME, accumulated on the device: medpy.metric.binary
+    dc, jc, hd, hd95, assd and ravd of the whole [D, H, W] case, the numbers of a CT results table.  (SurfaceDistanceMeter scores every
+    slice as its own 2D sample; the mean of per-slice HD95 is not the HD95 of the case.)
+
+    For one case and class k, P = (pred == k), T = (target == k).  The border of a mask is its voxels with a 6-neighbour outside it
+    (outside the volume counts as outside: scipy's binary_erosion with generate_binary_structure(3, 1) and border_value=0, which medpy
+    uses; in a one-slice volume every mask voxel is a border voxel).  D2(A -> B) is the squared distance of every border voxel of A to
+    the nearest border voxel of B.  ``spacing = (kz, ky, kx)``: positive INTEGERS, the voxel pitch along each axis in steps of ``unit``
+    (a positive float, e.g. millimetres): 3.0 x 0.78 x 0.78 mm is ``spacing=(50, 13, 13), unit=0.06``.  Integer pitches keep every
+    squared distance d2 = (kz dz)^2 + (ky dy)^2 + (kx dx)^2 an exact integer, so the statistics are bit-reproducible; a float pitch
+    is out of scope.  HD = sqrt(max D2), HD95 = numpy's 95th percentile (linear) of the pooled sqrt(D2(P -> T)) U sqrt(D2(T -> P)),
+    ASSD = the mean of the two directed means, all three scaled by ``unit``; RVD = (|P| - |T|) / |T| (0 when |T| = 0); Dice =
+    2 |P n T| / (|P| + |T|) and Jaccard = |P n T| / |P u T| (nan when both masks are empty).  A pair is valid for the distances when P
+    and T are both non-empty; the others are counted as empty_pred / empty_target / empty_both and not scored.
+
+    update(pred, target) scores ONE case: pred = fp32 logits [D, C, H, W] (arg-max, first maximum wins) or an integer label volume
+    [D, H, W]; target [D, H, W] integer; labels outside [0, C) belong to no class.  push(pred, target) appends a batch of consecutive
+    slices of the current case (the call of a 2D validation loop: it narrows the slices to uint8 on the device and nothing else),
+    close_case() scores what was pushed.  Limits, checked when a case is closed: 1 <= D <= 1024, 2 <= H, W <= 1024 and
+    (kz (D-1))^2 + (ky (H-1))^2 + (kx (W-1))^2 < 2^31.  No call synchronises with the host.  A case whose classes need more than
+    ``workspace_mb`` of scratch (about 20 bytes per voxel and class) runs in chunks of classes; the statistics do not depend on the
+    chunking."""
+
+    RAW_I = SurfaceDistanceMeter.RAW_I + ("n_both",)
+
+    def __init__(self, n_classes, classes=None, spacing=(1, 1, 1), unit=1.0, device="cuda", workspace_mb=1024):
+        if not 2 <= n_classes <= 64:
+            raise ValueError("VolumeSurfaceMeter: n_classes = %d outside [2, 64]" % n_classes)
+        classes = list(range(1, n_classes)) if classes is None else [int(k) for k in classes]
+        if not classes or len(set(classes)) != len(classes) or min(classes) < 0 or max(classes) >= n_classes:
+            raise ValueError("VolumeSurfaceMeter: classes %r must be distinct ids in [0, %d)" % (classes, n_classes))
+        try:
+            ok = len(spacing) == 3 and all(int(k) == k and 1 <= k < 2 ** 31 for k in spacing)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("VolumeSurfaceMeter: spacing %r must be three positive integers (kz, ky, kx): the pitches in steps of "
+                             "`unit` (a float pitch is out of scope)" % (spacing,))
+        if not unit > 0 or not workspace_mb > 0:
+            raise ValueError("VolumeSurfaceMeter: unit and workspace_mb must be positive")
+        self.n, self.classes, self.device = n_classes, classes, torch.device(device)
+        self.spacing, self.unit = tuple(int(k) for k in spacing), float(unit)
+        self.workspace_bytes = int(workspace_mb * (1 << 20))
+        self._si, self._sf = [], []
+        self._case, self._depth = None, 0                        # (lab_pred, lab_target) uint8 [capacity, H, W]; slices pushed
+
+    def reset(self):
+        self._si, self._sf = [], []
+        self._case, self._depth = None, 0
+
+    def chunking(self, D, H, W):
+        """Classes per lmn_volume_dist call: the most whose scratch fits workspace_mb."""
+        nk = len(self.classes)
+        need = lambda k: hip.volume_workspace(D, H, W, k)
+        if need(1) > self.workspace_bytes:
+            raise ValueError("VolumeSurfaceMeter: one class of a %dx%dx%d case needs %d bytes of scratch, workspace_mb allows %d"
+                             % (D, H, W, need(1), self.workspace_bytes))
+        return max(k for k in range(1, nk + 1) if need(k) <= self.workspace_bytes)
+
+    @torch.no_grad()
+    def push(self, pred, target):
+        """Append n consecutive slices of the current case: pred fp32 logits [n, C, H, W] or integer labels [n, H, W], target
+        [n, H, W]."""
+        if not pred.is_cuda or not target.is_cuda:
+            raise RuntimeError("lm_net_amd.VolumeSurfaceMeter: device tensors required (the HIP path has no CPU fallback)")
+        pred = _prediction(pred, self.n, "VolumeSurfaceMeter", torch.int64)
+        target = _target(target, pred, "VolumeSurfaceMeter")
+        n, H, W = target.shape
+        if n < 1:
+            raise ValueError("VolumeSurfaceMeter.push: no slices")
+        if self._case is not None and tuple(self._case[0].shape[1:]) != (H, W):
+            raise ValueError("VolumeSurfaceMeter.push: slices of %dx%d into an open case of %dx%d" % ((H, W) + tuple(self._case[0].shape[1:])))
+        if not (2 <= H <= hip.VOLUME_MAX_SIDE and 2 <= W <= hip.VOLUME_MAX_SIDE) or self._depth + n > hip.VOLUME_MAX_SIDE:
+            raise ValueError("VolumeSurfaceMeter.push: a case of %d slices of %dx%d is outside 1 <= D <= %d, 2 <= H, W <= %d"
+                             % (self._depth + n, H, W, hip.VOLUME_MAX_SIDE, hip.VOLUME_MAX_SIDE))
+        cap = 0 if self._case is None else self._case[0].shape[0]
+        if self._depth + n > cap:                                # grow the case buffers (device copy, no sync)
+            cap = min(max(self._depth + n, 2 * cap), hip.VOLUME_MAX_SIDE)
+            grown = tuple(torch.empty(cap, H, W, device=pred.device, dtype=torch.uint8) for _ in range(2))
+            for new, old in zip(grown, self._case or ()):
+                new[:self._depth].copy_(old[:self._depth])
+            self._case = grown
+        hip.volume_labels(pred, target, self.n, self._case[0], self._case[1], self._depth)
+        self._depth += n
+
+    @torch.no_grad()
+    def close_case(self):
+        """Score the slices pushed since the last case and append its raw statistics."""
+        if self._case is None or self._depth == 0:
+            raise ValueError("VolumeSurfaceMeter.close_case: no slices were pushed")
+        (lab_p, lab_t), D = self._case, self._depth
+        H, W = lab_p.shape[1:]
+        self._case, self._depth = None, 0
+        span = hip.volume_span((D, H, W), self.spacing)
+        if span >= 2 ** 31:
+            raise ValueError("VolumeSurfaceMeter: (kz (D-1))^2 + (ky (H-1))^2 + (kx (W-1))^2 = %d for spacing %r and a %dx%dx%d case; the "
+                             "bound is < 2^31 = %d" % (span, self.spacing, D, H, W, 2 ** 31))
+        nk = len(self.classes)
+        ks = self.chunking(D, H, W)
+        dev = lab_p.device
+        ws = torch.empty(hip.volume_workspace(D, H, W, ks), device=dev, dtype=torch.uint8)
+        si = torch.empty(nk, hip.VOLUME_NSTAT_I, device=dev, dtype=torch.int64)
+        sf = torch.empty(nk, hip.VOLUME_NSTAT_F, device=dev, dtype=torch.float64)
+        for k0 in range(0, nk, ks):                              # (a chunk of classes is a contiguous slice: written in place)
+            k1 = min(k0 + ks, nk)
+            hip.volume_dist(lab_p[:D], lab_t[:D], self.n, self.classes[k0:k1], self.spacing, ws, si[k0:k1], sf[k0:k1])
+        self._si.append(si[None])
+        self._sf.append(sf[None])
+
+    def update(self, pred, target):
+        """Score one whole case: push + close_case."""
+        if self._depth:
+            raise ValueError("VolumeSurfaceMeter.update: a case with %d pushed slices is open; close_case() first" % self._depth)
+        self.push(pred, target)
+        self.close_case()
+
+    def add_raw(self, stats_i, stats_f):
+        """Append raw statistics ([N, len(classes), 9] int64, [N, len(classes), 2] float64), e.g. another rank's raw()."""
+        nk = len(self.classes)
+        if tuple(stats_i.shape[1:]) != (nk, 9) or tuple(stats_f.shape[1:]) != (nk, 2) or stats_i.shape[0] != stats_f.shape[0]:
+            raise ValueError("VolumeSurfaceMeter.add_raw: shapes %s, %s" % (tuple(stats_i.shape), tuple(stats_f.shape)))
+        self._si.append(stats_i.to(self.device, torch.int64))
+        self._sf.append(stats_f.to(self.device, torch.float64))
+
+    def raw(self):
+        """The raw statistics of the closed cases, in order: int64 [N, len(classes), 9] (fields RAW_I) and float64 [N, len(classes), 2]
+        (the sums of sqrt(D2(P -> T)) and sqrt(D2(T -> P)), in steps of ``unit``), on the meter's device."""
+        nk = len(self.classes)
+        if not self._si:
+            return (torch.zeros(0, nk, 9, device=self.device, dtype=torch.int64),
+                    torch.zeros(0, nk, 2, device=self.device, dtype=torch.float64))
+        return torch.cat(self._si), torch.cat(self._sf)
+
+    def compute(self):
+        """The keys of SurfaceDistanceMeter.compute() -- the distances scaled by ``unit`` -- plus 'dice', 'jaccard' (per class: nanmean
+        over cases), 'mean_dice' (nanmean over classes) and 'per_case': {'hd', 'hd95', 'assd', 'rvd', 'dice', 'jaccard'} as float64
+        [N, len(classes)] arrays, nan where a pair is not scored ('per_sample' names the same dictionary)."""
+        si, sf = self.raw()
+        return volume_metrics(si.cpu().numpy(), sf.cpu().numpy(), self.classes, self.unit)
+
+
+def volume_metrics(si, sf, classes, unit=1.0):
+    """VolumeSurfaceMeter.compute() of raw statistics si [N, nk, 9] int64, sf [N, nk, 2] float64 (numpy, float64 throughout)."""
+    si = np.asarray(si, dtype=np.int64)
+    out = surface_metrics(si[..., :8], sf, classes, unit)
+    n_p, n_t, n_b = si[..., 0], si[..., 1], si[..., 8]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dice = np.where(n_p + n_t > 0, 2 * n_b / (n_p + n_t).astype(np.float64), np.nan)        # medpy dc; nan, not 0, on 0 / 0
+        jacc = np.where(n_p + n_t - n_b > 0, n_b / (n_p + n_t - n_b).astype(np.float64), np.nan)   # medpy jc
+    per = dict(out["per_sample"], dice=dice, jaccard=jacc)
+    out["per_case"] = out["per_sample"] = per
+    for key, a in (("dice", dice), ("jaccard", jacc)):
+        ok = ~np.isnan(a)
+        cnt = ok.sum(0)
+        out[key] = np.where(cnt > 0, np.where(ok, a, 0.0).sum(0) / np.maximum(cnt, 1), np.nan).tolist()
+    d = np.asarray(out["dice"], dtype=np.float64)
+    out["mean_dice"] = float(d[~np.isnan(d)].mean()) if (~np.isnan(d)).any() else float("nan")
     return out
 
 
