@@ -12,11 +12,14 @@ without a host decision; ``lm_net_amd.optim.decay_groups``), ``lm_net_amd.metric
 ``lm_net_amd.metrics.SurfaceDistanceMeter`` (on-device HD / HD95 / ASSD / RVD),
 ``lm_net_amd.metrics.VolumeSurfaceMeter`` (per-case 3D Dice / HD / HD95 / ASSD / RVD of a label volume with integer voxel pitches),
 ``lm_net_amd.post.DevicePostprocess`` (on-device arg-max, connected-component cleaning, resize back to the frame, overlay),
+``lm_net_amd.post.VolumePostprocess`` (3D connected-component cleaning of a whole case: the n largest components of an organ, a minimal
+volume, cavity filling, between the prediction and ``VolumeSurfaceMeter``),
 ``lm_net_amd.infer.TiledPredictor`` (frames of any size: overlapping tiles, mirrored copies and one blend launch),
 ``lm_net_amd.ddp.DistributedLMNet`` (bucketed RCCL gradient all-reduce).
 """
 from .LM_Net import LM_Net  # noqa: F401
 from .loss import FocalLoss, SegLoss, SigmoidSegLoss  # noqa: F401
 from .metrics import CurveMeter, ImageStatsMeter, SigmoidStatsMeter, VolumeSurfaceMeter  # noqa: F401
+from .post import VolumePostprocess  # noqa: F401
 
-__all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter", "VolumeSurfaceMeter"]
+__all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter", "VolumeSurfaceMeter", "VolumePostprocess"]

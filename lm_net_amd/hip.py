@@ -310,6 +310,14 @@ VOLUME_MAX_SIDE = 1024       # LMN_VOLUME_* of the header
 VOLUME_NSTAT_I = 9
 VOLUME_NSTAT_F = 2
 
+# include/volpost/lmnet_volpost.h: 3D connected-component cleaning of a label volume (lm_net_amd.post.VolumePostprocess).  A list of its
+# own for the same reason, and no struct; tests/test_volpost_cpu.py checks it against the header and ties the two entries that write
+# device memory to tests/test_guard_volpost_gpu.py.
+SYMBOLS_VOLPOST = ["lmn_volpost_workspace", "lmn_cc3d_label", "lmn_volpost_clean"]
+VOLPOST_MAX_SIDE = 1024      # LMN_VOLPOST_* of the header
+VOLPOST_MAX_KEEP = 4
+VOLPOST_NSTAT = 4
+
 _lib = None
 
 
@@ -323,7 +331,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -335,6 +343,7 @@ def load():
     lib.lmn_optim_workspace.restype = C.c_int64
     lib.lmn_curve_workspace.restype = C.c_int64
     lib.lmn_volume_workspace.restype = C.c_int64
+    lib.lmn_volpost_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1397,6 +1406,43 @@ def volume_dist(lab_pred, lab_target, n_classes, classes, spacing, workspace, st
                                   int(n_classes), ids, nk, int(spacing[0]), int(spacing[1]), int(spacing[2]),
                                   _raw(workspace, torch.uint8, "volume_dist"), _i64(workspace.numel()), _raw(stats_i, torch.int64, "volume_dist"),
                                   _raw(stats_f, torch.float64, "volume_dist"), _stream()), "volume_dist")
+
+
+def volpost_workspace(D, H, W):
+    """Bytes of scratch lmn_volpost_clean needs for a D x H x W volume, exactly (host arithmetic, no GPU)."""
+    n = int(load().lmn_volpost_workspace(int(D), int(H), int(W)))
+    if n < 0:
+        raise ValueError("lm_net_amd.volpost_workspace: " + load().lmn_last_error().decode())
+    return n
+
+
+def cc3d_label(labels, connectivity, roots, sizes):
+    """Connected components of ONE uint8 label volume [D, H, W] under connectivity 6, 18 or 26 into int32 roots / sizes [D, H, W]
+    (lmn_cc3d_label)."""
+    if labels.dim() != 3 or roots.numel() != labels.numel() or sizes.numel() != labels.numel():
+        raise ValueError("lm_net_amd.cc3d_label: roots / sizes do not match a label volume [D, H, W] (labels %s)" % (tuple(labels.shape),))
+    D, H, W = (int(d) for d in labels.shape)
+    _check(load().lmn_cc3d_label(_raw(labels, torch.uint8, "cc3d_label"), D, H, W, int(connectivity), _raw(roots, torch.int32, "cc3d_label"),
+                                 _raw(sizes, torch.int32, "cc3d_label"), _stream()), "cc3d_label")
+
+
+def volpost_clean(labels, n_classes, connectivity, class_mask, keep_largest, min_volume, hole_limit, workspace, labels_out, stats):
+    """lmn_volpost_clean of ONE case: labels uint8 [D, H, W] (L0) -> labels_out uint8 [D, H, W] (L2) and stats int32 [C, 4].
+    class_mask: bit k = class k is cleaned; keep_largest / min_volume: host sequences of C ints indexed by class; workspace: uint8 device
+    tensor of at least volpost_workspace(D, H, W) bytes."""
+    n = int(n_classes)
+    if labels.dim() != 3 or labels_out.numel() != labels.numel() or stats.numel() != n * VOLPOST_NSTAT:
+        raise ValueError("lm_net_amd.volpost_clean: output buffers do not match C=%d and a label volume [D, H, W] (labels %s)"
+                         % (n, tuple(labels.shape)))
+    if len(keep_largest) != n or len(min_volume) != n:
+        raise ValueError("lm_net_amd.volpost_clean: keep_largest and min_volume need one entry per class (%d)" % n)
+    D, H, W = (int(d) for d in labels.shape)
+    keep = (C.c_int32 * n)(*[int(v) for v in keep_largest])
+    minv = (C.c_int32 * n)(*[int(v) for v in min_volume])
+    _check(load().lmn_volpost_clean(_raw(labels, torch.uint8, "volpost_clean"), D, H, W, n, int(connectivity), C.c_uint64(int(class_mask)),
+                                    keep, minv, int(hole_limit), _raw(workspace, torch.uint8, "volpost_clean"), _i64(workspace.numel()),
+                                    _raw(labels_out, torch.uint8, "volpost_clean"), _raw(stats, torch.int32, "volpost_clean"), _stream()),
+           "volpost_clean")
 
 
 def _raw(t, dt, what):

@@ -24,6 +24,9 @@ Semantics, per sample, with L0 the uint8 label map after arg-max (first maximum 
 Default palette (in the frame's channel order, as the reference applies its colours to the array it has): classes 1, 2, 3 =
 (0, 0, 255), (0, 255, 0), (255, 0, 0), the reference's three; every other class k the PASCAL-VOC colour-map rule: bit j of the
 red / green / blue byte, counted from the top, is bit 3j / 3j + 1 / 3j + 2 of k.
+
+``VolumePostprocess`` is the same cleaning for a whole CT case, a label volume [D, H, W]: 3D components under connectivity 6, 18 or
+26, the n largest of a class, a minimal volume, cavities (include/volpost/lmnet_volpost.h); its docstring has the semantics.
 """
 import math
 from collections import namedtuple
@@ -191,3 +194,169 @@ class DevicePostprocess:
                 overlay = torch.empty(B, Hs, Ws, 3, device=dev, dtype=torch.uint8)
             hip.post_render(labels_net, hw, Hs, Ws, frames, self.palette, self.n, self.alpha256, self.mode, labels, overlay)
         return PostOutput(labels_net, labels, overlay, stats)
+
+
+VolumeOutput = namedtuple("VolumeOutput", ["labels", "stats"])
+
+
+class VolumePostprocess:
+    """3D connected-component cleaning of ONE case, a label volume [D, H, W]: post(volume) -> VolumeOutput(labels, stats).
+
+    DevicePostprocess cleans every slice as its own 2D sample, which is wrong for a case: "keep the largest component" per slice
+    deletes the parts of an organ that are a second island in some slice (they are joined to it through the neighbouring slices), a
+    false-positive blob survives in every slice where it is the only component, and a cavity is a 3D notion.  Semantics, with L0 the
+    uint8 volume after arg-max (first maximum wins) / clamping (values outside [0, C) -> 0), exactly DevicePostprocess step 1:
+
+    1. Components: voxels joined by a path of ``connectivity``-neighbour steps (6, 18 or 26: scipy.ndimage.generate_binary_structure(3,
+       1 | 2 | 3)) through voxels of equal label; every label, 0 included, is partitioned.  A component's root is the smallest linear
+       index ``(z * H + y) * W + x`` of its voxels.
+    2. Cleaning, for each class k in ``classes``: the ``keep_largest[k]`` largest components survive (all of them when that is 0; equal
+       sizes: the smaller root first); among those, the ones with at least ``min_volume[k]`` voxels survive.  Voxels of the others
+       become 0 -> L1.
+    3. Hole filling on L1: a component of label 0 under the DUAL connectivity (6 for 18 and 26, 26 for 6) with no voxel on any of the
+       six faces of the volume and a volume within the limit is a hole; its voxels take the label of the voxel at x - 1 of its root
+       voxel -> L2 = ``labels``.  (scipy.ndimage.binary_fill_holes(L1 > 0, generate_binary_structure(3, 1 or 3)) plus a labelling
+       rule.)  Every voxel of a one-slice volume lies on a face, so a one-slice volume has no holes.
+    4. ``stats[k]`` = (components of class k in L0, components of class k that survive, voxels of class k in L2, holes filled for
+       k = 0 and 0 otherwise), int32 [C, 4] on the device.
+
+    ``keep_largest``: False; True (1 for every class in ``classes``); an int n in [1, 4] (the n largest of every class in ``classes``:
+    2 for kidneys and lungs); or a dict {class: n}.  ``min_volume``: an int or one int per class in ``classes``.  ``fill_holes``: a
+    bool or a maximal hole volume.
+
+    push(pred) appends n consecutive slices of the current case -- fp32 logits [n, C, H, W] or a uint8 / int64 label map [n, H, W], the
+    input contract of DevicePostprocess -- narrowed to uint8 into a case buffer that grows as VolumeSurfaceMeter's does; close_case()
+    cleans what was pushed; post(volume) is both.  Limits, checked when a case is closed: 1 <= D <= 1024, 2 <= H, W <= 1024, and a
+    scratch of about 9.2 bytes per voxel within ``workspace_mb`` (one labelling cannot be chunked).  No call synchronises with the host
+    and every launch goes to the caller's current stream; ``labels[z0:z1]`` goes into VolumeSurfaceMeter.push as it is.  Every quantity
+    is an integer: two calls on one input give bit-identical outputs.  Not recorded by plans."""
+
+    def __init__(self, n_classes, connectivity=26, classes=None, keep_largest=False, min_volume=0, fill_holes=False, workspace_mb=2048):
+        if not 2 <= n_classes <= 64:
+            raise ValueError("VolumePostprocess: n_classes = %d outside [2, 64]" % n_classes)
+        if connectivity not in (6, 18, 26):
+            raise ValueError("VolumePostprocess: connectivity %r is none of 6, 18, 26" % (connectivity,))
+        classes = list(range(1, n_classes)) if classes is None else [int(k) for k in classes]
+        if len(set(classes)) != len(classes) or any(not 1 <= k < n_classes for k in classes):
+            raise ValueError("VolumePostprocess: classes %r must be distinct ids in [1, %d) (background is never removed)"
+                             % (classes, n_classes))
+        if isinstance(keep_largest, (bool, np.bool_)):
+            keep = {k: 1 for k in classes} if keep_largest else {}
+        elif isinstance(keep_largest, (int, np.integer)):
+            keep = {k: int(keep_largest) for k in classes}
+        elif isinstance(keep_largest, dict):
+            keep = {int(k): int(n) for k, n in keep_largest.items()}
+            if any(k not in classes for k in keep):
+                raise ValueError("VolumePostprocess: keep_largest %r names a class outside classes %r" % (keep_largest, classes))
+        else:
+            raise ValueError("VolumePostprocess: keep_largest = %r: a bool, an int in [1, %d] or a dict {class: n}"
+                             % (keep_largest, hip.VOLPOST_MAX_KEEP))
+        if any(not 1 <= n <= hip.VOLPOST_MAX_KEEP for n in keep.values()):
+            raise ValueError("VolumePostprocess: keep_largest = %r: component counts must be in [1, %d]" % (keep_largest, hip.VOLPOST_MAX_KEEP))
+        if isinstance(min_volume, (int, np.integer)):
+            volumes = {k: int(min_volume) for k in classes}
+        else:
+            if len(min_volume) != len(classes):
+                raise ValueError("VolumePostprocess: min_volume needs one entry per class in classes (%d)" % len(classes))
+            volumes = {k: int(a) for k, a in zip(classes, min_volume)}
+        if any(a < 0 or a > _INT32_MAX for a in volumes.values()):
+            raise ValueError("VolumePostprocess: min_volume must be in [0, 2^31)")
+        if isinstance(fill_holes, (bool, np.bool_)):
+            hole_limit = _INT32_MAX if fill_holes else 0
+        else:
+            hole_limit = int(fill_holes)
+            if not 0 <= hole_limit <= _INT32_MAX:
+                raise ValueError("VolumePostprocess: fill_holes = %r: a bool or a maximal hole volume in [0, 2^31)" % (fill_holes,))
+        if not workspace_mb > 0:
+            raise ValueError("VolumePostprocess: workspace_mb must be positive")
+        self.n, self.connectivity, self.classes = n_classes, connectivity, classes
+        self.keep_largest, self.min_volume, self.hole_limit = keep, volumes, hole_limit
+        self.workspace_bytes = int(workspace_mb * (1 << 20))
+        self.class_mask = sum(1 << k for k in classes)
+        self._keep = [keep.get(k, 0) for k in range(n_classes)]            # the host arrays of lmn_volpost_clean, indexed by class
+        self._minv = [volumes.get(k, 0) for k in range(n_classes)]
+        self._l0 = hip.PostParam()                                         # nothing cleaned: lmn_post_clean writes L0 alone, one kernel
+        self._l0.connectivity = 8                                          # (checked by the entry, used by nothing on this route)
+        self._case, self._depth = None, 0                                  # uint8 [capacity, H, W]; slices pushed
+
+    def _pred(self, pred, what):
+        if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+            raise RuntimeError("lm_net_amd.VolumePostprocess%s: device tensors required (the HIP path has no CPU path)" % what)
+        if pred.dim() == 4 and pred.is_floating_point():
+            if pred.shape[1] != self.n:
+                raise ValueError("VolumePostprocess: logits with %d channels, n_classes = %d" % (pred.shape[1], self.n))
+            pred = pred.contiguous().float()
+        elif pred.dim() == 3 and pred.dtype in (torch.uint8, torch.int64):
+            pred = pred.contiguous()
+        else:
+            raise ValueError("VolumePostprocess: pred must be logits [n, C, H, W] or a uint8 / int64 label map [n, H, W]")
+        return pred, int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
+
+    def scratch_bytes(self, D, H, W):
+        """Bytes of scratch one case of D x H x W voxels needs; ValueError when that exceeds workspace_mb."""
+        need = hip.volpost_workspace(D, H, W)
+        if need > self.workspace_bytes:
+            raise ValueError("VolumePostprocess: a %dx%dx%d case needs %d bytes of scratch, workspace_mb allows %d (one labelling cannot "
+                             "be chunked)" % (D, H, W, need, self.workspace_bytes))
+        return need
+
+    @torch.no_grad()
+    def push(self, pred):
+        """Append n consecutive slices of the current case: fp32 logits [n, C, H, W] or a uint8 / int64 label map [n, H, W]."""
+        pred, n, H, W = self._pred(pred, ".push")
+        side = hip.VOLPOST_MAX_SIDE
+        if n < 1:
+            raise ValueError("VolumePostprocess.push: no slices")
+        if self._case is not None and tuple(self._case.shape[1:]) != (H, W):
+            raise ValueError("VolumePostprocess.push: slices of %dx%d into an open case of %dx%d" % ((H, W) + tuple(self._case.shape[1:])))
+        if not (2 <= H <= side and 2 <= W <= side) or self._depth + n > side:
+            raise ValueError("VolumePostprocess.push: a case of %d slices of %dx%d is outside 1 <= D <= %d, 2 <= H, W <= %d"
+                             % (self._depth + n, H, W, side, side))
+        cap = 0 if self._case is None else self._case.shape[0]
+        if self._depth + n > cap:                                # grow the case buffer (device copy, no sync)
+            cap = min(max(self._depth + n, 2 * cap), side)
+            grown = torch.empty(cap, H, W, device=pred.device, dtype=torch.uint8)
+            if self._case is not None:
+                grown[:self._depth].copy_(self._case[:self._depth])
+            self._case = grown
+        hip.post_clean(pred, self.n, self._l0, None, self._case[self._depth:self._depth + n], None)
+        self._depth += n
+
+    def _take_case(self, what):
+        if self._case is None or self._depth == 0:
+            raise ValueError("VolumePostprocess.%s: no slices were pushed" % what)
+        lab, self._case, self._depth = self._case[:self._depth], None, 0
+        return lab
+
+    @torch.no_grad()
+    def close_case(self):
+        """Clean the slices pushed since the last case: VolumeOutput(labels uint8 [D, H, W], stats int32 [C, 4])."""
+        lab = self._take_case("close_case")
+        D, H, W = (int(d) for d in lab.shape)
+        dev = lab.device
+        ws = torch.empty(self.scratch_bytes(D, H, W), device=dev, dtype=torch.uint8)
+        labels = torch.empty(D, H, W, device=dev, dtype=torch.uint8)
+        stats = torch.empty(self.n, hip.VOLPOST_NSTAT, device=dev, dtype=torch.int32)
+        hip.volpost_clean(lab, self.n, self.connectivity, self.class_mask, self._keep, self._minv, self.hole_limit, ws, labels, stats)
+        return VolumeOutput(labels, stats)
+
+    def _whole(self, volume, what):
+        if self._depth:
+            raise ValueError("VolumePostprocess%s: a case with %d pushed slices is open; close_case() first" % (what, self._depth))
+        self.push(volume)
+
+    def __call__(self, volume):
+        """Clean one whole case: push + close_case."""
+        self._whole(volume, "")
+        return self.close_case()
+
+    @torch.no_grad()
+    def components(self, volume):
+        """(roots, sizes), int32 [D, H, W] each: the labelling of L0 under ``connectivity``.  roots = the root of the voxel's component,
+        sizes = the component's voxel count at its root voxel and 0 elsewhere."""
+        self._whole(volume, ".components")
+        lab = self._take_case("components")
+        roots = torch.empty(lab.shape, device=lab.device, dtype=torch.int32)
+        sizes = torch.empty(lab.shape, device=lab.device, dtype=torch.int32)
+        hip.cc3d_label(lab, self.connectivity, roots, sizes)
+        return roots, sizes
