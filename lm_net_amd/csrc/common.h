@@ -28,7 +28,19 @@ static inline int lmn_launch_status(const char* what) {
   return 0;
 }
 
+// a HIP runtime call of an entry (a memset ahead of its launches): on failure the entry returns the HIP error, text "<entry>: <error>"
+#define LMN_HIP_OK(expr, what)                                                      \
+  do {                                                                              \
+    const hipError_t _e = (expr);                                                   \
+    if (_e != hipSuccess) {                                                         \
+      snprintf(g_lmn_err, sizeof(g_lmn_err), what ": %s", hipGetErrorString(_e));   \
+      return (int)_e;                                                               \
+    }                                                                               \
+  } while (0)
+
 static inline int lmn_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// workspace regions start at multiples of 256 bytes
+static inline int64_t lmn_up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 // ---------------------------------------------------------------- runtime hooks (runtime.hip)
 // (1) in-library kernel timer (lmn_prof_begin / lmn_prof_end): HIP events around every kernel launch whose name matches

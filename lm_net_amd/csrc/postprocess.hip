@@ -6,14 +6,16 @@
 // max / min, so the result does not depend on arrival order: two calls on one input give bit-identical outputs.
 //
 // Connected-component labelling (lmn_cc_label, and twice inside lmn_post_clean), 8- or 4-connected, every label value partitioned:
-//   1. cc_tile_kernel     one 256-thread block labels a POST_TH x POST_TW = 32 x 64 tile inside LDS (2 KiB of labels + 8 KiB of
+//   1. cc_tile_kernel     one 256-thread block labels a CC_TH x CC_TW = 32 x 64 tile inside LDS (2 KiB of labels + 8 KiB of
 //                         tile-local parents = 10 KiB per block): row runs first, then lock-free unions of vertically / diagonally
 //                         adjacent runs, then every pixel writes the tile root of its component as an image pixel index.
 //   2. cc_seam_kernel     one thread per pixel next to a tile seam unites the trees across the seam in the global parent array.
 //   3. cc_flatten_kernel  every pixel finds its root (in place), adds 1 to areas[root] (pre-reduced per wave) and, for the hole
 //                         labelling, marks roots of components that touch the image frame (a bit of the area word).
 // A parent is always the smaller index, so a component's root is its smallest row-major pixel index.  No kernel waits for another
-// block: every loop is a find / union loop that either lowers a parent or ends.
+// block: every loop is a find / union loop that either lowers a parent or ends.  The tile and the seam pass, the union-find and the
+// argument for its safety are in cc_common.h, shared with the 3D cleaning (volpost.hip); the index space here is the image's pixel
+// index: pointers offset by the image, base 0, labels clamped by post_labels_kernel beforehand.
 //
 // Cleaning (lmn_post_clean):
 //   4. post_labels_kernel arg-max (pred_common.h) or the given label map -> uint8 L0 (outside [0, C) -> 0)
@@ -25,12 +27,9 @@
 // Render (lmn_post_render): post_render_kernel, one launch per 64 samples of a ragged batch: nearest resize to the frame (the
 // lmn_preprocess_u8 mask arithmetic with source and destination exchanged), 16 pixels per thread with 16-byte stores, fill or contour
 // overlay blended in 8-bit fixed point.  No frame-size intermediate.
+#include "cc_common.h"
 #include "pred_common.h"
 
-#define POST_TH 32
-#define POST_TW 64
-#define POST_PPT (POST_TH * POST_TW / 256)      // pixels per thread of the tile pass, consecutive in a row
-#define POST_SEGS (POST_TW / POST_PPT)          // threads per tile row
 #define POST_MAXSIDE 1024
 #define POST_FRAME_BIT (1 << 30)                // areas are < 2^21
 #define POST_RCHUNK 64                          // samples per render launch
@@ -43,190 +42,36 @@ struct PostRender {
   uint8_t pal[64][4];
 };
 
-inline int64_t post_up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
-// ---------------------------------------------------------------- union-find in LDS (tile-local indices)
-__device__ __forceinline__ int tile_find(int* par, int i) {
-  int r = i;
-  for (;;) {
-    const int p = __hip_atomic_load(par + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (p == r) break;
-    r = p;
-  }
-  return r;
-}
-// Lock-free union: the larger root takes the smaller as its parent.  Every iteration either ends or lowers a parent.
-__device__ __forceinline__ void tile_union(int* par, int a, int b) {
-  for (;;) {
-    a = tile_find(par, a);
-    b = tile_find(par, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(par + a, b);
-    if (old == a) return;
-    a = old;                                                 // a was no root any more: go on from what it pointed to
-  }
-}
-
-// ---------------------------------------------------------------- union-find in the global parent array (image pixel indices)
-// The per-XCD L2s are not coherent with each other, so a load here (relaxed, agent scope: it bypasses the L1 only) may return an OLD
-// parent of a node.  That is safe.  The invariant: every value a node's parent ever had is a member of the node's set with an index
-// <= the node's, and parents only ever decrease.  (Not "an ancestor": the path compression below re-points a node past its old
-// parent.)  So a walk over old values strictly descends inside one set and ends at a member that was a root at some time.  Whether
-// it still IS one is decided by the atomic alone: atomicMin returns the node's true parent at the moment of the update; when that
-// is the node itself the link has been made, otherwise the loop goes on from the returned value.  Equal roots of both ends prove
-// one set.  Compression writes min(parent, r) with r < n a member of n's set: it keeps the invariant, and it never changes a
-// current root, because a root is the smallest index of its tree and no member r < n exists for it (the loop runs while n > r).
-__device__ __forceinline__ int glob_find(int32_t* par, int i) {
-  int r = i, steps = 0;
-  for (;;) {
-    const int p = __hip_atomic_load(par + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == r) break;
-    r = p;
-    ++steps;
-  }
-  if (steps > 1) {                                           // compress the walked path: r is in the set of each of its nodes
-    int n = i;
-    while (n > r) n = atomicMin(par + n, r);
-  }
-  return r;
-}
-__device__ __forceinline__ void glob_union(int32_t* par, int a, int b) {
-  for (;;) {
-    a = glob_find(par, a);
-    b = glob_find(par, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(par + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
+// The tile and the seam pass of image blockIdx.z / blockIdx.y (cc_common.h; no C: the labels are clamped already).
 // only_zero: the hole labelling -- pixels of a non-zero label join nothing (they stay their own roots and are not counted)
 __global__ __launch_bounds__(256) void cc_tile_kernel(const uint8_t* __restrict__ lab, int H, int W, int conn8, int only_zero,
                                                       int32_t* __restrict__ parent) {
-  __shared__ uint8_t s_lab[POST_TH * POST_TW];
-  __shared__ int s_par[POST_TH * POST_TW];
-  const int tx0 = blockIdx.x * POST_TW, ty0 = blockIdx.y * POST_TH;
   const int64_t img = (int64_t)blockIdx.z * H * W;
-  const uint8_t* L = lab + img;
-  int32_t* P = parent + img;
-  const int twv = min(POST_TW, W - tx0), thv = min(POST_TH, H - ty0);      // the tile's valid extent
-  const int row = threadIdx.x / POST_SEGS, x0 = (threadIdx.x % POST_SEGS) * POST_PPT;
-  const int base = row * POST_TW + x0;
-  const bool rowv = row < thv;
-  const int nv = rowv ? max(0, min(POST_PPT, twv - x0)) : 0;              // valid pixels of this thread
-#pragma unroll
-  for (int j = 0; j < POST_PPT; ++j) s_lab[base + j] = j < nv ? L[(int64_t)(ty0 + row) * W + tx0 + x0 + j] : (uint8_t)0;
-  __syncthreads();
-  // row runs: a pixel points at the first pixel of its run inside the thread's segment, a segment's first pixel at its left neighbour
-  {
-    int start = base;
-    for (int j = 0; j < nv; ++j) {
-      const int i = base + j;
-      const uint8_t l = s_lab[i];
-      const bool joins = !(only_zero && l != 0);
-      const bool cont = joins && (j > 0 || x0 > 0) && s_lab[i - 1] == l;     // the run goes on from the left neighbour
-      if (j == 0 || !cont) start = i;
-      s_par[i] = !cont ? i : (j == 0 ? i - 1 : start);
-    }
-  }
-  __syncthreads();
-  // Unions with the row above.  An edge is skipped when a neighbour's edge implies it: the vertical edge when the left pixel and
-  // the upper-left pixel both have the label (the left pixel's vertical edge joins the same two runs); a diagonal edge when the
-  // pixel above has the label (it lies in the diagonal pixel's run), when the left pixel has it (upper-left: its vertical edge) or
-  // the right pixel has it (upper-right: its vertical edge).
-  if (row > 0) {
-    for (int j = 0; j < nv; ++j) {
-      const int i = base + j, x = x0 + j;
-      const uint8_t l = s_lab[i];
-      if (only_zero && l != 0) continue;
-      const bool left = x > 0 && s_lab[i - 1] == l;
-      if (s_lab[i - POST_TW] == l) {
-        if (!(left && s_lab[i - POST_TW - 1] == l)) tile_union(s_par, i, i - POST_TW);
-      } else if (conn8) {
-        if (x > 0 && !left && s_lab[i - POST_TW - 1] == l) tile_union(s_par, i, i - POST_TW - 1);
-        if (x + 1 < twv && s_lab[i + 1] != l && s_lab[i - POST_TW + 1] == l) tile_union(s_par, i, i - POST_TW + 1);
-      }
-    }
-  }
-  __syncthreads();
-  for (int j = 0; j < nv; ++j) {
-    const int r = tile_find(s_par, base + j);
-    P[(int64_t)(ty0 + row) * W + tx0 + x0 + j] = (ty0 + r / POST_TW) * W + tx0 + r % POST_TW;
-  }
+  cc_tile_body<false>(lab + img, parent + img, 0, H, W, 0, conn8, only_zero);
 }
 
-// One thread per pixel below a horizontal seam (rows y = k * POST_TH) and right of a vertical seam (columns x = k * POST_TW): the
-// edges to its neighbours on the other side.  A corner pixel's edges are issued twice, which is harmless.
 __global__ __launch_bounds__(256) void cc_seam_kernel(const uint8_t* __restrict__ lab, int H, int W, int conn8, int only_zero,
                                                       int32_t* parent) {
-  const int nhs = (H - 1) / POST_TH, nvs = (W - 1) / POST_TW;            // seams inside the image
-  const int idx = blockIdx.x * 256 + threadIdx.x;
   const int64_t img = (int64_t)blockIdx.y * H * W;
-  const uint8_t* L = lab + img;
-  int32_t* P = parent + img;
-  if (idx < nhs * W) {
-    const int s = idx / W, x = idx - s * W, y = (s + 1) * POST_TH;
-    const int i = y * W + x;
-    const uint8_t l = L[i];
-    if (only_zero && l != 0) return;
-    if (L[i - W] == l) {
-      glob_union(P, i, i - W);
-    } else if (conn8) {
-      if (x > 0 && L[i - W - 1] == l) glob_union(P, i, i - W - 1);
-      if (x + 1 < W && L[i - W + 1] == l) glob_union(P, i, i - W + 1);
-    }
-  } else if (idx < nhs * W + nvs * H) {
-    const int k = idx - nhs * W;
-    const int s = k / H, y = k - s * H, x = (s + 1) * POST_TW;
-    const int i = y * W + x;
-    const uint8_t l = L[i];
-    if (only_zero && l != 0) return;
-    if (L[i - 1] == l) {
-      glob_union(P, i, i - 1);
-    } else if (conn8) {                                    // (with the left pixel in the set its vertical edges imply both diagonals;
-      if (y > 0 && L[i - W - 1] == l) glob_union(P, i, i - W - 1);               //  the pixel below, if in the set, issues the lower one itself)
-      if (y + 1 < H && L[i + W - 1] == l && L[i + W] != l) glob_union(P, i, i + W - 1);
-    }
-  }
+  cc_seam_body<false>(lab + img, parent + img, 0, H, W, 0, conn8, only_zero);
 }
 
-// In place: a pixel's final root is a member of its set with a smaller index, so a concurrent walk that reads the old or the new
-// value still descends inside the set; no union runs here, so a root read as a root is one.
 __global__ __launch_bounds__(256) void cc_flatten_kernel(const uint8_t* __restrict__ lab, int H, int W, int only_zero, int mark_frame,
                                                          int32_t* roots, int32_t* __restrict__ areas) {
-  const int HW = H * W, i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  const int HW = H * W, i = blockIdx.x * 256 + threadIdx.x;
   const int64_t img = (int64_t)blockIdx.y * HW;
-  int32_t* P = roots + img;
   int32_t* A = areas + img;
   bool counted = false;
   int r = -1;
   if (i < HW && !(only_zero && lab[img + i] != 0)) {
     counted = true;
-    r = i;
-    for (;;) {
-      const int p = __hip_atomic_load(P + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (p == r) break;
-      r = p;
-    }
-    __hip_atomic_store(P + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    r = cc_root_store(roots + img, i);
     if (mark_frame) {
       const int y = i / W, x = i - y * W;
       if (y == 0 || y == H - 1 || x == 0 || x == W - 1) atomicOr(A + r, POST_FRAME_BIT);
     }
   }
-  // the wave's first four distinct roots add their lane counts once; whatever is left adds 1 per lane (exact either way)
-  unsigned long long todo = __ballot(counted);
-  for (int it = 0; it < 4 && todo; ++it) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int r0 = __shfl(r, leader, 64);
-    const unsigned long long same = __ballot(counted && r == r0) & todo;
-    if (lane == leader) atomicAdd(A + r0, __popcll(same));
-    todo &= ~same;
-  }
-  if ((todo >> lane) & 1) atomicAdd(A + r, 1);
+  cc_wave_count(counted, r, A);
 }
 
 __global__ __launch_bounds__(256) void post_labels_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ lab8,
@@ -246,8 +91,8 @@ __global__ __launch_bounds__(256) void post_labels_kernel(const float* __restric
   }
 }
 
-// The packed key settles "largest area, then smallest root" by itself.  A block reduces its offers per class in LDS first, so a map
-// in which every pixel is a root (the 4-connected checkerboard) still issues one global atomic per block and class.
+// The packed key (cc_common.h) settles "largest area, then smallest root" by itself.  A block reduces its offers per class in LDS
+// first, so a map in which every pixel is a root (the 4-connected checkerboard) still issues one global atomic per block and class.
 __global__ __launch_bounds__(256) void post_select_kernel(const uint8_t* __restrict__ lab, const int32_t* __restrict__ roots,
                                                           const int32_t* __restrict__ areas, int HW, int C, lmn_post_param_t prm,
                                                           unsigned long long* __restrict__ best, int32_t* __restrict__ stats) {
@@ -266,7 +111,7 @@ __global__ __launch_bounds__(256) void post_select_kernel(const uint8_t* __restr
     if (i < HW && roots[img + i] == i) {
       const int k = lab[img + i], a = areas[img + i];
       atomicAdd(&s_n[k], 1);
-      if ((prm.keep_largest_mask >> k) & 1) atomicMax(&s_best[k], ((unsigned long long)a << 32) | (0xFFFFFFFFu - (uint32_t)i));
+      if ((prm.keep_largest_mask >> k) & 1) atomicMax(&s_best[k], cc_key(a, i));
       else if (!((prm.class_mask >> k) & 1) || a >= prm.min_area[k]) atomicAdd(&s_pass[k], 1);
     }
   }
@@ -287,14 +132,14 @@ __global__ __launch_bounds__(256) void post_apply_kernel(const uint8_t* __restri
   const int64_t img = (int64_t)b * HW;
   if (blockIdx.x == 0 && threadIdx.x < C && ((prm.keep_largest_mask >> threadIdx.x) & 1)) {   // survivors of a keep_largest class
     const unsigned long long w = best[(int64_t)b * 64 + threadIdx.x];
-    stats[((int64_t)b * C + threadIdx.x) * 4 + 1] = (w != 0 && (int)(w >> 32) >= prm.min_area[threadIdx.x]) ? 1 : 0;
+    stats[((int64_t)b * C + threadIdx.x) * 4 + 1] = (w != 0 && cc_key_size(w) >= prm.min_area[threadIdx.x]) ? 1 : 0;
   }
   if (i >= HW) return;
   int k = lab[img + i];
   if ((prm.class_mask >> k) & 1) {
     const int r = roots[img + i];
     bool keep = areas[img + r] >= prm.min_area[k];
-    if ((prm.keep_largest_mask >> k) & 1) keep = keep && (uint32_t)best[(int64_t)b * 64 + k] == 0xFFFFFFFFu - (uint32_t)r;
+    if ((prm.keep_largest_mask >> k) & 1) keep = keep && cc_key_root(best[(int64_t)b * 64 + k]) == r;
     if (!keep) k = 0;
   }
   out[img + i] = (uint8_t)k;
@@ -309,9 +154,9 @@ __global__ __launch_bounds__(256) void post_fill_kernel(const uint8_t* __restric
   if (threadIdx.x < 64) s_cnt[threadIdx.x] = 0;
   if (threadIdx.x == 0) s_holes = 0;
   __syncthreads();
-  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int b = blockIdx.y;
   const int64_t img = (int64_t)b * HW;
-  for (int it = 0; it < POST_PPB / 256; ++it) {                 // (a uniform trip count: every lane takes part in the ballots)
+  for (int it = 0; it < POST_PPB / 256; ++it) {                 // (a uniform trip count: every lane reaches cc_wave_count's ballots)
     const int i = blockIdx.x * POST_PPB + it * 256 + threadIdx.x;
     int k = -1;
     if (i < HW) {
@@ -325,15 +170,7 @@ __global__ __launch_bounds__(256) void post_fill_kernel(const uint8_t* __restric
       }
       out[img + i] = (uint8_t)k;
     }
-    unsigned long long todo = __ballot(k >= 0);
-    for (int t = 0; t < 4 && todo; ++t) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const int k0 = __shfl(k, leader, 64);
-      const unsigned long long same = __ballot(k == k0) & todo;
-      if (lane == leader) atomicAdd(&s_cnt[k0], __popcll(same));
-      todo &= ~same;
-    }
-    if ((todo >> lane) & 1) atomicAdd(&s_cnt[k], 1);
+    cc_wave_count(k >= 0, k, s_cnt);
   }
   __syncthreads();
   if (threadIdx.x < C && s_cnt[threadIdx.x]) atomicAdd(stats + ((int64_t)b * C + threadIdx.x) * 4 + 2, s_cnt[threadIdx.x]);
@@ -449,20 +286,11 @@ bool post_dims_ok(int B, int H, int W) {
 // the three labelling kernels on a zeroed `areas`
 void cc_launch(const uint8_t* lab, int B, int H, int W, int conn8, int only_zero, int mark_frame, int32_t* roots, int32_t* areas,
                hipStream_t st) {
-  const int nseam = ((H - 1) / POST_TH) * W + ((W - 1) / POST_TW) * H;
-  LMN_LAUNCH(cc_tile_kernel, dim3(lmn_cdiv(W, POST_TW), lmn_cdiv(H, POST_TH), B), dim3(256), 0, st, lab, H, W, conn8, only_zero, roots);
+  const int nseam = ((H - 1) / CC_TH) * W + ((W - 1) / CC_TW) * H;
+  LMN_LAUNCH(cc_tile_kernel, dim3(lmn_cdiv(W, CC_TW), lmn_cdiv(H, CC_TH), B), dim3(256), 0, st, lab, H, W, conn8, only_zero, roots);
   if (nseam > 0) LMN_LAUNCH(cc_seam_kernel, dim3(lmn_cdiv(nseam, 256), B), dim3(256), 0, st, lab, H, W, conn8, only_zero, roots);
   LMN_LAUNCH(cc_flatten_kernel, dim3(lmn_cdiv(H * W, 256), B), dim3(256), 0, st, lab, H, W, only_zero, mark_frame, roots, areas);
 }
-
-#define POST_HIP(expr, what)                                                        \
-  do {                                                                              \
-    const hipError_t _e = (expr);                                                   \
-    if (_e != hipSuccess) {                                                         \
-      snprintf(g_lmn_err, sizeof(g_lmn_err), what ": %s", hipGetErrorString(_e));   \
-      return (int)_e;                                                               \
-    }                                                                               \
-  } while (0)
 
 }  // namespace
 
@@ -476,7 +304,7 @@ int64_t lmn_post_workspace(int B, int H, int W) {
     return -1;
   }
   const int64_t N = (int64_t)B * H * W;
-  return 2 * post_up256(N) + 2 * post_up256(4 * N) + post_up256((int64_t)B * 64 * 8);
+  return 2 * lmn_up256(N) + 2 * lmn_up256(4 * N) + lmn_up256((int64_t)B * 64 * 8);
 }
 
 int lmn_cc_label(const uint8_t* labels, int B, int H, int W, int connectivity, void* workspace, int64_t ws_bytes, int32_t* roots,
@@ -487,7 +315,7 @@ int lmn_cc_label(const uint8_t* labels, int B, int H, int W, int connectivity, v
   LMN_REQUIRE(post_dims_ok(B, H, W), "cc_label: B=%d %dx%d outside B in [1, 65535], sides in [2, %d]", B, H, W, POST_MAXSIDE);
   LMN_REQUIRE(connectivity == 4 || connectivity == 8, "cc_label: connectivity %d is neither 4 nor 8", connectivity);
   hipStream_t st = (hipStream_t)stream;
-  POST_HIP(hipMemsetAsync(areas, 0, sizeof(int32_t) * (size_t)B * H * W, st), "cc_label");
+  LMN_HIP_OK(hipMemsetAsync(areas, 0, sizeof(int32_t) * (size_t)B * H * W, st), "cc_label");
   cc_launch(labels, B, H, W, connectivity == 8, 0, 0, roots, areas, st);
   return lmn_launch_status("cc_label");
 }
@@ -520,13 +348,13 @@ int lmn_post_clean(const float* logits, const uint8_t* labels_u8, const int64_t*
   const int64_t need = lmn_post_workspace(B, H, W);
   LMN_REQUIRE(ws_bytes >= need, "post_clean: workspace of %lld bytes too small, %lld needed", (long long)ws_bytes, (long long)need);
   uint8_t* lab0 = (uint8_t*)workspace;
-  uint8_t* lab1 = lab0 + post_up256(N);
-  int32_t* roots = (int32_t*)(lab1 + post_up256(N));
-  int32_t* areas = (int32_t*)((uint8_t*)roots + post_up256(4 * N));
-  unsigned long long* best = (unsigned long long*)((uint8_t*)areas + post_up256(4 * N));
+  uint8_t* lab1 = lab0 + lmn_up256(N);
+  int32_t* roots = (int32_t*)(lab1 + lmn_up256(N));
+  int32_t* areas = (int32_t*)((uint8_t*)roots + lmn_up256(4 * N));
+  unsigned long long* best = (unsigned long long*)((uint8_t*)areas + lmn_up256(4 * N));
   const dim3 pgrid(lmn_cdiv(HW, 256), B), wgrid(lmn_cdiv(HW, POST_PPB), B);
-  POST_HIP(hipMemsetAsync(stats, 0, sizeof(int32_t) * 4 * (size_t)B * C, st), "post_clean");
-  POST_HIP(hipMemsetAsync(areas, 0, (size_t)(post_up256(4 * N) + post_up256((int64_t)B * 64 * 8)), st), "post_clean");   // areas and best, adjacent
+  LMN_HIP_OK(hipMemsetAsync(stats, 0, sizeof(int32_t) * 4 * (size_t)B * C, st), "post_clean");
+  LMN_HIP_OK(hipMemsetAsync(areas, 0, (size_t)(lmn_up256(4 * N) + lmn_up256((int64_t)B * 64 * 8)), st), "post_clean");   // areas and best, adjacent
   LMN_LAUNCH(post_labels_kernel, dim3(lgrid), dim3(256), 0, st, logits, labels_u8, labels_i64, C, (int64_t)HW, N, lab0);
   cc_launch(lab0, B, H, W, prm.connectivity == 8, 0, 0, roots, areas, st);
   LMN_LAUNCH(post_select_kernel, wgrid, dim3(256), 0, st, (const uint8_t*)lab0, (const int32_t*)roots, (const int32_t*)areas, HW, C, prm, best,
@@ -535,7 +363,7 @@ int lmn_post_clean(const float* logits, const uint8_t* labels_u8, const int64_t*
              (const unsigned long long*)best, lab1, stats);
   const int32_t* hroots = nullptr;
   if (prm.hole_limit > 0) {
-    POST_HIP(hipMemsetAsync(areas, 0, sizeof(int32_t) * (size_t)N, st), "post_clean");
+    LMN_HIP_OK(hipMemsetAsync(areas, 0, sizeof(int32_t) * (size_t)N, st), "post_clean");
     cc_launch(lab1, B, H, W, prm.connectivity == 4, 1, 1, roots, areas, st);                 // the dual connectivity
     hroots = roots;
   }

@@ -27,11 +27,10 @@
 
 struct SurfCls { uint8_t id[64]; };
 
-static inline int64_t surf_up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-static inline int64_t surf_lab_bytes(int64_t B, int64_t HW) { return surf_up256(2 * B * HW); }
-static inline int64_t surf_g_bytes(int64_t np, int64_t HW) { return surf_up256(2 * np * HW * (int64_t)sizeof(uint16_t)); }
-static inline int64_t surf_d2_bytes(int64_t np, int64_t HW) { return surf_up256(2 * np * HW * (int64_t)sizeof(int32_t)); }
-static inline int64_t surf_rc_bytes(int64_t np, int64_t H) { return surf_up256(2 * np * H * (int64_t)sizeof(int32_t)); }
+static inline int64_t surf_lab_bytes(int64_t B, int64_t HW) { return lmn_up256(2 * B * HW); }
+static inline int64_t surf_g_bytes(int64_t np, int64_t HW) { return lmn_up256(2 * np * HW * (int64_t)sizeof(uint16_t)); }
+static inline int64_t surf_d2_bytes(int64_t np, int64_t HW) { return lmn_up256(2 * np * HW * (int64_t)sizeof(int32_t)); }
+static inline int64_t surf_rc_bytes(int64_t np, int64_t H) { return lmn_up256(2 * np * H * (int64_t)sizeof(int32_t)); }
 
 __global__ __launch_bounds__(256) void surf_labels_kernel(const float* __restrict__ logits, const int64_t* __restrict__ plab,
                                                           const int64_t* __restrict__ target, int C, int64_t hw, int64_t total,
@@ -319,11 +318,7 @@ int lmn_surface_dist(const float* pred_logits, const int64_t* pred_labels, const
   int32_t* d2 = (int32_t*)((uint8_t*)g + surf_g_bytes(np, HW));
   int32_t* rowcnt = (int32_t*)((uint8_t*)d2 + surf_d2_bytes(np, HW));
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(stats_i, 0, sizeof(int64_t) * SURF_NSTAT_I * (size_t)np, st);
-  if (e != hipSuccess) {
-    snprintf(g_lmn_err, sizeof(g_lmn_err), "surface_dist: %s", hipGetErrorString(e));
-    return (int)e;
-  }
+  LMN_HIP_OK(hipMemsetAsync(stats_i, 0, sizeof(int64_t) * SURF_NSTAT_I * (size_t)np, st), "surface_dist");
   const int lgrid = lmn_cdiv(total, 256) < 2048 ? lmn_cdiv(total, 256) : 2048;
   LMN_LAUNCH(surf_labels_kernel, dim3(lgrid), dim3(256), 0, st, pred_logits, pred_labels, target, C, HW, total, lab);
   LMN_LAUNCH(surf_col_kernel, dim3(lmn_cdiv(W, 64), np, 2), dim3(64, SURF_SEG), 0, st, (const uint8_t*)lab, B, nk, H, W, cls, g,

@@ -1,9 +1,10 @@
 // 3D connected-component cleaning of a label volume on the device (lm_net_amd.post.VolumePostprocess; include/volpost/
 // lmnet_volpost.h): the components of a [D, H, W] uint8 volume under connectivity 6, 18 or 26, the n largest of a class (n <= 4),
 // a minimal volume, cavity filling under the dual connectivity, per-class statistics.  postprocess.hip with one more axis: the same
-// union-find (LDS tiles per slice, lock-free atomicMin unions), a volume-sized index space, links to the slice above and a selection
-// of several components.  Integer arithmetic throughout; every cross-block sum is an int32 atomic add, every selection a 64-bit
-// atomic max and every mark an atomic or, so the result does not depend on arrival order: two calls give bit-identical outputs.
+// tile and seam passes and the same union-find (cc_common.h: LDS tiles per slice, lock-free unions, and the argument for
+// their safety), a volume-sized index space, links to the slice above and a selection of several components.  Integer arithmetic
+// throughout; every cross-block sum is an int32 atomic add, every selection a 64-bit atomic max and every mark an atomic or, so the
+// result does not depend on arrival order: two calls give bit-identical outputs.
 //
 // Labelling (lmn_cc3d_label, and twice inside lmn_volpost_clean), every label value partitioned:
 //   1. vp_tile_kernel     one 256-thread block labels a 32 x 64 tile of ONE slice inside LDS (2 KiB of labels + 8 KiB of tile-local
@@ -22,33 +23,20 @@
 // arithmetic of every kernel here (at most 2^30 + 1023).  A byte offset into the int32 arrays is not: every pointer is formed as
 // `base + index` on a typed pointer, which the compiler widens to 64 bits.
 //
-// SAFETY of the union-find in the global parent array, restated for the volume index space.  The per-XCD L2s are not coherent with
-// each other, so a load of a parent (relaxed, agent scope: it bypasses the L1 only) may return an OLD value.  The invariant: every
-// value a voxel's parent ever had is a member of the voxel's set with an index <= the voxel's, and parents only ever decrease.  The
-// tile pass establishes it (a tile root is the smallest index of its tile component: within one slice the volume index orders voxels
-// as the tile-local index does row by row, and the slice offset is common); atomicMin(parent[a], b) with b < a a member of a's set
-// keeps it.  So a walk over old values strictly descends inside one set and ends, after at most as many steps as the set has
-// members, at a voxel that was a root at some time.  Whether it still IS one the atomic alone decides: atomicMin returns the true
-// parent at the moment of the update; when that is the voxel itself the link has been made, otherwise the loop goes on from the
-// returned value, which is smaller.  Equal roots of both ends prove one set.  Path compression writes min(parent, r) with r < n a
-// member of n's set, which keeps the invariant and never changes a current root.  NO KERNEL WAITS FOR ANOTHER BLOCK: there is no
-// lock, no grid barrier and no "retry until someone else has written"; every loop either lowers a parent or ends, and a parent is
-// bounded below by 0.
+// SAFETY of the union-find in the global parent array: the comment at cc_find (cc_common.h).  Its index space here is the volume
+// voxel index: the tile and the seam pass take the volume's pointers and the slice offset as base, and vp_zlink_kernel's links keep
+// the invariant as every union does (the smaller root becomes the parent).
 //
 // Cleaning (lmn_volpost_clean):
 //   5. vp_select_kernel   pass j = 0 .. max(keep_largest) - 1: root voxels offer (size << 32 | ~root) to slot (class, j), restricted
 //                         for j >= 1 to keys below slot (class, j - 1): block-level max in LDS, then one 64-bit atomic max per
-//                         block and slot.  The packed key settles "largest size, then smallest root".  Pass 0 counts the components.
+//                         block and slot.  The packed key (cc_common.h) settles "largest size, then smallest root".  Pass 0 counts the components.
 //   6. vp_apply_kernel    L1 = L0 without the components that do not survive keep_largest / min_volume.
 //   7. (labelling of L1's zero voxels under the dual connectivity with face marks) vp_fill_kernel: holes take the label at x - 1 of
 //      their root voxel; per-class voxel counts and the number of holes.
-#include "common.h"
+#include "cc_common.h"
 #include "../../include/volpost/lmnet_volpost.h"
 
-#define VP_TH 32
-#define VP_TW 64
-#define VP_PPT (VP_TH * VP_TW / 256)          // voxels per thread of the tile pass, consecutive in a row
-#define VP_SEGS (VP_TW / VP_PPT)              // threads per tile row
 #define VP_MAXSIDE LMN_VOLPOST_MAX_SIDE
 #define VP_MAXKEEP LMN_VOLPOST_MAX_KEEP
 #define VP_PPB 1024                           // voxels per block of the select and fill passes
@@ -63,151 +51,21 @@ struct VpParam {
   uint8_t keep[64];                           // 0 = every component, else the number of largest components kept
 };
 
-inline int64_t vp_up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-inline int64_t vp_face_bytes(int64_t V) { return vp_up256(4 * ((V + 31) / 32)); }
+inline int64_t vp_face_bytes(int64_t V) { return lmn_up256(4 * ((V + 31) / 32)); }
 
 // a label as the cleaning reads it: values >= C are 0 (C = 256: every value stands)
-__device__ __forceinline__ int vp_lab(const uint8_t* __restrict__ L, int i, int C) {
-  const int l = L[i];
-  return l < C ? l : 0;
-}
+__device__ __forceinline__ int vp_lab(const uint8_t* __restrict__ L, int i, int C) { return cc_lab<true>(L, i, C); }
 
-// ---------------------------------------------------------------- union-find in LDS (tile-local indices)
-__device__ __forceinline__ int vp_tile_find(int* par, int i) {
-  int r = i;
-  for (;;) {
-    const int p = __hip_atomic_load(par + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (p == r) break;
-    r = p;
-  }
-  return r;
-}
-// Lock-free union: the larger root takes the smaller as its parent.  Every iteration either ends or lowers a parent.
-__device__ __forceinline__ void vp_tile_union(int* par, int a, int b) {
-  for (;;) {
-    a = vp_tile_find(par, a);
-    b = vp_tile_find(par, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(par + a, b);
-    if (old == a) return;
-    a = old;                                                 // a was no root any more: go on from what it pointed to
-  }
-}
-
-// ---------------------------------------------------------------- union-find in the global parent array (volume voxel indices)
-// (the safety argument is at the top of the file)
-__device__ __forceinline__ int vp_find(int32_t* par, int i) {
-  int r = i, steps = 0;
-  for (;;) {
-    const int p = __hip_atomic_load(par + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == r) break;
-    r = p;                                                   // p < r: the walk descends
-    ++steps;
-  }
-  if (steps > 1) {                                           // compress the walked path: r is in the set of each of its nodes
-    int n = i;
-    while (n > r) n = atomicMin(par + n, r);                 // n strictly decreases: the walk left n for a smaller parent, and parents only decrease
-  }
-  return r;
-}
-__device__ __forceinline__ void vp_union(int32_t* par, int a, int b) {
-  for (;;) {
-    a = vp_find(par, a);                                     // the finds come first: two ends of one set issue no atomic
-    b = vp_find(par, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(par + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
-// only_zero: the hole labelling -- voxels of a non-zero label join nothing (they stay their own roots and are not counted)
+// The tile and the seam pass of slice blockIdx.z / blockIdx.y (cc_common.h), in volume voxel indices: the slice's first voxel (< 2^30)
+// is the base.  only_zero: the hole labelling -- voxels of a non-zero label join nothing (they stay their own roots and are not counted)
 __global__ __launch_bounds__(256) void vp_tile_kernel(const uint8_t* __restrict__ lab, int H, int W, int C, int conn8, int only_zero,
                                                       int32_t* __restrict__ parent) {
-  __shared__ uint8_t s_lab[VP_TH * VP_TW];
-  __shared__ int s_par[VP_TH * VP_TW];
-  const int tx0 = blockIdx.x * VP_TW, ty0 = blockIdx.y * VP_TH;
-  const int sl = (int)blockIdx.z * H * W;                                  // first voxel of the slice: < 2^30
-  const uint8_t* L = lab + sl;
-  int32_t* P = parent + sl;
-  const int twv = min(VP_TW, W - tx0), thv = min(VP_TH, H - ty0);          // the tile's valid extent
-  const int row = threadIdx.x / VP_SEGS, x0 = (threadIdx.x % VP_SEGS) * VP_PPT;
-  const int base = row * VP_TW + x0;
-  const bool rowv = row < thv;
-  const int nv = rowv ? max(0, min(VP_PPT, twv - x0)) : 0;                 // valid voxels of this thread
-#pragma unroll
-  for (int j = 0; j < VP_PPT; ++j) s_lab[base + j] = j < nv ? (uint8_t)vp_lab(L, (ty0 + row) * W + tx0 + x0 + j, C) : (uint8_t)0;
-  __syncthreads();
-  // row runs: a voxel points at the first voxel of its run inside the thread's segment, a segment's first voxel at its left neighbour
-  {
-    int start = base;
-    for (int j = 0; j < nv; ++j) {
-      const int i = base + j;
-      const uint8_t l = s_lab[i];
-      const bool joins = !(only_zero && l != 0);
-      const bool cont = joins && (j > 0 || x0 > 0) && s_lab[i - 1] == l;     // the run goes on from the left neighbour
-      if (j == 0 || !cont) start = i;
-      s_par[i] = !cont ? i : (j == 0 ? i - 1 : start);
-    }
-  }
-  __syncthreads();
-  // Unions with the row above.  An edge is skipped when a neighbour's edge implies it: the vertical edge when the left voxel and
-  // the upper-left voxel both have the label; a diagonal edge when the voxel above has the label, when the left voxel has it
-  // (upper-left) or the right voxel has it (upper-right).
-  if (row > 0) {
-    for (int j = 0; j < nv; ++j) {
-      const int i = base + j, x = x0 + j;
-      const uint8_t l = s_lab[i];
-      if (only_zero && l != 0) continue;
-      const bool left = x > 0 && s_lab[i - 1] == l;
-      if (s_lab[i - VP_TW] == l) {
-        if (!(left && s_lab[i - VP_TW - 1] == l)) vp_tile_union(s_par, i, i - VP_TW);
-      } else if (conn8) {
-        if (x > 0 && !left && s_lab[i - VP_TW - 1] == l) vp_tile_union(s_par, i, i - VP_TW - 1);
-        if (x + 1 < twv && s_lab[i + 1] != l && s_lab[i - VP_TW + 1] == l) vp_tile_union(s_par, i, i - VP_TW + 1);
-      }
-    }
-  }
-  __syncthreads();
-  for (int j = 0; j < nv; ++j) {
-    const int r = vp_tile_find(s_par, base + j);
-    P[(ty0 + row) * W + tx0 + x0 + j] = sl + (ty0 + r / VP_TW) * W + tx0 + r % VP_TW;
-  }
+  cc_tile_body<true>(lab, parent, (int)blockIdx.z * H * W, H, W, C, conn8, only_zero);
 }
 
-// One thread per voxel below a horizontal seam (rows y = k * VP_TH) and right of a vertical seam (columns x = k * VP_TW) of slice
-// blockIdx.y: the edges to its in-plane neighbours on the other side.  A corner voxel's edges are issued twice, which is harmless.
 __global__ __launch_bounds__(256) void vp_seam_kernel(const uint8_t* __restrict__ lab, int H, int W, int C, int conn8, int only_zero,
                                                       int32_t* parent) {
-  const int nhs = (H - 1) / VP_TH, nvs = (W - 1) / VP_TW;                // seams inside a slice
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  const int sl = (int)blockIdx.y * H * W;
-  if (idx < nhs * W) {
-    const int s = idx / W, x = idx - s * W, y = (s + 1) * VP_TH;
-    const int i = sl + y * W + x;
-    const int l = vp_lab(lab, i, C);
-    if (only_zero && l != 0) return;
-    if (vp_lab(lab, i - W, C) == l) {
-      vp_union(parent, i, i - W);
-    } else if (conn8) {
-      if (x > 0 && vp_lab(lab, i - W - 1, C) == l) vp_union(parent, i, i - W - 1);
-      if (x + 1 < W && vp_lab(lab, i - W + 1, C) == l) vp_union(parent, i, i - W + 1);
-    }
-  } else if (idx < nhs * W + nvs * H) {
-    const int k = idx - nhs * W;
-    const int s = k / H, y = k - s * H, x = (s + 1) * VP_TW;
-    const int i = sl + y * W + x;
-    const int l = vp_lab(lab, i, C);
-    if (only_zero && l != 0) return;
-    if (vp_lab(lab, i - 1, C) == l) {
-      vp_union(parent, i, i - 1);
-    } else if (conn8) {                                    // (with the left voxel in the set its vertical edges imply both diagonals;
-      if (y > 0 && vp_lab(lab, i - W - 1, C) == l) vp_union(parent, i, i - W - 1);       //  the voxel below, if in the set, issues the lower one itself)
-      if (y + 1 < H && vp_lab(lab, i + W - 1, C) == l && vp_lab(lab, i + W, C) != l) vp_union(parent, i, i + W - 1);
-    }
-  }
+  cc_seam_body<true>(lab, parent, (int)blockIdx.y * H * W, H, W, C, conn8, only_zero);
 }
 
 // Links to the slice above.  v = (z, y, x) with label l; its candidates are the voxels u = (z - 1, y + dy, x + dx) of label l with
@@ -235,7 +93,7 @@ __global__ __launch_bounds__(256) void vp_zlink_kernel(const uint8_t* __restrict
   const int up = i - HW;
   const bool run = x > 0 && vp_lab(lab, i - 1, C) == l;               // v continues a row run
   if (vp_lab(lab, up, C) == l) {                                       // (a)
-    if (!(run && vp_lab(lab, up - 1, C) == l)) vp_union(parent, i, up);   // (c): x > 0, so up - 1 is in the row
+    if (!(run && vp_lab(lab, up - 1, C) == l)) cc_union(parent, i, up);   // (c): x > 0, so up - 1 is in the row
     return;
   }
   if (allow == (1 << 4)) return;                                       // connectivity 6: the centre was the only candidate
@@ -253,42 +111,25 @@ __global__ __launch_bounds__(256) void vp_zlink_kernel(const uint8_t* __restrict
         if (dx <= 0 && ((allow >> (3 * (dy + 1) + dx + 2)) & 1)) continue;
         if (x + dx > 0 && vp_lab(lab, u - 1, C) == l) continue;
       }
-      vp_union(parent, i, u);
+      cc_union(parent, i, u);
     }
   }
 }
 
-// In place: a voxel's final root is a member of its set with a smaller index, so a concurrent walk that reads the old or the new
-// value still descends inside the set; no union runs here, so a root read as a root is one.
 __global__ __launch_bounds__(256) void vp_flatten_kernel(const uint8_t* __restrict__ lab, int D, int H, int W, int C, int only_zero,
                                                          int V, int32_t* roots, int32_t* __restrict__ sizes, uint32_t* __restrict__ face) {
-  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 256 + threadIdx.x;
   bool counted = false;
   int r = -1;
   if (i < V && !(only_zero && vp_lab(lab, i, C) != 0)) {
     counted = true;
-    r = i;
-    for (;;) {
-      const int p = __hip_atomic_load(roots + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (p == r) break;
-      r = p;
-    }
-    __hip_atomic_store(roots + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    r = cc_root_store(roots, i);
     if (face) {
       const int HW = H * W, z = i / HW, yx = i - z * HW, y = yx / W, x = yx - y * W;
       if (z == 0 || z == D - 1 || y == 0 || y == H - 1 || x == 0 || x == W - 1) atomicOr(face + (r >> 5), 1u << (r & 31));
     }
   }
-  // the wave's first four distinct roots add their lane counts once; whatever is left adds 1 per lane (exact either way)
-  unsigned long long todo = __ballot(counted);
-  for (int it = 0; it < 4 && todo; ++it) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int r0 = __shfl(r, leader, 64);
-    const unsigned long long same = __ballot(counted && r == r0) & todo;
-    if (lane == leader) atomicAdd(sizes + r0, __popcll(same));
-    todo &= ~same;
-  }
-  if ((todo >> lane) & 1) atomicAdd(sizes + r, 1);
+  cc_wave_count(counted, r, sizes);
 }
 
 // Pass `rank` of the selection.  best[k * VP_MAXKEEP + j]: the key of class k's (j + 1)-th largest component, 0 = there is none.
@@ -314,7 +155,7 @@ __global__ __launch_bounds__(256) void vp_select_kernel(const uint8_t* __restric
       const int k = vp_lab(lab, i, C), a = sizes[i];
       if (rank == 0) atomicAdd(&s_n[k], 1);
       if (prm.keep[k] > rank) {
-        const vp_u64 key = ((vp_u64)(uint32_t)a << 32) | (0xFFFFFFFFu - (uint32_t)i);
+        const vp_u64 key = cc_key(a, i);
         if (key < s_below[k]) atomicMax(&s_best[k], key);
       } else if (rank == 0 && prm.keep[k] == 0 && (!((prm.class_mask >> k) & 1) || a >= prm.min_volume[k])) {
         atomicAdd(&s_pass[k], 1);
@@ -340,7 +181,7 @@ __global__ __launch_bounds__(256) void vp_apply_kernel(const uint8_t* __restrict
     int n = 0;
     for (int j = 0; j < prm.keep[k]; ++j) {
       const vp_u64 w = best[k * VP_MAXKEEP + j];
-      n += (w != 0 && (int)(w >> 32) >= prm.min_volume[k]) ? 1 : 0;
+      n += (w != 0 && cc_key_size(w) >= prm.min_volume[k]) ? 1 : 0;
     }
     stats[k * 4 + 1] = n;
   }
@@ -353,7 +194,7 @@ __global__ __launch_bounds__(256) void vp_apply_kernel(const uint8_t* __restrict
       bool among = false;
       for (int j = 0; j < prm.keep[k]; ++j) {
         const vp_u64 w = best[k * VP_MAXKEEP + j];
-        among = among || (w != 0 && (uint32_t)w == 0xFFFFFFFFu - (uint32_t)r);
+        among = among || (w != 0 && cc_key_root(w) == r);
       }
       keep = keep && among;
     }
@@ -371,8 +212,7 @@ __global__ __launch_bounds__(256) void vp_fill_kernel(const uint8_t* __restrict_
   if (threadIdx.x < 64) s_cnt[threadIdx.x] = 0;
   if (threadIdx.x == 0) s_holes = 0;
   __syncthreads();
-  const int lane = threadIdx.x & 63;
-  for (int it = 0; it < VP_PPB / 256; ++it) {                   // (a uniform trip count: every lane takes part in the ballots)
+  for (int it = 0; it < VP_PPB / 256; ++it) {                   // (a uniform trip count: every lane reaches cc_wave_count's ballots)
     const int i = blockIdx.x * VP_PPB + it * 256 + threadIdx.x;
     int k = -1;
     if (i < V) {
@@ -386,15 +226,7 @@ __global__ __launch_bounds__(256) void vp_fill_kernel(const uint8_t* __restrict_
       }
       out[i] = (uint8_t)k;
     }
-    unsigned long long todo = __ballot(k >= 0);
-    for (int t = 0; t < 4 && todo; ++t) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const int k0 = __shfl(k, leader, 64);
-      const unsigned long long same = __ballot(k == k0) & todo;
-      if (lane == leader) atomicAdd(&s_cnt[k0], __popcll(same));
-      todo &= ~same;
-    }
-    if ((todo >> lane) & 1) atomicAdd(&s_cnt[k], 1);
+    cc_wave_count(k >= 0, k, s_cnt);
   }
   __syncthreads();
   if (threadIdx.x < C && s_cnt[threadIdx.x]) atomicAdd(stats + threadIdx.x * 4 + 2, s_cnt[threadIdx.x]);
@@ -412,21 +244,12 @@ int vp_allow(int connectivity) { return connectivity == 6 ? 0x010 : connectivity
 void vp_label(const uint8_t* lab, int D, int H, int W, int C, int connectivity, int only_zero, int32_t* roots, int32_t* sizes,
               uint32_t* face, hipStream_t st) {
   const int conn8 = connectivity != 6;
-  const int V = D * H * W, nseam = ((H - 1) / VP_TH) * W + ((W - 1) / VP_TW) * H, nz = (D - 1) * H * W;
-  LMN_LAUNCH(vp_tile_kernel, dim3(lmn_cdiv(W, VP_TW), lmn_cdiv(H, VP_TH), D), dim3(256), 0, st, lab, H, W, C, conn8, only_zero, roots);
+  const int V = D * H * W, nseam = ((H - 1) / CC_TH) * W + ((W - 1) / CC_TW) * H, nz = (D - 1) * H * W;
+  LMN_LAUNCH(vp_tile_kernel, dim3(lmn_cdiv(W, CC_TW), lmn_cdiv(H, CC_TH), D), dim3(256), 0, st, lab, H, W, C, conn8, only_zero, roots);
   if (nseam > 0) LMN_LAUNCH(vp_seam_kernel, dim3(lmn_cdiv(nseam, 256), D), dim3(256), 0, st, lab, H, W, C, conn8, only_zero, roots);
   if (nz > 0) LMN_LAUNCH(vp_zlink_kernel, dim3(lmn_cdiv(nz, 256)), dim3(256), 0, st, lab, H, W, C, vp_allow(connectivity), only_zero, nz, roots);
   LMN_LAUNCH(vp_flatten_kernel, dim3(lmn_cdiv(V, 256)), dim3(256), 0, st, lab, D, H, W, C, only_zero, V, roots, sizes, face);
 }
-
-#define VP_HIP(expr, what)                                                          \
-  do {                                                                              \
-    const hipError_t _e = (expr);                                                   \
-    if (_e != hipSuccess) {                                                         \
-      snprintf(g_lmn_err, sizeof(g_lmn_err), what ": %s", hipGetErrorString(_e));   \
-      return (int)_e;                                                               \
-    }                                                                               \
-  } while (0)
 
 }  // namespace
 
@@ -439,7 +262,7 @@ int64_t lmn_volpost_workspace(int D, int H, int W) {
     return -1;
   }
   const int64_t V = (int64_t)D * H * W;
-  return vp_up256(V) + 2 * vp_up256(4 * V) + vp_face_bytes(V) + vp_up256(64 * VP_MAXKEEP * 8);
+  return lmn_up256(V) + 2 * lmn_up256(4 * V) + vp_face_bytes(V) + lmn_up256(64 * VP_MAXKEEP * 8);
 }
 
 int lmn_cc3d_label(const uint8_t* labels, int D, int H, int W, int connectivity, int32_t* roots, int32_t* sizes, lmn_stream_t stream) {
@@ -448,7 +271,7 @@ int lmn_cc3d_label(const uint8_t* labels, int D, int H, int W, int connectivity,
   LMN_REQUIRE(H >= 2 && H <= VP_MAXSIDE && W >= 2 && W <= VP_MAXSIDE, "cc3d_label: size %dx%d outside [2, %d]", H, W, VP_MAXSIDE);
   LMN_REQUIRE(connectivity == 6 || connectivity == 18 || connectivity == 26, "cc3d_label: connectivity %d is none of 6, 18, 26", connectivity);
   hipStream_t st = (hipStream_t)stream;
-  VP_HIP(hipMemsetAsync(sizes, 0, sizeof(int32_t) * (size_t)D * H * W, st), "cc3d_label");
+  LMN_HIP_OK(hipMemsetAsync(sizes, 0, sizeof(int32_t) * (size_t)D * H * W, st), "cc3d_label");
   vp_label(labels, D, H, W, 256, connectivity, 0, roots, sizes, nullptr, st);
   return lmn_launch_status("cc3d_label");
 }
@@ -484,14 +307,14 @@ int lmn_volpost_clean(const uint8_t* labels, int D, int H, int W, int C, int con
   const int64_t V64 = (int64_t)D * H * W;
   const int V = (int)V64;
   uint8_t* lab1 = (uint8_t*)workspace;
-  int32_t* roots = (int32_t*)(lab1 + vp_up256(V64));
-  int32_t* sizes = (int32_t*)((uint8_t*)roots + vp_up256(4 * V64));
-  uint32_t* face = (uint32_t*)((uint8_t*)sizes + vp_up256(4 * V64));
+  int32_t* roots = (int32_t*)(lab1 + lmn_up256(V64));
+  int32_t* sizes = (int32_t*)((uint8_t*)roots + lmn_up256(4 * V64));
+  uint32_t* face = (uint32_t*)((uint8_t*)sizes + lmn_up256(4 * V64));
   vp_u64* best = (vp_u64*)((uint8_t*)face + vp_face_bytes(V64));
   hipStream_t st = (hipStream_t)stream;
   const dim3 pgrid(lmn_cdiv(V, 256)), wgrid(lmn_cdiv(V, VP_PPB));
-  VP_HIP(hipMemsetAsync(stats, 0, sizeof(int32_t) * 4 * (size_t)C, st), "volpost_clean");
-  VP_HIP(hipMemsetAsync(sizes, 0, (size_t)(need - vp_up256(V64) - vp_up256(4 * V64)), st), "volpost_clean");     // sizes, face and best, adjacent
+  LMN_HIP_OK(hipMemsetAsync(stats, 0, sizeof(int32_t) * 4 * (size_t)C, st), "volpost_clean");
+  LMN_HIP_OK(hipMemsetAsync(sizes, 0, (size_t)(need - lmn_up256(V64) - lmn_up256(4 * V64)), st), "volpost_clean");     // sizes, face and best, adjacent
   vp_label(labels, D, H, W, C, connectivity, 0, roots, sizes, nullptr, st);
   for (int rank = 0; rank < (ranks > 1 ? ranks : 1); ++rank)
     LMN_LAUNCH(vp_select_kernel, wgrid, dim3(256), 0, st, labels, (const int32_t*)roots, (const int32_t*)sizes, V, C, prm, rank, best, stats);
@@ -499,7 +322,7 @@ int lmn_volpost_clean(const uint8_t* labels, int D, int H, int W, int C, int con
              lab1, stats);
   const int32_t* hroots = nullptr;
   if (hole_limit > 0) {
-    VP_HIP(hipMemsetAsync(sizes, 0, sizeof(int32_t) * (size_t)V, st), "volpost_clean");
+    LMN_HIP_OK(hipMemsetAsync(sizes, 0, sizeof(int32_t) * (size_t)V, st), "volpost_clean");
     vp_label(lab1, D, H, W, C, connectivity == 6 ? 26 : 6, 1, roots, sizes, face, st);                  // the dual connectivity
     hroots = roots;
   }

@@ -39,11 +39,10 @@ typedef unsigned long long vol_u64;
 
 struct VolCls { uint8_t id[64]; };
 
-static inline int64_t vol_up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-static inline int64_t vol_g1_bytes(int64_t nk, int64_t V) { return vol_up256(2 * nk * V * (int64_t)sizeof(uint16_t)); }
-static inline int64_t vol_g2_bytes(int64_t nk, int64_t V) { return vol_up256(2 * nk * V * (int64_t)sizeof(int32_t)); }
-static inline int64_t vol_rc_bytes(int64_t nk, int64_t R) { return vol_up256(2 * nk * R * (int64_t)sizeof(int32_t)); }
-static inline int64_t vol_rf_bytes(int64_t nk, int64_t R) { return vol_up256(2 * nk * R); }
+static inline int64_t vol_g1_bytes(int64_t nk, int64_t V) { return lmn_up256(2 * nk * V * (int64_t)sizeof(uint16_t)); }
+static inline int64_t vol_g2_bytes(int64_t nk, int64_t V) { return lmn_up256(2 * nk * V * (int64_t)sizeof(int32_t)); }
+static inline int64_t vol_rc_bytes(int64_t nk, int64_t R) { return lmn_up256(2 * nk * R * (int64_t)sizeof(int32_t)); }
+static inline int64_t vol_rf_bytes(int64_t nk, int64_t R) { return lmn_up256(2 * nk * R); }
 
 __global__ __launch_bounds__(256) void vol_labels_kernel(const float* __restrict__ logits, const int64_t* __restrict__ plab,
                                                          const int64_t* __restrict__ target, int C, int64_t hw, int64_t total,
@@ -427,12 +426,8 @@ int lmn_volume_dist(const uint8_t* lab_pred, const uint8_t* lab_target, int D, i
   int32_t* rowcnt = (int32_t*)((uint8_t*)d2 + vol_g2_bytes(nk, V));
   uint8_t* rowflag = (uint8_t*)rowcnt + vol_rc_bytes(nk, R);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(stats_i, 0, sizeof(int64_t) * VOL_NSTAT_I * (size_t)nk, st);
-  if (e == hipSuccess) e = hipMemsetAsync(rowflag, 0, (size_t)(2 * nk * R), st);
-  if (e != hipSuccess) {
-    snprintf(g_lmn_err, sizeof(g_lmn_err), "volume_dist: %s", hipGetErrorString(e));
-    return (int)e;
-  }
+  LMN_HIP_OK(hipMemsetAsync(stats_i, 0, sizeof(int64_t) * VOL_NSTAT_I * (size_t)nk, st), "volume_dist");
+  LMN_HIP_OK(hipMemsetAsync(rowflag, 0, (size_t)(2 * nk * R), st), "volume_dist");
   const int xt = lmn_cdiv(W, 64);
   LMN_LAUNCH(vol_z_kernel, dim3(xt, H, 2 * nk), dim3(64, VOL_SEG), 0, st, lab_pred, lab_target, nk, D, H, W, cls, g1, rowflag,
              (vol_u64*)stats_i);

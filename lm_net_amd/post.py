@@ -65,6 +65,47 @@ def default_palette(n_classes):
     return pal
 
 
+def _clean_args(cls, size, n_classes, classes, min_size, fill_holes):
+    """The constructor checks DevicePostprocess and VolumePostprocess share -> (classes, {class: minimal size}, hole_limit).
+    cls: the class name of the messages; size: its word for what a component measures, "area" or "volume"."""
+    if not 2 <= n_classes <= 64:
+        raise ValueError("%s: n_classes = %d outside [2, 64]" % (cls, n_classes))
+    classes = list(range(1, n_classes)) if classes is None else [int(k) for k in classes]
+    if len(set(classes)) != len(classes) or any(not 1 <= k < n_classes for k in classes):
+        raise ValueError("%s: classes %r must be distinct ids in [1, %d) (background is never removed)" % (cls, classes, n_classes))
+    if isinstance(min_size, (int, np.integer)):
+        sizes = {k: int(min_size) for k in classes}
+    else:
+        if len(min_size) != len(classes):
+            raise ValueError("%s: min_%s needs one entry per class in classes (%d)" % (cls, size, len(classes)))
+        sizes = {k: int(a) for k, a in zip(classes, min_size)}
+    if any(a < 0 or a > _INT32_MAX for a in sizes.values()):
+        raise ValueError("%s: min_%s must be in [0, 2^31)" % (cls, size))
+    if isinstance(fill_holes, (bool, np.bool_)):
+        hole_limit = _INT32_MAX if fill_holes else 0
+    else:
+        hole_limit = int(fill_holes)
+        if not 0 <= hole_limit <= _INT32_MAX:
+            raise ValueError("%s: fill_holes = %r: a bool or a maximal hole %s in [0, 2^31)" % (cls, fill_holes, size))
+    return classes, sizes, hole_limit
+
+
+def _check_pred(cls, what, batch, n_classes, pred):
+    """A prediction as both cleaners take it: fp32 logits [batch, C, H, W] or a uint8 / int64 label map [batch, H, W] on the device
+    -> (contiguous pred, batch size, H, W).  cls, what: the class and method name of the messages; batch: its letter for the batch."""
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        raise RuntimeError("lm_net_amd.%s%s: device tensors required (the HIP path has no CPU path)" % (cls, what))
+    if pred.dim() == 4 and pred.is_floating_point():
+        if pred.shape[1] != n_classes:
+            raise ValueError("%s: logits with %d channels, n_classes = %d" % (cls, pred.shape[1], n_classes))
+        pred = pred.contiguous().float()
+    elif pred.dim() == 3 and pred.dtype in (torch.uint8, torch.int64):
+        pred = pred.contiguous()
+    else:
+        raise ValueError("%s: pred must be logits [%s, C, H, W] or a uint8 / int64 label map [%s, H, W]" % (cls, batch, batch))
+    return pred, int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
+
+
 class DevicePostprocess:
     """post(pred, src_hw=None, frames=None) -> PostOutput(labels_net, labels, overlay, stats); see the module docstring.
 
@@ -80,34 +121,15 @@ class DevicePostprocess:
 
     def __init__(self, n_classes, connectivity=8, classes=None, keep_largest=False, min_area=0, fill_holes=False, palette=None,
                  alpha=1.0, overlay="fill"):
-        if not 2 <= n_classes <= 64:
-            raise ValueError("DevicePostprocess: n_classes = %d outside [2, 64]" % n_classes)
+        classes, areas, hole_limit = _clean_args("DevicePostprocess", "area", n_classes, classes, min_area, fill_holes)
         if connectivity not in (4, 8):
             raise ValueError("DevicePostprocess: connectivity %r is neither 4 nor 8" % (connectivity,))
-        classes = list(range(1, n_classes)) if classes is None else [int(k) for k in classes]
-        if len(set(classes)) != len(classes) or any(not 1 <= k < n_classes for k in classes):
-            raise ValueError("DevicePostprocess: classes %r must be distinct ids in [1, %d) (background is never removed)"
-                             % (classes, n_classes))
         if isinstance(keep_largest, (bool, np.bool_)):
             largest = list(classes) if keep_largest else []
         else:
             largest = [int(k) for k in keep_largest]
             if any(k not in classes for k in largest):
                 raise ValueError("DevicePostprocess: keep_largest %r names a class outside classes %r" % (largest, classes))
-        if isinstance(min_area, (int, np.integer)):
-            areas = {k: int(min_area) for k in classes}
-        else:
-            if len(min_area) != len(classes):
-                raise ValueError("DevicePostprocess: min_area needs one entry per class in classes (%d)" % len(classes))
-            areas = {k: int(a) for k, a in zip(classes, min_area)}
-        if any(a < 0 or a > _INT32_MAX for a in areas.values()):
-            raise ValueError("DevicePostprocess: min_area must be in [0, 2^31)")
-        if isinstance(fill_holes, (bool, np.bool_)):
-            hole_limit = _INT32_MAX if fill_holes else 0
-        else:
-            hole_limit = int(fill_holes)
-            if not 0 <= hole_limit <= _INT32_MAX:
-                raise ValueError("DevicePostprocess: fill_holes = %r: a bool or a maximal hole area in [0, 2^31)" % (fill_holes,))
         if overlay not in ("fill", "contour"):
             raise ValueError("DevicePostprocess: overlay %r is neither 'fill' nor 'contour'" % (overlay,))
         pal = default_palette(n_classes) if palette is None else np.asarray(palette)
@@ -125,17 +147,7 @@ class DevicePostprocess:
             self.params.min_area[k] = a
 
     def _pred(self, pred, what):
-        if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
-            raise RuntimeError("lm_net_amd.DevicePostprocess%s: device tensors required (the HIP path has no CPU path)" % what)
-        if pred.dim() == 4 and pred.is_floating_point():
-            if pred.shape[1] != self.n:
-                raise ValueError("DevicePostprocess: logits with %d channels, n_classes = %d" % (pred.shape[1], self.n))
-            pred = pred.contiguous().float()
-        elif pred.dim() == 3 and pred.dtype in (torch.uint8, torch.int64):
-            pred = pred.contiguous()
-        else:
-            raise ValueError("DevicePostprocess: pred must be logits [B, C, H, W] or a uint8 / int64 label map [B, H, W]")
-        B, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]
+        pred, B, H, W = _check_pred("DevicePostprocess", what, "B", self.n, pred)
         if B < 1 or not (2 <= H <= 1024 and 2 <= W <= 1024):
             raise ValueError("DevicePostprocess: B=%d, %dx%d outside B >= 1, sides in [2, 1024]" % (B, H, W))
         return pred, B, H, W
@@ -232,14 +244,9 @@ class VolumePostprocess:
     is an integer: two calls on one input give bit-identical outputs.  Not recorded by plans."""
 
     def __init__(self, n_classes, connectivity=26, classes=None, keep_largest=False, min_volume=0, fill_holes=False, workspace_mb=2048):
-        if not 2 <= n_classes <= 64:
-            raise ValueError("VolumePostprocess: n_classes = %d outside [2, 64]" % n_classes)
+        classes, volumes, hole_limit = _clean_args("VolumePostprocess", "volume", n_classes, classes, min_volume, fill_holes)
         if connectivity not in (6, 18, 26):
             raise ValueError("VolumePostprocess: connectivity %r is none of 6, 18, 26" % (connectivity,))
-        classes = list(range(1, n_classes)) if classes is None else [int(k) for k in classes]
-        if len(set(classes)) != len(classes) or any(not 1 <= k < n_classes for k in classes):
-            raise ValueError("VolumePostprocess: classes %r must be distinct ids in [1, %d) (background is never removed)"
-                             % (classes, n_classes))
         if isinstance(keep_largest, (bool, np.bool_)):
             keep = {k: 1 for k in classes} if keep_largest else {}
         elif isinstance(keep_largest, (int, np.integer)):
@@ -253,20 +260,6 @@ class VolumePostprocess:
                              % (keep_largest, hip.VOLPOST_MAX_KEEP))
         if any(not 1 <= n <= hip.VOLPOST_MAX_KEEP for n in keep.values()):
             raise ValueError("VolumePostprocess: keep_largest = %r: component counts must be in [1, %d]" % (keep_largest, hip.VOLPOST_MAX_KEEP))
-        if isinstance(min_volume, (int, np.integer)):
-            volumes = {k: int(min_volume) for k in classes}
-        else:
-            if len(min_volume) != len(classes):
-                raise ValueError("VolumePostprocess: min_volume needs one entry per class in classes (%d)" % len(classes))
-            volumes = {k: int(a) for k, a in zip(classes, min_volume)}
-        if any(a < 0 or a > _INT32_MAX for a in volumes.values()):
-            raise ValueError("VolumePostprocess: min_volume must be in [0, 2^31)")
-        if isinstance(fill_holes, (bool, np.bool_)):
-            hole_limit = _INT32_MAX if fill_holes else 0
-        else:
-            hole_limit = int(fill_holes)
-            if not 0 <= hole_limit <= _INT32_MAX:
-                raise ValueError("VolumePostprocess: fill_holes = %r: a bool or a maximal hole volume in [0, 2^31)" % (fill_holes,))
         if not workspace_mb > 0:
             raise ValueError("VolumePostprocess: workspace_mb must be positive")
         self.n, self.connectivity, self.classes = n_classes, connectivity, classes
@@ -279,19 +272,6 @@ class VolumePostprocess:
         self._l0.connectivity = 8                                          # (checked by the entry, used by nothing on this route)
         self._case, self._depth = None, 0                                  # uint8 [capacity, H, W]; slices pushed
 
-    def _pred(self, pred, what):
-        if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
-            raise RuntimeError("lm_net_amd.VolumePostprocess%s: device tensors required (the HIP path has no CPU path)" % what)
-        if pred.dim() == 4 and pred.is_floating_point():
-            if pred.shape[1] != self.n:
-                raise ValueError("VolumePostprocess: logits with %d channels, n_classes = %d" % (pred.shape[1], self.n))
-            pred = pred.contiguous().float()
-        elif pred.dim() == 3 and pred.dtype in (torch.uint8, torch.int64):
-            pred = pred.contiguous()
-        else:
-            raise ValueError("VolumePostprocess: pred must be logits [n, C, H, W] or a uint8 / int64 label map [n, H, W]")
-        return pred, int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
-
     def scratch_bytes(self, D, H, W):
         """Bytes of scratch one case of D x H x W voxels needs; ValueError when that exceeds workspace_mb."""
         need = hip.volpost_workspace(D, H, W)
@@ -303,7 +283,7 @@ class VolumePostprocess:
     @torch.no_grad()
     def push(self, pred):
         """Append n consecutive slices of the current case: fp32 logits [n, C, H, W] or a uint8 / int64 label map [n, H, W]."""
-        pred, n, H, W = self._pred(pred, ".push")
+        pred, n, H, W = _check_pred("VolumePostprocess", ".push", "n", self.n, pred)
         side = hip.VOLPOST_MAX_SIDE
         if n < 1:
             raise ValueError("VolumePostprocess.push: no slices")

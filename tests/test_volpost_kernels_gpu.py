@@ -79,13 +79,32 @@ def test_uint8_label_maps_with_out_of_range_values(connectivity, C):
     assert (lab8 >= C).any() and np.array_equal(_np(out.labels), L2) and np.array_equal(_np(out.stats), stats)
 
 
+ONE_SLICE_SHAPES = [(1, 8, 8), (1, 33, 65), (1, 70, 130)]
+
+
+def _seam_pairs(roots):
+    """Same-component pixel pairs of the restatement's roots across row 32 and across column 64 (the first tile seams)."""
+    r = roots[0]
+    return int((r[31] == r[32]).sum()), int((r[:, 63] == r[:, 64]).sum())
+
+
+@pytest.mark.parametrize("shape", ONE_SLICE_SHAPES, ids=ids)
 @pytest.mark.parametrize("connectivity", [6, 26])
-def test_one_slice_equals_the_2d_cleaning(connectivity):
-    """(1, 8, 8) with fill_holes=False: labels and stats equal DevicePostprocess(connectivity=4 | 8) on the same map."""
+def test_one_slice_equals_the_2d_cleaning(connectivity, shape):
+    """One slice with fill_holes=False: labels, stats, roots and sizes equal DevicePostprocess(connectivity=4 | 8) on the same map.
+    (1, 8, 8) is a single tile; (1, 33, 65) is one pixel past a tile seam in each direction; (1, 70, 130) has two seams along each
+    axis and ragged last tiles, so the 2D and the 3D kernels feed the shared tile and seam passes with different pointers and bases.
+    Decided on the restatement alone first: where the shape has seams a component crosses row 32 and one crosses column 64, and the
+    cleaning removes a component -- otherwise a seam bug would hide."""
     from lm_net_amd import VolumePostprocess
     from lm_net_amd.post import DevicePostprocess
     for C in (2, 4, 9):
-        pred = _device_pred("labels", (1, 8, 8), C)
+        if shape[1] > 32:                                                     # (both seam shapes have seams along both axes)
+            want_r, _ = _ref_components("labels", shape, C, connectivity)
+            _, want_stats, _ = R.clean(R.blob_labels(shape, C), C, connectivity, keep_largest=True, min_volume=2)
+            rows, cols = _seam_pairs(want_r)
+            assert rows >= 1 and cols >= 1 and (want_stats[:, 0] - want_stats[:, 1]).sum() >= 1
+        pred = _device_pred("labels", shape, C)
         a = VolumePostprocess(C, connectivity=connectivity, keep_largest=True, min_volume=2)(pred)
         b = DevicePostprocess(C, connectivity=4 if connectivity == 6 else 8, keep_largest=True, min_area=2)(pred)
         assert torch.equal(a.labels, b.labels_net) and torch.equal(a.stats, b.stats[0])
