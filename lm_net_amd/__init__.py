@@ -11,6 +11,8 @@ best threshold of any thresholded metric from on-device score histograms),
 without a host decision; ``lm_net_amd.optim.decay_groups``), ``lm_net_amd.metrics.ConfusionMeter`` (on-device Dice / IoU),
 ``lm_net_amd.metrics.SurfaceDistanceMeter`` (on-device HD / HD95 / ASSD / RVD),
 ``lm_net_amd.metrics.VolumeSurfaceMeter`` (per-case 3D Dice / HD / HD95 / ASSD / RVD of a label volume with integer voxel pitches),
+``lm_net_amd.metrics.LesionMeter`` (per-lesion detection, lesion-wise F1 and panoptic quality: the join of the 3D components of prediction
+and target in a device hash table),
 ``lm_net_amd.post.DevicePostprocess`` (on-device arg-max, connected-component cleaning, resize back to the frame, overlay),
 ``lm_net_amd.post.VolumePostprocess`` (3D connected-component cleaning of a whole case: the n largest components of an organ, a minimal
 volume, cavity filling, between the prediction and ``VolumeSurfaceMeter``),
@@ -19,7 +21,8 @@ volume, cavity filling, between the prediction and ``VolumeSurfaceMeter``),
 """
 from .LM_Net import LM_Net  # noqa: F401
 from .loss import FocalLoss, SegLoss, SigmoidSegLoss  # noqa: F401
-from .metrics import CurveMeter, ImageStatsMeter, SigmoidStatsMeter, VolumeSurfaceMeter  # noqa: F401
+from .metrics import CurveMeter, ImageStatsMeter, LesionMeter, SigmoidStatsMeter, VolumeSurfaceMeter  # noqa: F401
 from .post import VolumePostprocess  # noqa: F401
 
-__all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter", "VolumeSurfaceMeter", "VolumePostprocess"]
+__all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter", "VolumeSurfaceMeter", "VolumePostprocess",
+           "LesionMeter"]

@@ -318,6 +318,15 @@ VOLPOST_MAX_SIDE = 1024      # LMN_VOLPOST_* of the header
 VOLPOST_MAX_KEEP = 4
 VOLPOST_NSTAT = 4
 
+# include/lesion/lmnet_lesion.h: the components of a predicted and a target volume and the join between them (lm_net_amd.metrics.
+# LesionMeter).  A list of its own for the same reason, and no struct; tests/test_lesion_cpu.py checks it against the header and ties
+# lmn_lesion_match to tests/test_guard_lesion_gpu.py.
+SYMBOLS_LESION = ["lmn_lesion_workspace", "lmn_lesion_match"]
+LESION_MAX_SIDE = 1024       # LMN_LESION_* of the header
+LESION_MIN_SLOTS = 64
+LESION_MAX_SLOTS = 1 << 22
+LESION_NCTRL = 4
+
 _lib = None
 
 
@@ -331,7 +340,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -344,6 +353,7 @@ def load():
     lib.lmn_curve_workspace.restype = C.c_int64
     lib.lmn_volume_workspace.restype = C.c_int64
     lib.lmn_volpost_workspace.restype = C.c_int64
+    lib.lmn_lesion_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1443,6 +1453,37 @@ def volpost_clean(labels, n_classes, connectivity, class_mask, keep_largest, min
                                     keep, minv, int(hole_limit), _raw(workspace, torch.uint8, "volpost_clean"), _i64(workspace.numel()),
                                     _raw(labels_out, torch.uint8, "volpost_clean"), _raw(stats, torch.int32, "volpost_clean"), _stream()),
            "volpost_clean")
+
+
+def lesion_workspace(D, H, W):
+    """Bytes of scratch lmn_lesion_match needs for a D x H x W volume, exactly (host arithmetic, no GPU)."""
+    n = int(load().lmn_lesion_workspace(int(D), int(H), int(W)))
+    if n < 0:
+        raise ValueError("lm_net_amd.lesion_workspace: " + load().lmn_last_error().decode())
+    return n
+
+
+def lesion_match(pred, target, n_classes, connectivity, class_mask, workspace, comp_keys, comp_sizes, pair_keys, pair_counts, ctrl):
+    """lmn_lesion_match of ONE case: pred / target uint8 [D, H, W] device tensors -> the component records comp_keys int64 [M] /
+    comp_sizes int32 [M] (key = side << 40 | class << 32 | root), the pair table pair_keys int64 [S] / pair_counts int32 [S]
+    (key = root_p << 32 | root_g; S a power of two in [64, 2^22]) and ctrl int32 [4] (lesions found, pairs stored, insertions that
+    found the table full, 0).  Unused slots hold -1 / 0; the slot of a record depends on arrival order.  class_mask: bit k = class k
+    is scored; workspace: uint8 device tensor of at least lesion_workspace(D, H, W) bytes."""
+    if pred.dim() != 3 or pred.shape != target.shape:
+        raise ValueError("lm_net_amd.lesion_match: pred %s, target %s: two uint8 volumes [D, H, W] of one shape required"
+                         % (tuple(pred.shape), tuple(target.shape)))
+    if comp_keys.dim() != 1 or comp_sizes.shape != comp_keys.shape or pair_keys.dim() != 1 or pair_counts.shape != pair_keys.shape \
+            or ctrl.numel() != LESION_NCTRL:
+        raise ValueError("lm_net_amd.lesion_match: record buffers %s / %s, %s / %s, ctrl %s: keys and sizes [M], keys and counts [S] and "
+                         "ctrl [%d] required" % (tuple(comp_keys.shape), tuple(comp_sizes.shape), tuple(pair_keys.shape),
+                                                 tuple(pair_counts.shape), tuple(ctrl.shape), LESION_NCTRL))
+    D, H, W = (int(d) for d in pred.shape)
+    _check(load().lmn_lesion_match(_raw(pred, torch.uint8, "lesion_match"), _raw(target, torch.uint8, "lesion_match"), D, H, W, int(n_classes),
+                                   int(connectivity), C.c_uint64(int(class_mask)), _raw(workspace, torch.uint8, "lesion_match"),
+                                   _i64(workspace.numel()), _raw(comp_keys, torch.int64, "lesion_match"),
+                                   _raw(comp_sizes, torch.int32, "lesion_match"), int(comp_keys.numel()),
+                                   _raw(pair_keys, torch.int64, "lesion_match"), _raw(pair_counts, torch.int32, "lesion_match"),
+                                   int(pair_keys.numel()), _raw(ctrl, torch.int32, "lesion_match"), _stream()), "lesion_match")
 
 
 def _raw(t, dt, what):

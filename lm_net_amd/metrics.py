@@ -25,6 +25,10 @@ float64 on the host.
 ``VolumeSurfaceMeter`` scores a whole 3D case: Dice, Jaccard, HD, HD95, ASSD and RVD of the ``[D, H, W]`` label volume with integer
 voxel pitches (``medpy.metric.binary`` ``dc`` / ``jc`` / ``hd`` / ``hd95`` / ``assd`` / ``ravd`` per case), from the eleven exact raw
 statistics per (case, class) of ``lmn_volume_dist``; slices arrive batch by batch from a 2D validation loop (``push`` / ``close_case``).
+
+``LesionMeter`` scores a case per LESION: the 3D components of prediction and target (``lmn_cc3d_label``) and the join between them, a
+device hash table of component pairs with their shared voxel counts (``lmn_lesion_match``); detection by overlap, lesion-wise F1,
+panoptic quality and a lesion-wise Dice follow from those integers in float64 on the host (``lesion_metrics``).
 """
 import warnings
 
@@ -583,6 +587,34 @@ def surface_metrics(si, sf, classes, spacing=1.0):
     return out
 
 
+@torch.no_grad()
+def _push_slices(meter, what, pred, target):
+    """push() of the per-case meters (``what`` names the class in the messages): narrow n consecutive slices of the open case to uint8
+    on the device (lmn_volume_labels; 255 = no class) behind the ``meter._depth`` slices that ``meter._case`` = (lab_pred, lab_target),
+    uint8 [capacity, H, W], holds already.  The buffers grow by device copies; nothing synchronises."""
+    if not pred.is_cuda or not target.is_cuda:
+        raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % what)
+    pred = _prediction(pred, meter.n, what, torch.int64)
+    target = _target(target, pred, what)
+    n, H, W = target.shape
+    if n < 1:
+        raise ValueError("%s.push: no slices" % what)
+    if meter._case is not None and tuple(meter._case[0].shape[1:]) != (H, W):
+        raise ValueError("%s.push: slices of %dx%d into an open case of %dx%d" % ((what, H, W) + tuple(meter._case[0].shape[1:])))
+    if not (2 <= H <= hip.VOLUME_MAX_SIDE and 2 <= W <= hip.VOLUME_MAX_SIDE) or meter._depth + n > hip.VOLUME_MAX_SIDE:
+        raise ValueError("%s.push: a case of %d slices of %dx%d is outside 1 <= D <= %d, 2 <= H, W <= %d"
+                         % (what, meter._depth + n, H, W, hip.VOLUME_MAX_SIDE, hip.VOLUME_MAX_SIDE))
+    cap = 0 if meter._case is None else meter._case[0].shape[0]
+    if meter._depth + n > cap:                                   # grow the case buffers (device copy, no sync)
+        cap = min(max(meter._depth + n, 2 * cap), hip.VOLUME_MAX_SIDE)
+        grown = tuple(torch.empty(cap, H, W, device=pred.device, dtype=torch.uint8) for _ in range(2))
+        for new, old in zip(grown, meter._case or ()):
+            new[:meter._depth].copy_(old[:meter._depth])
+        meter._case = grown
+    hip.volume_labels(pred, target, meter.n, meter._case[0], meter._case[1], meter._depth)
+    meter._depth += n
+
+
 class VolumeSurfaceMeter:
     """Per-case 3D Dice, Jaccard, HD, HD95, ASSD and RVD per class of a label VOLUME, accumulated on the device: medpy.metric.binary
     dc, jc, hd, hd95, assd and ravd of the whole [D, H, W] case, the numbers of a CT results table.  (SurfaceDistanceMeter scores every
@@ -643,31 +675,10 @@ class VolumeSurfaceMeter:
                              % (D, H, W, need(1), self.workspace_bytes))
         return max(k for k in range(1, nk + 1) if need(k) <= self.workspace_bytes)
 
-    @torch.no_grad()
     def push(self, pred, target):
         """Append n consecutive slices of the current case: pred fp32 logits [n, C, H, W] or integer labels [n, H, W], target
         [n, H, W]."""
-        if not pred.is_cuda or not target.is_cuda:
-            raise RuntimeError("lm_net_amd.VolumeSurfaceMeter: device tensors required (the HIP path has no CPU fallback)")
-        pred = _prediction(pred, self.n, "VolumeSurfaceMeter", torch.int64)
-        target = _target(target, pred, "VolumeSurfaceMeter")
-        n, H, W = target.shape
-        if n < 1:
-            raise ValueError("VolumeSurfaceMeter.push: no slices")
-        if self._case is not None and tuple(self._case[0].shape[1:]) != (H, W):
-            raise ValueError("VolumeSurfaceMeter.push: slices of %dx%d into an open case of %dx%d" % ((H, W) + tuple(self._case[0].shape[1:])))
-        if not (2 <= H <= hip.VOLUME_MAX_SIDE and 2 <= W <= hip.VOLUME_MAX_SIDE) or self._depth + n > hip.VOLUME_MAX_SIDE:
-            raise ValueError("VolumeSurfaceMeter.push: a case of %d slices of %dx%d is outside 1 <= D <= %d, 2 <= H, W <= %d"
-                             % (self._depth + n, H, W, hip.VOLUME_MAX_SIDE, hip.VOLUME_MAX_SIDE))
-        cap = 0 if self._case is None else self._case[0].shape[0]
-        if self._depth + n > cap:                                # grow the case buffers (device copy, no sync)
-            cap = min(max(self._depth + n, 2 * cap), hip.VOLUME_MAX_SIDE)
-            grown = tuple(torch.empty(cap, H, W, device=pred.device, dtype=torch.uint8) for _ in range(2))
-            for new, old in zip(grown, self._case or ()):
-                new[:self._depth].copy_(old[:self._depth])
-            self._case = grown
-        hip.volume_labels(pred, target, self.n, self._case[0], self._case[1], self._depth)
-        self._depth += n
+        _push_slices(self, "VolumeSurfaceMeter", pred, target)
 
     @torch.no_grad()
     def close_case(self):
@@ -741,6 +752,261 @@ def volume_metrics(si, sf, classes, unit=1.0):
         out[key] = np.where(cnt > 0, np.where(ok, a, 0.0).sum(0) / np.maximum(cnt, 1), np.nan).tolist()
     d = np.asarray(out["dice"], dtype=np.float64)
     out["mean_dice"] = float(d[~np.isnan(d)].mean()) if (~np.isnan(d)).any() else float("nan")
+    return out
+
+
+class LesionMeter:
+    """Per-LESION detection and panoptic quality per class of a label volume, accumulated on the device: how many target lesions were
+    found, how many predicted lesions are false alarms, lesion-wise F1 and panoptic quality -- the lesion column of a results table,
+    which otherwise goes through .cpu() and scipy.ndimage.label for every case.  (The pooled meters cannot give it: a voxel-wise Dice
+    of 0.9 says nothing about a missed 30-voxel metastasis.)
+
+    For one case, Lp and Lt are the uint8 label volumes [D, H, W] of prediction and target; a 2D image is a one-slice case.  A value
+    >= C is read as 0 on both sides, so VOID TARGET VOXELS ARE BACKGROUND for this meter.
+      Lesions: for each scored class k (``classes``, default 1 .. C-1) the components of Lp == k (side 0, sizes n_p) and of Lt == k
+        (side 1, sizes n_g) under ``connectivity`` 6, 18 or 26 -- the components of lmn_cc3d_label.  The root of a lesion is its
+        smallest linear voxel index; it identifies the lesion and its class.
+      Pairs: for every pair (p, g) of the same class that shares a voxel, n_pg is the number of shared voxels.
+      Detection by overlap (``overlap`` = tau in [0, 1], default 0; ``min_size``, default 0): components with fewer than min_size
+        voxels are dropped from both sides, and their pairs go with them.  o_g = sum_p n_pg, o_p = sum_g n_pg.  g is detected iff
+        o_g >= 1 and o_g >= tau n_g; p is a hit iff o_p >= 1 and o_p >= tau n_p (both comparisons in float64).  det_tp, det_fn =
+        |G| - det_tp, det_fp = the p that are no hit; sensitivity = det_tp / |G|, precision = (|P| - det_fp) / |P|, f1 = 2sp / (s + p)
+        and 0 when s + p = 0; a ratio is nan where its denominator is 0.
+      Matching by IoU (``iou`` = theta in [0.5, 1), default 0.5): (p, g) is matched iff n_pg / (n_p + n_g - n_pg) > theta, which is
+        unique because theta >= 0.5.  tp, fp = |P| - tp, fn = |G| - tp; sq = sum IoU / tp, rq = tp / (tp + fp/2 + fn/2), pq = sq rq:
+        0 when tp = 0 and the denominator is positive, nan when there are no lesions on either side.  lesion_dice = the sum over the
+        matched pairs of 2 n_pg / (n_p + n_g), divided by tp + fp + fn: in the spirit of the BraTS lesion-wise Dice, without its
+        dilation; it is not that challenge's code.
+      Reductions: 'pooled' sums the counts over the cases and applies the formulas; 'per_case' holds arrays [N, len(classes)]; 'mean'
+        is the nanmean of per_case over the cases; sensitivity_by_size(bins) is the pooled sensitivity per stratum of n_g.
+
+    push(pred, target), close_case() and update(pred, target) work as in VolumeSurfaceMeter; update_images(pred, target) scores each
+    image of a [B, H, W] batch as a one-slice case.  A case may hold ``max_components`` lesions (both sides, all scored classes) and
+    ``max_pairs`` pairs (the table has the power of two >= 2 max_pairs slots); compute() raises when a case had more.  close_case()
+    needs 16 bytes of scratch per voxel, checked against ``workspace_mb`` there.  Only compute() and sensitivity_by_size() synchronise
+    with the host."""
+
+    def __init__(self, n_classes, classes=None, connectivity=26, max_components=8192, max_pairs=8192, workspace_mb=2048, device="cuda"):
+        if not 2 <= n_classes <= 64:
+            raise ValueError("LesionMeter: n_classes = %d outside [2, 64]" % n_classes)
+        classes = list(range(1, n_classes)) if classes is None else [int(k) for k in classes]
+        if not classes or len(set(classes)) != len(classes) or min(classes) < 1 or max(classes) >= n_classes:
+            raise ValueError("LesionMeter: classes %r must be distinct ids in [1, %d)" % (classes, n_classes))
+        if connectivity not in (6, 18, 26):
+            raise ValueError("LesionMeter: connectivity %r is none of 6, 18, 26" % (connectivity,))
+        if int(max_components) != max_components or not 1 <= max_components < 2 ** 31:
+            raise ValueError("LesionMeter: max_components %r must be an integer in [1, 2^31)" % (max_components,))
+        if int(max_pairs) != max_pairs or not 1 <= 2 * max_pairs <= hip.LESION_MAX_SLOTS:
+            raise ValueError("LesionMeter: max_pairs %r must be an integer in [1, %d]" % (max_pairs, hip.LESION_MAX_SLOTS // 2))
+        if not workspace_mb > 0:
+            raise ValueError("LesionMeter: workspace_mb must be positive")
+        self.n, self.classes, self.device, self.connectivity = n_classes, classes, torch.device(device), int(connectivity)
+        self.class_mask = sum(1 << k for k in classes)
+        self.max_components, self.max_pairs = int(max_components), int(max_pairs)
+        self.pair_slots = hip.LESION_MIN_SLOTS
+        while self.pair_slots < 2 * self.max_pairs:
+            self.pair_slots *= 2
+        self.workspace_bytes = int(workspace_mb * (1 << 20))
+        self.reset()
+
+    def reset(self):
+        self._rec = []                                           # per closed case (or add_raw): the five record tensors, [n, ...]
+        self._case, self._depth = None, 0                        # (lab_pred, lab_target) uint8 [capacity, H, W]; slices pushed
+
+    def scratch_bytes(self, D, H, W):
+        """Bytes of scratch close_case() takes for a D x H x W case; raises where workspace_mb does not allow them."""
+        need = hip.lesion_workspace(D, H, W)
+        if need > self.workspace_bytes:
+            raise ValueError("LesionMeter: a %dx%dx%d case needs %d bytes of scratch, workspace_mb allows %d"
+                             % (D, H, W, need, self.workspace_bytes))
+        return need
+
+    def push(self, pred, target):
+        """Append n consecutive slices of the current case: pred fp32 logits [n, C, H, W] or integer labels [n, H, W], target
+        [n, H, W]."""
+        _push_slices(self, "LesionMeter", pred, target)
+
+    @torch.no_grad()
+    def close_case(self):
+        """Match the lesions of the slices pushed since the last case and append its records in canonical order: sorted by key, the
+        empty slots last (a device sort, no sync)."""
+        if self._case is None or self._depth == 0:
+            raise ValueError("LesionMeter.close_case: no slices were pushed")
+        (lab_p, lab_t), D = self._case, self._depth
+        H, W = lab_p.shape[1:]
+        self._case, self._depth = None, 0
+        dev = lab_p.device
+        ws = torch.empty(self.scratch_bytes(D, H, W), device=dev, dtype=torch.uint8)
+        ck = torch.empty(self.max_components, device=dev, dtype=torch.int64)
+        cs = torch.empty(self.max_components, device=dev, dtype=torch.int32)
+        pk = torch.empty(self.pair_slots, device=dev, dtype=torch.int64)
+        pc = torch.empty(self.pair_slots, device=dev, dtype=torch.int32)
+        ctrl = torch.empty(hip.LESION_NCTRL, device=dev, dtype=torch.int32)
+        hip.lesion_match(lab_p[:D], lab_t[:D], self.n, self.connectivity, self.class_mask, ws, ck, cs, pk, pc, ctrl)
+        ck, cs = _canonical_records(ck, cs)
+        pk, pc = _canonical_records(pk, pc)
+        self._rec.append((ck[None], cs[None], pk[None], pc[None], ctrl[None]))
+
+    def update(self, pred, target):
+        """Score one whole case: push + close_case."""
+        if self._depth:
+            raise ValueError("LesionMeter.update: a case with %d pushed slices is open; close_case() first" % self._depth)
+        self.push(pred, target)
+        self.close_case()
+
+    def update_images(self, pred, target):
+        """Score every image of a batch as a one-slice case: pred fp32 logits [B, C, H, W] or integer labels [B, H, W], target
+        [B, H, W]."""
+        if self._depth:
+            raise ValueError("LesionMeter.update_images: a case with %d pushed slices is open; close_case() first" % self._depth)
+        if target.dim() != 3 or pred.shape[0] != target.shape[0]:
+            raise ValueError("LesionMeter.update_images: pred %s, target %s: a batch [B, H, W] required"
+                             % (tuple(pred.shape), tuple(target.shape)))
+        for b in range(target.shape[0]):
+            self.update(pred[b:b + 1], target[b:b + 1])
+
+    def _shapes(self):
+        return ((self.max_components,), (self.max_components,), (self.pair_slots,), (self.pair_slots,), (hip.LESION_NCTRL,))
+
+    RAW_DTYPES = (torch.int64, torch.int32, torch.int64, torch.int32, torch.int32)
+
+    def add_raw(self, comp_keys, comp_sizes, pair_keys, pair_counts, ctrl):
+        """Append records ([N, max_components] int64 / int32, [N, pair_slots] int64 / int32, [N, 4] int32), e.g. another rank's
+        raw()."""
+        rec = (comp_keys, comp_sizes, pair_keys, pair_counts, ctrl)
+        if any(t.dim() != 2 or tuple(t.shape[1:]) != s or t.shape[0] != ctrl.shape[0] for t, s in zip(rec, self._shapes())):
+            raise ValueError("LesionMeter.add_raw: shapes %s; [N, ...] of %s required" % ([tuple(t.shape) for t in rec], list(self._shapes())))
+        self._rec.append(tuple(t.to(self.device, dt) for t, dt in zip(rec, self.RAW_DTYPES)))
+
+    def raw(self):
+        """The records of the closed cases, in order, on the meter's device: comp_keys int64 [N, max_components] (side << 40 | class << 32
+        | root) and comp_sizes int32; pair_keys int64 [N, pair_slots] (root_p << 32 | root_g) and pair_counts int32; ctrl int32 [N, 4]
+        (lesions found, pairs stored, pair insertions dropped, 0).  Each case sorted by key, unused slots (-1 / 0) last: two runs on
+        one input are bit-identical."""
+        if not self._rec:
+            return tuple(torch.zeros((0,) + s, device=self.device, dtype=dt) for s, dt in zip(self._shapes(), self.RAW_DTYPES))
+        return tuple(torch.cat(ts) for ts in zip(*self._rec))
+
+    def compute(self, overlap=0.0, iou=0.5, min_size=0):
+        """lesion_metrics of the records (the one synchronising call): {'classes', 'pooled', 'per_case', 'mean'}.  Raises ValueError
+        for a case that found more lesions than max_components or dropped a pair insertion."""
+        return lesion_metrics(tuple(t.cpu().numpy() for t in self.raw()), self.classes, overlap=overlap, iou=iou, min_size=min_size)
+
+    def sensitivity_by_size(self, bins, overlap=0.0, min_size=0):
+        """Pooled sensitivity per stratum [bins[i], bins[i + 1]) of the target lesion size n_g: {'bins', 'n_target', 'det_tp',
+        'sensitivity'}, the last three [len(bins) - 1, len(classes)]."""
+        return lesion_metrics(tuple(t.cpu().numpy() for t in self.raw()), self.classes, overlap=overlap, min_size=min_size,
+                              size_bins=bins)["by_size"]
+
+
+def _canonical_records(keys, values):
+    """Records of one case sorted by key with the empty slots (key -1, value 0) last, on the device.  (A key is below 2^62, so
+    clearing the sign bit leaves it alone and turns -1 into the largest int64.)"""
+    top = torch.iinfo(torch.int64).max
+    k, order = torch.sort(keys & top)
+    return torch.where(k == top, torch.full_like(k, -1), k), values[order]
+
+
+LESION_COUNTS = ("n_pred", "n_target", "det_tp", "det_fn", "det_fp", "tp", "fp", "fn")
+LESION_SCORES = ("sensitivity", "precision", "f1", "sq", "rq", "pq", "lesion_dice")
+
+
+def _lesion_scores(c, sum_iou, sum_dice):
+    """The formulas of LesionMeter on count arrays (a dictionary of LESION_COUNTS) and the sums over the matched pairs, float64."""
+    f = {k: np.asarray(v, dtype=np.float64) for k, v in c.items()}
+    sum_iou, sum_dice = np.asarray(sum_iou, dtype=np.float64), np.asarray(sum_dice, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = _nan_div(f["det_tp"], f["n_target"])
+        p = _nan_div(f["n_pred"] - f["det_fp"], f["n_pred"])
+        f1 = np.where(s + p == 0, 0.0, 2 * s * p / (s + p))           # (nan where s or p is)
+        den = f["tp"] + 0.5 * f["fp"] + 0.5 * f["fn"]
+        sq = _nan_div(sum_iou, f["tp"])
+        rq = _nan_div(f["tp"], den)
+        pq = np.where(den > 0, np.where(f["tp"] > 0, sq * rq, 0.0), np.nan)
+        ld = _nan_div(sum_dice, f["tp"] + f["fp"] + f["fn"])
+    return dict(sensitivity=s, precision=p, f1=f1, sq=sq, rq=rq, pq=pq, lesion_dice=ld)
+
+
+def lesion_metrics(records, classes, overlap=0.0, iou=0.5, min_size=0, size_bins=None):
+    """LesionMeter.compute() of records = (comp_keys [N, M], comp_sizes [N, M], pair_keys [N, S], pair_counts [N, S], ctrl [N, 4]) as
+    LesionMeter.raw() returns them (numpy; the order of the records of a case does not matter here).  Integers and float64 throughout.
+    Returns {'classes', 'pooled': counts (LESION_COUNTS) and scores (LESION_SCORES) per class, 'per_case': the same as [N, nk] arrays,
+    'mean': the nanmean of the per-case scores over the cases}, plus 'by_size' when size_bins is given."""
+    ck, cs, pk, pc, ctrl = (np.asarray(a) for a in records)
+    if not 0.0 <= overlap <= 1.0:
+        raise ValueError("lesion_metrics: overlap %r outside [0, 1]" % (overlap,))
+    if not 0.5 <= iou < 1.0:
+        raise ValueError("lesion_metrics: iou %r outside [0.5, 1): below 0.5 a match is not unique" % (iou,))
+    if int(min_size) != min_size or min_size < 0:
+        raise ValueError("lesion_metrics: min_size %r must be an integer >= 0" % (min_size,))
+    N, nk = ck.shape[0], len(classes)
+    for n in range(N):
+        if ctrl[n, 0] > ck.shape[1]:
+            raise ValueError("lesion_metrics: case %d has %d lesions, max_components allows %d" % (n, ctrl[n, 0], ck.shape[1]))
+        if ctrl[n, 2] > 0:
+            raise ValueError("lesion_metrics: case %d dropped %d pair insertions: its table of %d slots (2 max_pairs, rounded up) is "
+                             "full" % (n, ctrl[n, 2], pk.shape[1]))
+    col = np.full(256, -1, np.int64)                                  # class id -> column of `classes`
+    col[[int(k) for k in classes]] = np.arange(nk)
+    counts = {k: np.zeros((N, nk), np.int64) for k in LESION_COUNTS}
+    sum_iou, sum_dice = np.zeros((N, nk)), np.zeros((N, nk))
+    edges = None
+    if size_bins is not None:
+        edges = np.asarray(size_bins, dtype=np.float64)
+        if edges.ndim != 1 or edges.size < 2 or not (np.diff(edges) > 0).all():
+            raise ValueError("lesion_metrics: size_bins %r must be at least two ascending edges" % (size_bins,))
+        bin_n, bin_tp = np.zeros((edges.size - 1, nk), np.int64), np.zeros((edges.size - 1, nk), np.int64)
+    for n in range(N):
+        ok = ck[n] >= 0
+        key, size = ck[n][ok].astype(np.int64), cs[n][ok].astype(np.int64)
+        keep = size >= min_size
+        key, size = key[keep], size[keep]
+        side, root = key >> 40, key & 0xFFFFFFFF
+        cj = col[(key >> 32) & 0xFF]
+        on = cj >= 0                                                  # (records of a class this call does not score)
+        P, G = np.flatnonzero((side == 0) & on), np.flatnonzero((side == 1) & on)
+        P, G = P[np.argsort(root[P], kind="stable")], G[np.argsort(root[G], kind="stable")]
+        ok = pk[n] >= 0
+        pkey, npg = pk[n][ok].astype(np.int64), pc[n][ok].astype(np.int64)
+        ip, ig = np.searchsorted(root[P], pkey >> 32), np.searchsorted(root[G], pkey & 0xFFFFFFFF)
+        # a pair whose lesion was dropped by min_size, or is of a class outside `classes`, goes with it
+        live = (ip < P.size) & (ig < G.size)
+        live[live] = (root[P][ip[live]] == pkey[live] >> 32) & (root[G][ig[live]] == pkey[live] & 0xFFFFFFFF)
+        ip, ig, npg = ip[live], ig[live], npg[live]
+        n_p, n_g = size[P], size[G]
+        o_p, o_g = np.bincount(ip, npg, P.size), np.bincount(ig, npg, G.size)          # float64 sums of integers < 2^53: exact
+        hit = (o_p >= 1) & (o_p >= overlap * n_p.astype(np.float64))
+        det = (o_g >= 1) & (o_g >= overlap * n_g.astype(np.float64))
+        union = (n_p[ip] + n_g[ig] - npg).astype(np.float64)
+        v_iou = npg / union
+        match = v_iou > iou
+        v_dice = 2 * npg / (n_p[ip] + n_g[ig]).astype(np.float64)
+        cP, cG = cj[P], cj[G]
+        counts["n_pred"][n] = np.bincount(cP, minlength=nk)
+        counts["n_target"][n] = np.bincount(cG, minlength=nk)
+        counts["det_tp"][n] = np.bincount(cG[det], minlength=nk)
+        counts["det_fp"][n] = np.bincount(cP[~hit], minlength=nk)
+        counts["tp"][n] = np.bincount(cP[ip[match]], minlength=nk)
+        sum_iou[n] = np.bincount(cP[ip[match]], v_iou[match], nk)
+        sum_dice[n] = np.bincount(cP[ip[match]], v_dice[match], nk)
+        if edges is not None:
+            b = np.searchsorted(edges, n_g, side="right") - 1
+            inb = (b >= 0) & (b < edges.size - 1)
+            np.add.at(bin_n, (b[inb], cG[inb]), 1)
+            np.add.at(bin_tp, (b[inb & det], cG[inb & det]), 1)
+    counts["det_fn"] = counts["n_target"] - counts["det_tp"]
+    counts["fp"] = counts["n_pred"] - counts["tp"]
+    counts["fn"] = counts["n_target"] - counts["tp"]
+    per_case = dict(counts, **_lesion_scores(counts, sum_iou, sum_dice))
+    pooled_counts = {k: v.sum(0) for k, v in counts.items()}
+    pooled = dict(pooled_counts, **_lesion_scores(pooled_counts, sum_iou.sum(0), sum_dice.sum(0)))
+    mean = {}
+    for k in LESION_SCORES:
+        mean[k] = _nanmean_last(per_case[k].T)
+    out = {"classes": list(classes), "pooled": pooled, "per_case": per_case, "mean": mean}
+    if edges is not None:
+        out["by_size"] = {"bins": edges.tolist(), "n_target": bin_n, "det_tp": bin_tp,
+                          "sensitivity": _nan_div(bin_tp, bin_n)}
     return out
 
 
