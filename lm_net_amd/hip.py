@@ -327,6 +327,21 @@ LESION_MIN_SLOTS = 64
 LESION_MAX_SLOTS = 1 << 22
 LESION_NCTRL = 4
 
+# include/distmap/lmnet_distmap.h: dense signed squared distance maps of label masks and the boundary / Hausdorff losses on them
+# (lm_net_amd.loss.distance_maps, BoundaryLoss, HausdorffDTLoss).  A list of its own for the same reason, and no struct;
+# tests/test_distmap_cpu.py checks it against the header and ties the three device entries to tests/test_guard_distmap_gpu.py.
+SYMBOLS_DISTMAP = ["lmn_dist_workspace", "lmn_dist_map", "lmn_dist_loss_fwd", "lmn_dist_loss_bwd"]
+DISTMAP_MAX_SIDE = 1024      # LMN_DISTMAP_* of the header
+DISTMAP_LABELS_U8 = 0
+DISTMAP_LABELS_I64 = 1
+DISTMAP_SOFTMAX = 0
+DISTMAP_SIGMOID = 1
+DISTMAP_FLAG_EMPTY = 1
+DISTMAP_FLAG_FULL = 2
+DISTMAP_BOUNDARY = 0
+DISTMAP_HAUSDORFF = 1
+DISTMAP_SUMS_WORDS = 4
+
 _lib = None
 
 
@@ -340,7 +355,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -354,6 +369,7 @@ def load():
     lib.lmn_volume_workspace.restype = C.c_int64
     lib.lmn_volpost_workspace.restype = C.c_int64
     lib.lmn_lesion_workspace.restype = C.c_int64
+    lib.lmn_dist_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1484,6 +1500,87 @@ def lesion_match(pred, target, n_classes, connectivity, class_mask, workspace, c
                                    _raw(comp_sizes, torch.int32, "lesion_match"), int(comp_keys.numel()),
                                    _raw(pair_keys, torch.int64, "lesion_match"), _raw(pair_counts, torch.int32, "lesion_match"),
                                    int(pair_keys.numel()), _raw(ctrl, torch.int32, "lesion_match"), _stream()), "lesion_match")
+
+
+def dist_workspace(B, nk, H, W):
+    """Bytes of scratch lmn_dist_map needs for B samples x nk classes of H x W pixels, exactly (host arithmetic, no GPU)."""
+    n = int(load().lmn_dist_workspace(int(B), int(nk), int(H), int(W)))
+    if n < 0:
+        raise ValueError("lm_net_amd.dist_workspace: " + load().lmn_last_error().decode())
+    return n
+
+
+def dist_label_kind(t):
+    """LMN_DISTMAP_LABELS_* of a label tensor: uint8 or int64."""
+    if t.dtype == torch.uint8:
+        return DISTMAP_LABELS_U8
+    if t.dtype == torch.int64:
+        return DISTMAP_LABELS_I64
+    raise ValueError("lm_net_amd: labels are uint8 or int64, got %s" % t.dtype)
+
+
+def _dist_nk(class_mask):
+    return bin(int(class_mask) & (2 ** 64 - 1)).count("1")
+
+
+def dist_map(src, n_classes, class_mask, workspace, sd2, flags, mode=None, threshold=0.0):
+    """sd2 int32 [B, nk, H, W] and flags int32 [B, nk] of the masks of the classes of class_mask (lmn_dist_map).  src: a uint8 / int64
+    label map [B, H, W] (mode None), or fp32 logits [B, C, H, W] with mode DISTMAP_SOFTMAX (threshold: a probability) or
+    DISTMAP_SIGMOID (threshold: a logit); workspace: uint8 device tensor of at least dist_workspace(B, nk, H, W) bytes."""
+    nk = _dist_nk(class_mask)
+    from_logits = mode is not None
+    if src.dim() != (4 if from_logits else 3) or not src.is_contiguous() or (from_logits and src.shape[1] != n_classes):
+        want = "logits [B, %d, H, W]" % n_classes if from_logits else "labels [B, H, W]"
+        raise ValueError("lm_net_amd.dist_map: src %s: contiguous %s required" % (tuple(src.shape), want))
+    B, H, W = src.shape[0], src.shape[-2], src.shape[-1]
+    if sd2.numel() != B * nk * H * W or flags.numel() != B * nk:
+        raise ValueError("lm_net_amd.dist_map: sd2 %s / flags %s do not hold [%d, %d, %d, %d] / [%d, %d]"
+                         % (tuple(sd2.shape), tuple(flags.shape), B, nk, H, W, B, nk))
+    logits = _p(src) if from_logits else None
+    labels = None if from_logits else _raw(src, src.dtype, "dist_map")
+    kind = DISTMAP_LABELS_U8 if from_logits else dist_label_kind(src)
+    _check(load().lmn_dist_map(logits, labels, kind, _f(threshold), int(mode or 0), B, int(n_classes), H, W, C.c_uint64(int(class_mask)),
+                               _raw(workspace, torch.uint8, "dist_map"), _i64(workspace.numel()), _raw(sd2, torch.int32, "dist_map"),
+                               _raw(flags, torch.int32, "dist_map"), _stream()), "dist_map")
+
+
+def _dist_loss_dims(what, logits, target, head, class_mask, sd2_g, sd2_p):
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise ValueError("lm_net_amd.%s: contiguous logits [B, C, H, W] required, got %s" % (what, tuple(logits.shape)))
+    B, Cn, H, W = logits.shape
+    want = (B, H, W) if head == DISTMAP_SOFTMAX else (B, Cn, H, W)
+    if tuple(target.shape) != want or not target.is_contiguous() or not target.is_cuda:
+        raise ValueError("lm_net_amd.%s: target %s: a contiguous device tensor %s required" % (what, tuple(target.shape), want))
+    nk = _dist_nk(class_mask)
+    for m in (sd2_g, sd2_p):
+        if m is not None and tuple(m.shape) != (B, nk, H, W):
+            raise ValueError("lm_net_amd.%s: distance map %s, expected %s" % (what, tuple(m.shape), (B, nk, H, W)))
+    return B, Cn, H, W
+
+
+def dist_loss_fwd(logits, target, head, term, alpha, scale, class_mask, sd2_g, sd2_p, sums, loss):
+    """loss[0] = scale * the boundary (DISTMAP_BOUNDARY, sd2_p None) or Hausdorff (DISTMAP_HAUSDORFF) term of fp32 logits [B, C, H, W]
+    under a softmax head (target: label map [B, H, W]) or a sigmoid head (target: planes [B, C, H, W]), uint8 or int64, on the maps
+    int32 [B, nk, H, W] of dist_map (lmn_dist_loss_fwd); sums: int32 workspace of DISTMAP_SUMS_WORDS words, read by dist_loss_bwd."""
+    B, Cn, H, W = _dist_loss_dims("dist_loss_fwd", logits, target, head, class_mask, sd2_g, sd2_p)
+    if sums.numel() < DISTMAP_SUMS_WORDS or loss.numel() < 1:
+        raise ValueError("lm_net_amd.dist_loss_fwd: sums needs %d words and loss one float" % DISTMAP_SUMS_WORDS)
+    _check(load().lmn_dist_loss_fwd(_p(logits), C.c_void_p(target.data_ptr()), dist_label_kind(target), int(head), int(term), _f(alpha),
+                                    _f(scale), B, Cn, H, W, C.c_uint64(int(class_mask)), _raw(sd2_g, torch.int32, "dist_loss_fwd"),
+                                    _raw(sd2_p, torch.int32, "dist_loss_fwd"), _raw(sums, torch.int32, "dist_loss_fwd"), _p(loss),
+                                    _stream()), "dist_loss_fwd")
+
+
+def dist_loss_bwd(logits, target, head, term, alpha, class_mask, sd2_g, sd2_p, sums, gscale, dlogits):
+    """dlogits = gscale[0] * d loss / d logits (gscale None: 1) from the sums of dist_loss_fwd on the same arguments
+    (lmn_dist_loss_bwd); every element of dlogits is written."""
+    B, Cn, H, W = _dist_loss_dims("dist_loss_bwd", logits, target, head, class_mask, sd2_g, sd2_p)
+    if sums.numel() < DISTMAP_SUMS_WORDS or tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous():
+        raise ValueError("lm_net_amd.dist_loss_bwd: sums needs %d words and dlogits the logits' shape" % DISTMAP_SUMS_WORDS)
+    _check(load().lmn_dist_loss_bwd(_p(logits), C.c_void_p(target.data_ptr()), dist_label_kind(target), int(head), int(term), _f(alpha),
+                                    B, Cn, H, W, C.c_uint64(int(class_mask)), _raw(sd2_g, torch.int32, "dist_loss_bwd"),
+                                    _raw(sd2_p, torch.int32, "dist_loss_bwd"), _raw(sums, torch.int32, "dist_loss_bwd"), _p(gscale),
+                                    _p(dlogits), _stream()), "dist_loss_bwd")
 
 
 def _raw(t, dt, what):

@@ -241,3 +241,229 @@ class SigmoidSegLoss(torch.nn.Module):
             raise RuntimeError("lm_net_amd.SigmoidSegLoss: device tensors required (the HIP path has no CPU fallback)")
         param = hip.sig_param(*self.args, target_kind=hip.sig_target_kind(target))
         return _SigmoidSegLossFn.apply(logits.float().contiguous(), target.contiguous(), w_bce, pos_w, w_dice, param, self)
+
+
+# ---------------------------------------------------------------------------------------------------------------- distance maps
+# Boundary and Hausdorff losses on dense signed distance maps (include/distmap/lmnet_distmap.h).  The map is stored as the signed
+# SQUARED distance, an exact int32; a plane whose mask is empty or the whole image is all 0 and flagged.
+_DIST_MODES = {"labels": None, "softmax": hip.DISTMAP_SOFTMAX, "sigmoid": hip.DISTMAP_SIGMOID}
+_DIST_MAX_CLASSES = 64
+
+
+def _dist_classes(what, n_classes, classes):
+    """(sorted class ids, class_mask).  None: 1 .. n_classes - 1, or class 0 when there is one class only."""
+    if int(n_classes) != n_classes or not 1 <= n_classes <= _DIST_MAX_CLASSES:
+        raise ValueError("%s: n_classes = %r outside [1, %d]" % (what, n_classes, _DIST_MAX_CLASSES))
+    if classes is None:
+        classes = list(range(1, n_classes)) if n_classes > 1 else [0]
+    ids = [int(k) for k in classes]
+    if not ids or len(set(ids)) != len(ids) or any(k != c for k, c in zip(ids, classes)) or min(ids) < 0 or max(ids) >= n_classes:
+        raise ValueError("%s: classes %r must be distinct integers in [0, %d)" % (what, list(classes), n_classes))
+    ids.sort()
+    return ids, sum(1 << k for k in ids)
+
+
+def _dist_check_size(what, B, nk, H, W):
+    if not (2 <= H <= hip.DISTMAP_MAX_SIDE and 2 <= W <= hip.DISTMAP_MAX_SIDE):
+        raise ValueError("%s: size %d x %d outside the limit 2 <= H, W <= %d" % (what, H, W, hip.DISTMAP_MAX_SIDE))
+    if B < 1 or B * nk * H * W >= 1 << 31:
+        raise ValueError("%s: B * nk * H * W = %d outside the limit [1, 2^31)" % (what, B * nk * H * W))
+
+
+def _dist_run(src, n_classes, class_mask, nk, mode, threshold):
+    """(sd2, flags) of a checked source: the scratch comes from the caching allocator, nothing synchronises."""
+    B, H, W = src.shape[0], src.shape[-2], src.shape[-1]
+    ws = torch.empty(hip.dist_workspace(B, nk, H, W), device=src.device, dtype=torch.uint8)
+    sd2 = torch.empty((B, nk, H, W), device=src.device, dtype=torch.int32)
+    flags = torch.empty((B, nk), device=src.device, dtype=torch.int32)
+    hip.dist_map(src, n_classes, class_mask, ws, sd2, flags, mode=mode, threshold=threshold)
+    return sd2, flags
+
+
+def distance_maps(labels_or_logits, n_classes, classes=None, mode="labels", threshold=0.5):
+    """The dense signed Euclidean distance transform of the class masks, exact, on the device: ``(sd2, flags)`` with ``sd2`` int32
+    ``[B, nk, H, W]`` the signed SQUARED distance between pixel centres (``+min |x - q|^2`` over the mask for a pixel outside it,
+    ``-min |x - q|^2`` over the complement for a pixel inside) and ``flags`` int32 ``[B, nk]``: 0, 1 for an empty mask, 2 for a mask
+    that is the whole image.  ``sd2.abs().float().sqrt()`` is ``edt(M) + edt(~M)`` of ``scipy.ndimage.distance_transform_edt``.
+    Deliberate difference from scipy: a flagged plane is all 0 (scipy returns arbitrary numbers for an input without a zero).
+
+    ``mode="labels"``: an int64 or uint8 label map ``[B, H, W]`` (``[B, 1, H, W]`` is accepted); the mask of class k is ``label == k``
+    and a label outside ``[0, n_classes)`` belongs to no class.  ``mode="softmax"``: fp32 logits ``[B, C, H, W]``, mask
+    ``softmax(z)_k > threshold``.  ``mode="sigmoid"``: mask ``sigmoid(z_k) > threshold`` (compared as ``z_k > logit(threshold)``).
+    ``classes=None`` means ``1 .. n_classes - 1`` (class 0 when there is only one); the planes come in ascending class order.
+    Limits: 1 .. 64 classes, 2 <= H, W <= 1024, B * nk * H * W < 2^31.  Device tensors only; nothing synchronises."""
+    what = "distance_maps"
+    if mode not in _DIST_MODES:
+        raise ValueError("%s: mode = %r, expected 'labels', 'softmax' or 'sigmoid'" % (what, mode))
+    ids, mask = _dist_classes(what, n_classes, classes)
+    x = labels_or_logits
+    if not 0.0 < float(threshold) < 1.0:
+        raise ValueError("%s: threshold = %g outside (0, 1)" % (what, threshold))
+    if mode == "labels":
+        if x.dim() == 4 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 3 or x.dtype not in (torch.int64, torch.uint8):
+            raise ValueError("%s: a uint8 or int64 label map [B, H, W] required, got %s %s" % (what, x.dtype, tuple(x.shape)))
+        thr = 0.0
+    else:
+        if x.dim() != 4 or x.shape[1] != n_classes or not x.is_floating_point():
+            raise ValueError("%s: logits [B, %d, H, W] required, got %s %s" % (what, n_classes, x.dtype, tuple(x.shape)))
+        if mode == "softmax" and n_classes < 2:
+            raise ValueError("%s: a softmax needs n_classes >= 2" % what)
+        thr = float(threshold) if mode == "softmax" else hip.sig_logit_threshold(threshold)
+        x = x.detach().float()
+    _dist_check_size(what, x.shape[0], len(ids), x.shape[-2], x.shape[-1])
+    if not x.is_cuda:
+        raise RuntimeError("lm_net_amd.distance_maps: device tensors required (the HIP path has no CPU fallback)")
+    return _dist_run(x.contiguous(), int(n_classes), mask, len(ids), _DIST_MODES[mode], thr)
+
+
+class _DistLossFn(torch.autograd.Function):
+    """The loss entries of include/distmap/lmnet_distmap.h.  cfg = (head, term, alpha, scale, class_mask)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, sd2_g, sd2_p, cfg):
+        head, term, alpha, scale, class_mask = cfg
+        sums = torch.empty(hip.DISTMAP_SUMS_WORDS, device=logits.device, dtype=torch.int32)
+        loss = torch.empty(1, device=logits.device)
+        hip.dist_loss_fwd(logits, target, head, term, alpha, scale, class_mask, sd2_g, sd2_p, sums, loss)
+        ctx.save_for_backward(logits, target, sd2_g, sums, *(() if sd2_p is None else (sd2_p,)))
+        ctx.cfg = cfg
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, sd2_g, sums = ctx.saved_tensors[:4]
+        sd2_p = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        head, term, alpha, scale, class_mask = ctx.cfg
+        d = torch.empty_like(logits)
+        hip.dist_loss_bwd(logits, target, head, term, alpha, class_mask, sd2_g, sd2_p, sums, g.reshape(1).contiguous().float(), d)
+        return d, None, None, None, None
+
+
+class _DistLoss(torch.nn.Module):
+    """What BoundaryLoss and HausdorffDTLoss share: the classes, the head, the checks and the target's distance map."""
+
+    MAX_CLASSES = _DIST_MAX_CLASSES
+    TERM = None
+
+    def __init__(self, n_classes, classes=None, head="softmax", scale=1.0):
+        super().__init__()
+        self.what = type(self).__name__
+        if head not in ("softmax", "sigmoid"):
+            raise ValueError("%s: head = %r, expected 'softmax' or 'sigmoid'" % (self.what, head))
+        self.classes, self.class_mask = _dist_classes(self.what, n_classes, classes)
+        if head == "softmax" and n_classes < 2:
+            raise ValueError("%s: a softmax head needs n_classes >= 2 (one logit: head='sigmoid')" % self.what)
+        self.n_classes, self.head = int(n_classes), head
+        self.scale = float(scale)
+        self.maps = None
+
+    def _check(self, logits, target):
+        """-> (fp32 contiguous logits, contiguous target of the head's shape)"""
+        w = self.what
+        if not (self.scale - self.scale == 0.0):
+            raise ValueError("%s: scale = %r is not finite" % (w, self.scale))
+        if logits.dim() != 4 or logits.shape[1] != self.n_classes:
+            raise ValueError("%s: logits must be [B, %d, H, W], got %s" % (w, self.n_classes, tuple(logits.shape)))
+        B, Cn, H, W = logits.shape
+        _dist_check_size(w, B, len(self.classes), H, W)
+        if B * Cn * H * W >= 1 << 31:
+            raise ValueError("%s: B * C * H * W = %d beyond the limit 2^31" % (w, B * Cn * H * W))
+        if target.dtype == torch.bool:
+            target = target.to(torch.uint8)
+        if target.dtype not in (torch.uint8, torch.int64):
+            raise ValueError("%s: target must be uint8, bool or int64, got %s" % (w, target.dtype))
+        if self.head == "softmax":
+            if target.dim() == 4 and target.shape[1] == 1:
+                target = target[:, 0]
+            ok = tuple(target.shape) == (B, H, W)
+        else:
+            if Cn == 1 and tuple(target.shape) == (B, H, W):
+                target = target[:, None]
+            ok = tuple(target.shape) == (B, Cn, H, W)
+        if not ok:
+            raise ValueError("%s: target %s does not match logits %s under a %s head" % (w, tuple(target.shape), tuple(logits.shape), self.head))
+        if not logits.is_cuda or not target.is_cuda:
+            raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % w)
+        return logits.float().contiguous(), target.contiguous()
+
+    def target_maps(self, target):
+        """(sd2, flags) of the target's masks for this loss's classes and head: what ``forward(..., maps=)`` takes, so that a caller who
+        trains both terms computes it once.  Softmax head: ``distance_maps(target, n_classes, classes)``.  Sigmoid head: plane k's mask
+        is ``target[:, k] == 1`` (a void element belongs to no mask)."""
+        if self.head == "softmax":
+            return distance_maps(target, self.n_classes, self.classes)
+        if target.dtype == torch.bool:
+            target = target.to(torch.uint8)
+        if target.dim() == 3:
+            target = target[:, None]
+        if target.dim() != 4 or target.shape[1] != self.n_classes or target.dtype not in (torch.uint8, torch.int64):
+            raise ValueError("%s: target planes [B, %d, H, W] of uint8, bool or int64 required, got %s %s"
+                             % (self.what, self.n_classes, target.dtype, tuple(target.shape)))
+        B, _, H, W = target.shape
+        nk = len(self.classes)
+        planes = target if nk == self.n_classes else torch.stack([target[:, k] for k in self.classes], 1)    # (no index tensor: no copy)
+        sd2, flags = distance_maps(planes.reshape(B * nk, H, W), 2, [1])             # every plane a two-class label map
+        return sd2.view(B, nk, H, W), flags.view(B, nk)
+
+    def _prediction_maps(self, logits):
+        return None
+
+    def _alpha(self):
+        return 2.0
+
+    def forward(self, logits, target, maps=None):
+        logits, target = self._check(logits, target)
+        if maps is None:
+            maps = self.target_maps(target)
+        sd2 = maps[0]
+        want = (logits.shape[0], len(self.classes)) + tuple(logits.shape[2:])
+        if tuple(sd2.shape) != want or sd2.dtype != torch.int32 or not sd2.is_cuda:
+            raise ValueError("%s: maps[0] must be an int32 device tensor %s, got %s %s" % (self.what, want, sd2.dtype, tuple(sd2.shape)))
+        self.maps = sd2
+        head = hip.DISTMAP_SOFTMAX if self.head == "softmax" else hip.DISTMAP_SIGMOID
+        cfg = (head, self.TERM, self._alpha(), self.scale, self.class_mask)
+        return _DistLossFn.apply(logits, target, sd2.contiguous(), self._prediction_maps(logits), cfg)
+
+
+class BoundaryLoss(_DistLoss):
+    """The boundary loss of Kervadec et al. (MIDL 2019): ``scale * mean(p * phi)`` over the valid pixels and the scored classes, with
+    ``phi`` the signed distance map of the target (``one_hot2dist``: ``edt(neg) * neg - (edt(pos) - 1) * pos``; 0 on a plane whose
+    mask is empty or the whole image: Kervadec's ``if posmask.any()``) computed on the device at every step by ``distance_maps``.
+
+    ``classes=None`` means ``1 .. n_classes - 1`` (Kervadec's ``idc=[1]`` at two classes); for a one-logit sigmoid head it is class 0,
+    the only plane.  ``scale`` is a plain attribute read at every call, so ``seg(l, y) + bl(l, y)`` with a rising ``bl.scale`` is the
+    paper's schedule.  ``head="softmax"``: fp32 logits ``[B, C, H, W]`` and an int64 / uint8 label map ``[B, H, W]`` (``[B, 1, H, W]``
+    accepted), valid pixels are those with a label in ``[0, C)``.  ``head="sigmoid"``: target planes ``[B, C, H, W]`` (or
+    ``[B, H, W]`` at C = 1), a valid element is one whose target is 0 or 1.  ``maps`` holds the last target ``sd2``;
+    ``forward(logits, target, maps=crit.target_maps(target))`` takes a precomputed ``(sd2, flags)``.  Nothing synchronises.
+    Deliberate difference from torch: without a valid pixel the loss is 0 and the gradient all zero, never NaN.  Parity with
+    Kervadec's or MONAI's code is not pinned by the tests (neither is a dependency); the formulas of
+    ``include/distmap/lmnet_distmap.h`` are.  Limits: 1 .. 64 classes, 2 <= H, W <= 1024, B * nk * H * W < 2^31."""
+
+    TERM = hip.DISTMAP_BOUNDARY
+
+
+class HausdorffDTLoss(_DistLoss):
+    """The distance-transform Hausdorff loss of Karimi and Salcudean (TMI 2019): ``scale * mean((p - g)^2 (d_p^alpha + d_g^alpha))``
+    over the valid pixels and the scored classes, with ``d_g = sqrt(|sd2|)`` of the target's mask and ``d_p`` the same of the
+    prediction thresholded at 0.5 (``softmax(z)_k > 0.5`` or ``z_k > 0``), both computed on the device at every step; ``d_p`` is a
+    constant of the step (no gradient flows through it).  ``alpha`` in (0, 8]; ``alpha == 2`` uses the integer squares as they are.
+    Classes, heads, targets, ``scale``, ``maps`` and the limits are those of ``BoundaryLoss``; ``pred_maps`` holds the last ``d_p^2``."""
+
+    TERM = hip.DISTMAP_HAUSDORFF
+
+    def __init__(self, n_classes, classes=None, head="softmax", alpha=2.0, scale=1.0):
+        super().__init__(n_classes, classes, head, scale)
+        if not 0.0 < float(alpha) <= 8.0:
+            raise ValueError("HausdorffDTLoss: alpha = %r outside the limit (0, 8]" % (alpha,))
+        self.alpha = float(alpha)
+        self.pred_maps = None
+
+    def _alpha(self):
+        return self.alpha
+
+    def _prediction_maps(self, logits):
+        self.pred_maps = distance_maps(logits, self.n_classes, self.classes, mode=self.head)[0]
+        return self.pred_maps
