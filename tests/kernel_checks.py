@@ -620,13 +620,18 @@ def check_conv_rp():
     for (B, H, W, Cin, E, Cout, dt) in [(2, 20, 52, 12, 24, 12, f32), (2, 4, 4, 96, 192, 96, f32), (3, 9, 13, 24, 48, 24, f32), (1, 12, 16, 48, 96, 48, f32),
                                         (1, 64, 80, 48, 96, 48, f32), (1, 64, 80, 96, 192, 96, f32),
                                         (2, 8, 12, 12, 24, 12, b16), (3, 9, 13, 24, 48, 24, b16), (2, 4, 4, 96, 192, 96, b16), (1, 64, 80, 48, 96, 48, b16),
-                                        (1, 64, 80, 96, 192, 96, b16)]:
-        tag = " Cin=%d E=%d %dx%d %s" % (Cin, E, H, W, "bf16" if dt == b16 else "fp32")
-        tol = 1e-6 if dt == f32 else 2e-2
-        t64, s64 = (TOL, 2e-4) if dt == f32 else (1e-2, 1e-2)
-        q = (lambda t: t) if dt == f32 else (lambda t: t.to(b16).double())
+                                        (1, 64, 80, 96, 192, 96, b16),
+                                        # "mma": fp32 storage, bf16 matrix-core operands (compute_dtype "bf16-mma": the `| 1` instances beside `| 4`)
+                                        (2, 20, 52, 12, 24, 12, "mma"), (2, 4, 4, 96, 192, 96, "mma"), (3, 9, 13, 24, 48, 24, "mma"), (1, 12, 16, 48, 96, 48, "mma"),
+                                        (1, 64, 80, 48, 96, 48, "mma"), (1, 64, 80, 96, 192, 96, "mma")]:
+        mma = dt == "mma"
+        dt = f32 if mma else dt
+        tag = " Cin=%d E=%d %dx%d %s" % (Cin, E, H, W, "bf16-mma" if mma else "bf16" if dt == b16 else "fp32")
+        tol = (1e-6 if dt == f32 else 2e-2)        # (the same call on two layouts: bf16 operands round the same values the same way)
+        t64, s64 = (TOL, 2e-4) if dt == f32 and not mma else (1e-2, 1e-2)
+        q = (lambda t: t) if dt == f32 and not mma else (lambda t: t.to(b16).double())
         prev = hip._MMA[0]
-        hip._MMA[0] = hip.BF16 if dt == b16 else hip.F32
+        hip._MMA[0] = hip.BF16 if dt == b16 or mma else hip.F32
         try:
             cast = lambda t: t.to(dt).contiguous()
             xr, prer, dyr, dhr = q(R(B, Cin, H, W, seed=301)), q(R(B, E, H, W, seed=302)), q(R(B, Cout, H, W, seed=303)), q(R(B, E, H, W, seed=304))
@@ -657,7 +662,7 @@ def check_conv_rp():
             rows.append(("conv out NHWC / row-planar: batch sums vs fp64" + tag, max(rel(sa, s_ref), rel(sb, s_ref)), s64))
             # pointwise + shortcut: first source row-planar with GELU x gate
             n0, n1 = hip.conv_pack_size(1, Cout, [E]), hip.conv_pack_size(1, Cout, [Cin])
-            h2 = 2 if dt == b16 else 1
+            h2 = 2 if dt == b16 or mma else 1          # (bf16 operands pack into half the floats)
             wp2 = torch.empty(n0 + n1, device=DEV)
             hip.conv_pack(wpw, 1, [E], out=wp2[:n0 // h2])
             hip.conv_pack(wsc, 1, [Cin], out=wp2[n0 // h2:(n0 + n1) // h2])
@@ -1692,9 +1697,9 @@ def _dgelu_widths():
     wave: the smallest map where the tile cost model of conv_fwd.hip picks two), 192.  bf16 storage: bf16-representable operands, so
     only the stored output is rounded (8e-3, as in check_bf16_storage_rows)."""
     rows = []
-    for dt in (torch.float32, torch.bfloat16):
-        q = (lambda t: t) if dt == torch.float32 else (lambda t: t.to(torch.bfloat16).double())
-        hip._MMA[0] = hip.F32 if dt == torch.float32 else hip.BF16
+    for dt, mma in ((torch.float32, False), (torch.bfloat16, True), (torch.float32, True)):     # (the last: fp32 storage, bf16 operands -- "bf16-mma")
+        q = (lambda t: t) if not mma else (lambda t: t.to(torch.bfloat16).double())
+        hip._MMA[0] = hip.BF16 if mma else hip.F32
         try:
             for (B, H, W, Cin, E, kern) in [(1, 6, 8, 12, 24, "conv_tile_kernel<1, 2, 1,"), (1, 6, 8, 24, 48, "conv_tile_kernel<1, 3, 1,"),
                                             (1, 16, 48, 48, 96, "conv_tileM_kernel<1, 1, 1,"), (1, 64, 80, 48, 96, "conv_tileM_kernel<1, 2, 1,"),
@@ -1706,7 +1711,7 @@ def _dgelu_widths():
                 o = torch.full((B, H, W, E), float("nan"), device=DEV, dtype=dt)
                 _, names = launched(lambda: hip.conv_fwd([dict(view=nhwc(dy).to(dt), flags=0)], hip.conv_pack_t(dev(wpw), 1), o, B=B, Hin=H, Win=W, Hout=H, Wout=W, Cout=E,
                                                          transposed=1, epilogue=hip.EP_DGELU, aux=nhwc(pre).to(dt)))
-                tg = " %d->%d %dx%d %s" % (Cin, E, H, W, "bf16" if dt == torch.bfloat16 else "fp32")
+                tg = " %d->%d %dx%d %s" % (Cin, E, H, W, "bf16" if dt == torch.bfloat16 else "bf16-mma" if mma else "fp32")
                 rows.append(("conv DGELU" + tg, rel(nchw(o), pl.grad), TOL if dt == torch.float32 else 8e-3))
                 rows.append(form_row("conv DGELU" + tg, names, [kern]))
         finally:
@@ -2155,17 +2160,19 @@ def check_conv3_storage():
     prev = hip.conv_dma_config(0, 1)
     mma0 = hip._MMA[0]
     try:
-        for dt in (f32, b16):
-            hip._MMA[0] = hip.F32 if dt == f32 else hip.BF16
-            q = (lambda t: t) if dt == f32 else (lambda t: t.to(b16).double())
-            to, tsum = (TOL, 2e-4) if dt == f32 else (8e-3, 2e-4)
+        for dt, mma in ((f32, False), (b16, True), (f32, True)):     # (fp32 storage with bf16 operands: compute_dtype "bf16-mma", the `PM = 1` instances)
+            hip._MMA[0] = hip.BF16 if mma else hip.F32
+            q = (lambda t: t) if not mma else (lambda t: t.to(b16).double())
+            to, tsum = (TOL, 2e-4) if dt == f32 else (8e-3, 2e-4)     # (bf16-representable operands: exact products, so fp32 storage keeps TOL)
             for (B, H, W, Cin, Cout, st, up, stats) in [
                     (1, 9, 40, 12, 12, 1, 0, 0), (1, 9, 40, 24, 12, 1, 0, 1), (1, 18, 40, 12, 24, 2, 0, 0), (1, 9, 20, 48, 24, 1, 0, 0), (1, 9, 20, 72, 24, 1, 0, 1),
                     (1, 18, 40, 24, 48, 2, 0, 0), (1, 9, 20, 48, 48, 1, 0, 0), (2, 16, 24, 144, 48, 1, 0, 1), (1, 18, 36, 48, 96, 2, 0, 0), (1, 44, 44, 96, 96, 1, 0, 0),
                     (1, 44, 44, 192, 96, 1, 0, 1), (1, 8, 8, 96, 192, 1, 0, 0),
+                    (1, 8, 8, 96, 192, 1, 0, 1),     # statistics on a small wide map: one cout tile a wave (64 x 64 inputs)
+                    (1, 9, 40, 12, 36, 1, 0, 0),     # three cout tiles with LDS-staged weights (Wodd: 12 -> 36)
                     (1, 9, 20, 24, 12, 1, 1, 0), (1, 9, 20, 48, 24, 1, 1, 0), (1, 10, 12, 96, 48, 1, 1, 0), (1, 22, 22, 192, 96, 1, 1, 0)]:   # (up: H x W is the source map)
                 Hi, Wi = (2 * H, 2 * W) if up else (H, W)
-                tag = " %dx%dx%d %d->%d s%d%s %s" % (B, Hi, Wi, Cin, Cout, st, " up2" if up else "", "bf16" if dt == b16 else "fp32")
+                tag = " %dx%dx%d %d->%d s%d%s %s" % (B, Hi, Wi, Cin, Cout, st, " up2" if up else "", "bf16" if dt == b16 else "bf16-mma" if mma else "fp32")
                 xr = q(R(B, Cin, H, W, seed=601)).requires_grad_(True)
                 wr = q(R(Cout, Cin, 3, 3, seed=602, scale=1.0 / math.sqrt(9 * Cin))).requires_grad_(True)
                 br = R(Cout, seed=603).requires_grad_(True)
@@ -2174,7 +2181,7 @@ def check_conv3_storage():
                 Ho, Wo = z.shape[2:]
                 resr, dyr = q(R(B, Cout, Ho, Wo, seed=604)), q(R(B, Cout, Ho, Wo, seed=605))
                 z.backward(dyr)
-                t_out = max(to, 1e-2) if up and dt == b16 else to
+                t_out = max(to, 1e-2) if up and mma else to
                 xd = nhwc(xr.detach()).to(dt)
                 src = dict(view=xd, flags=hip.SRC_UP2) if up else xd
                 wp = hip.conv_pack(dev(wr.detach()), 3, [Cin])
@@ -2202,7 +2209,7 @@ def check_conv3_storage():
                 dyd = nhwc(dyr).to(dt)
                 if up and hip.conv_wgrad_up2_ok(xd, dyd, B=B, Hin=Hi, Win=Wi, Cout=Cout):
                     hip.conv_wgrad([src], dyd, dW, db, **kw)
-                    rows.append(("conv3 weight gradient (up2 on load)" + tag, max(rel(dW, wr.grad), rel(db, br.grad)), tsum if dt == f32 else 1e-2))
+                    rows.append(("conv3 weight gradient (up2 on load)" + tag, max(rel(dW, wr.grad), rel(db, br.grad)), tsum if not mma else 1e-2))
                 elif not up:
                     hip.conv_wgrad([xd], dyd, dW, db, **kw)
                     rows.append(("conv3 weight gradient" + tag, max(rel(dW, wr.grad), rel(db, br.grad)), tsum))

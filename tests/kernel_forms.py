@@ -10,7 +10,8 @@ can run another instance than the one its comment names, and pass.  Three uses:
   * ``OWNED`` maps the exact name of an instance to its owner: a ``kernel_checks.check_*`` function or a pytest node id
     (``tests/<file>.py::<test>``) that compares THAT instance with a high-precision reference of the operation -- not with another
     kernel.  ``owner_check`` (the decorator of every check_*) and the named tests assert that the owner really launches what it owns;
-    tests/test_kernel_census_gpu.py asserts that every instance a training step launches has an owner;
+    tests/test_kernel_census_gpu.py asserts that every instance a training step launches has an owner, and
+    tests/test_kernel_census_envelope_gpu.py the same for the wide variants, other windows, class counts and precisions;
   * ``form_row`` turns a claim about dispatch ("the M-split kernel", "two-stage reduction") into a (name, err, tol) row.
 
 A new kernel instance that reaches the step needs an entry here and a case in its owner that selects it (README, tests section).
@@ -295,3 +296,144 @@ OWNED = {
     "segloss_sums_kernel<2>": "tests/test_multiclass_kernels_gpu.py::test_two_class_loss_vs_f64_owns_the_step_kernels",
     "adamw_kernel": "tests/test_optim_kernels_gpu.py::test_plain_adamw_step_vs_f64_owns_the_step_kernel",
 }
+
+# ---- the wider envelope (tests/test_kernel_census_envelope_gpu.py): wide variants, na_kernel_size 5 / 7, "bf16-mma", other class counts
+_WIDE = "tests/test_wide_kernels_gpu.py::"
+OWNED.update({
+    # general neighbourhood attention, any head dim: <lanes per head, vector width, register array> (csrc/na_gen.hip LMN_NG_SELECT);
+    # both storages against oracle/natten_ref.py in float64
+    "na_any_%s_kernel<%s, %s>" % (k, a, t): _WIDE + "test_na_general_head_dims_vs_oracle_f64"
+    for k in ("fwd", "bwd_q", "bwd_kv")
+    for a in ("1, 1, 8", "1, 2, 8", "1, 4, 16", "1, 1, 32", "2, 1, 16", "2, 2, 16", "2, 4, 16")
+    for t in ("float", "__bf16")
+})
+OWNED.update({
+    "gattn_bwd_kv_kernel<128, float>": _WIDE + "test_gattn_wide_head_dim_vs_f64",
+    "gattn_bwd_kv_kernel<64, float>": _WIDE + "test_gattn_wide_head_dim_vs_f64",
+    "gattn_bwd_q_kernel<128, float>": _WIDE + "test_gattn_wide_head_dim_vs_f64",
+    "gattn_bwd_q_kernel<64, float>": _WIDE + "test_gattn_wide_head_dim_vs_f64",
+    "gattn_fwd_kernel<128, float>": _WIDE + "test_gattn_wide_head_dim_vs_f64",
+    "gattn_fwd_kernel<64, float>": _WIDE + "test_gattn_wide_head_dim_vs_f64",
+    "ln_bwd_wide_kernel<float>": _WIDE + "test_layernorm_wide_rows_vs_f64",
+    "ln_fwd_wide_kernel<float>": _WIDE + "test_layernorm_wide_rows_vs_f64",
+    "gattn_bwd_kv_kernel<128, __bf16>": "check_wide_bf16_rows",
+    "gattn_bwd_kv_kernel<64, __bf16>": "check_wide_bf16_rows",
+    "gattn_bwd_q_kernel<128, __bf16>": "check_wide_bf16_rows",
+    "gattn_bwd_q_kernel<64, __bf16>": "check_wide_bf16_rows",
+    "gattn_fwd_kernel<128, __bf16>": "check_wide_bf16_rows",
+    "gattn_fwd_kernel<64, __bf16>": "check_wide_bf16_rows",
+    "ln_bwd_wide_kernel<__bf16>": "check_wide_bf16_rows",
+    "ln_fwd_wide_kernel<__bf16>": "check_wide_bf16_rows",
+    "na_bwd_kv_kernel<16, float>": "check_na_hd16",
+    "na_bwd_q_kernel<16, float>": "check_na_hd16",
+    "na_fwd_kernel<16, float>": "check_na_hd16",
+})
+OWNED.update({"na_%s_gen_kernel<%d, float>" % (k, hd): "check_na" for k in ("fwd", "bwd_q", "bwd_kv") for hd in (1, 2, 4, 8, 16)})
+OWNED.update({"na_%s_gen_kernel<%d, __bf16>" % (k, hd): "check_wide_bf16_rows" for k in ("fwd", "bwd_q", "bwd_kv") for hd in (1, 2, 4, 8, 16)})
+# the rest of the envelope's list: other template arguments of the conv, weight-gradient, depthwise and row kernels ("bf16-mma": operand
+# type 1 / 5; wide variants: other tile shapes; deploy-mode bf16).  Each owner holds a case at the channel counts that select the instance
+OWNED.update({
+    "dw_bwd_kernel<__bf16, 0, false, false, 2>": "check_bf16_storage_rows",
+    "dw_fwd_kernel<__bf16, false>": "check_bf16_storage_rows",
+    "dw_stats0_kernel<__bf16, false>": "check_bf16_storage_rows",
+    "dw_stats1_kernel<__bf16, false>": "check_bf16_storage_rows",
+    "conv_tileM_kernel<1, 1, 3, 4, false, false>": "check_bn_bwd_rp_wide",
+    "conv_tileM_kernel<1, 1, 3, 6, false, false>": "check_bn_bwd_rp_wide",
+    "conv_tileM_kernel<1, 1, 4, 4, false, false>": "check_bn_bwd_rp_wide",
+    "conv_tileM_kernel<1, 1, 4, 6, false, false>": "check_bn_bwd_rp_wide",
+    "conv_tileM_kernel<9, 1, 0, 1, false, false>": "check_conv3_storage",
+    "conv_tileM_kernel<9, 1, 2, 2, false, false>": "check_conv3_storage",
+    "conv_tileM_kernel<9, 2, 0, 1, false, false>": "check_conv3_storage",
+    "conv_tileM_kernel<9, 2, 0, 1, false, true>": "check_conv3_storage",
+    "conv_tileM_kernel<9, 2, 2, 1, false, false>": "check_conv3_storage",
+    "conv_tile_kernel<9, 1, 0, false, 0, false, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 1, 0, false, 1, true, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 1, 0, false, 1, true, false, true, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 1, 0, true, 1, false, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 1, 2, false, 1, true, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 2, 0, false, 1, false, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 2, 0, false, 1, false, false, true, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 2, 0, false, 1, true, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 2, 0, true, 1, false, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 2, 2, false, 1, false, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 3, 0, false, 1, false, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 3, 0, false, 1, false, false, true, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 3, 0, false, 2, true, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 3, 0, true, 1, false, false, false, 2>": "check_conv3_storage",
+    "conv_tile_kernel<9, 3, 2, false, 1, false, false, false, 2>": "check_conv3_storage",
+    "wgrad3_kernel<1, 1, 1, false>": "check_conv3_storage",
+    "wgrad3_kernel<1, 1, 1, true>": "check_conv3_storage",
+    "wgrad3_kernel<2, 2, 1, false>": "check_conv3_storage",
+    "wgrad3_kernel<2, 2, 1, true>": "check_conv3_storage",
+    "wgrad_lds_kernel<9, 1, 1, 1>": "check_conv3_storage",
+    "wgrad_lds_kernel<9, 2, 2, 1>": "check_conv3_storage",
+    "wgrad_1x1w_kernel<1, 1, 1>": "check_conv_bf16",
+    "wgrad_1x1w_kernel<2, 2, 1>": "check_conv_bf16",
+    "conv_tileM_kernel<1, 1, 1, 1, false, false>": "check_conv_bn_epilogues",
+    "conv_tileM_kernel<1, 2, 1, 1, false, false>": "check_conv_bn_epilogues",
+    "conv_tile_kernel<1, 2, 1, false, 1, false, false, false, 2>": "check_conv_bn_epilogues",
+    "conv_tile_kernel<1, 3, 1, false, 1, false, false, false, 2>": "check_conv_bn_epilogues",
+    "conv_tileM_kernel<1, 1, 0, 1, true, false>": "check_conv_mma_forms",
+    "conv_tileM_kernel<1, 2, 0, 1, true, false>": "check_conv_mma_forms",
+    "conv_tile_kernel<1, 1, 6, false, 1, false, false, false, 2>": "check_conv_mma_forms",
+    "conv_tile_kernel<1, 2, 0, false, 1, false, true, false, 2>": "check_conv_mma_forms",
+    "conv_tile_kernel<1, 2, 6, false, 1, false, false, false, 2>": "check_conv_mma_forms",
+    "conv_tile_kernel<1, 3, 0, false, 1, false, true, false, 2>": "check_conv_mma_forms",
+    "conv_tile_kernel<1, 3, 6, false, 1, false, false, false, 2>": "check_conv_mma_forms",
+    "wgrad_1x1w_kernel<3, 1, 1>": "check_conv_mma_forms",
+    "conv_tileM_kernel<1, 1, 0, 2, false, false>": "check_conv_rp",
+    "conv_tileM_kernel<1, 1, 0, 6, false, false>": "check_conv_rp",
+    "conv_tileM_kernel<1, 1, 2, 0, false, false>": "check_conv_rp",
+    "conv_tileM_kernel<1, 1, 2, 2, false, false>": "check_conv_rp",
+    "conv_tileM_kernel<1, 1, 2, 5, false, false>": "check_conv_rp",
+    "conv_tileM_kernel<1, 1, 5, 5, false, false>": "check_conv_rp",
+    "conv_tileM_kernel<1, 2, 0, 1, false, false>": "check_conv_rp",
+    "conv_tileM_kernel<1, 2, 0, 5, false, false>": "check_conv_rp",
+    "conv_tileM_kernel<1, 2, 2, 5, false, false>": "check_conv_rp",
+    "conv_tileM_kernel<1, 2, 5, 5, false, false>": "check_conv_rp",
+    "conv_tile_kernel<1, 1, 0, false, 1, false, false, false, 2>": "check_conv_rp",
+    "conv_tile_kernel<1, 1, 0, false, 5, false, false, false, 2>": "check_conv_rp",
+    "conv_tile_kernel<1, 2, 0, false, 1, false, false, false, 2>": "check_conv_rp",
+    "conv_tile_kernel<1, 2, 0, false, 5, false, false, false, 2>": "check_conv_rp",
+    "conv_tile_kernel<1, 2, 2, false, 5, false, false, false, 2>": "check_conv_rp",
+    "conv_tile_kernel<1, 2, 5, false, 5, false, false, false, 2>": "check_conv_rp",
+    "conv_tile_kernel<1, 3, 0, false, 1, false, false, false, 2>": "check_conv_rp",
+    "conv_tile_kernel<1, 3, 0, false, 5, false, false, false, 2>": "check_conv_rp",
+    "conv_tile_kernel<1, 3, 2, false, 5, false, false, false, 2>": "check_conv_rp",
+    "conv_tile_kernel<1, 3, 5, false, 5, false, false, false, 2>": "check_conv_rp",
+    "wgrad_1x1w_kernel<1, 2, 1>": "check_conv_rp",
+    "wgrad_1x1w_kernel<1, 2, 5>": "check_conv_rp",
+    "wgrad_1x1w_kernel<1, 3, 5>": "check_conv_rp",
+    "wgrad_1x1w_kernel<2, 1, 1>": "check_conv_rp",
+    "wgrad_1x1w_kernel<2, 1, 5>": "check_conv_rp",
+    "wgrad_1x1w_kernel<2, 3, 1>": "check_conv_rp",
+    "wgrad_1x1w_kernel<2, 3, 5>": "check_conv_rp",
+    "wgrad_1x1w_kernel<2, 4, 1>": "check_conv_rp",
+    "wgrad_1x1w_kernel<2, 4, 5>": "check_conv_rp",
+    "wgrad_1x1w_kernel<3, 2, 1>": "check_conv_rp",
+    "wgrad_1x1w_kernel<3, 2, 5>": "check_conv_rp",
+    "wgrad_1x1w_kernel<4, 2, 1>": "check_conv_rp",
+    "wgrad_1x1w_kernel<4, 2, 5>": "check_conv_rp",
+    "dw_bwd_kernel<float, 0, false, false, 2>": "check_dw",
+    "dw_merge_kernel": "check_dw",
+    "dw_stats0_kernel<float, false>": "check_dw",
+    "dw_stats1_kernel<float, false>": "check_dw",
+    "conv_tileM_kernel<9, 1, 0, 2, false, true>": "check_fused_sources_modes",
+    "up2_fwd_kernel<__bf16>": "check_fused_sources_modes",
+    "wgrad_1x1_kernel<3, 1, 2>": "check_fused_sources_modes",
+    "ln_bwd_kernel<16, float>": "check_ln",
+    "avgpool_fwd_kernel<__bf16>": "check_rows_envelope",
+    "avgpool_fwd_kernel<float>": "check_rows_envelope",
+    "bnact_fwd_kernel<__bf16>": "check_rows_envelope",
+    "ln_bwd_kernel<16, __bf16>": "check_rows_envelope",
+    "se_bwd_params_kernel": "check_se",
+    "wgrad_1x1_kernel<1, 3, 2>": "check_wgrad_1x1_envelope",
+    "wgrad_1x1_kernel<3, 1, 6>": "check_wgrad_1x1_envelope",
+    "wgrad_1x1w_kernel<1, 3, 0>": "check_wgrad_1x1_envelope",
+    "wgrad_1x1w_kernel<1, 4, 4>": "check_wgrad_1x1_envelope",
+    "wgrad_1x1w_kernel<1, 4, 6>": "check_wgrad_1x1_envelope",
+    "wgrad_1x1w_kernel<3, 1, 4>": "check_wgrad_1x1_envelope",
+    "wgrad_1x1w_kernel<4, 1, 0>": "check_wgrad_1x1_envelope",
+    "segloss_bwd_gen_kernel": "tests/test_multiclass_kernels_gpu.py::test_general_c_loss_vs_f64",
+    "segloss_sums_gen_kernel": "tests/test_multiclass_kernels_gpu.py::test_general_c_loss_vs_f64",
+})

@@ -44,8 +44,9 @@ def test_owned_kernels_are_launched_somewhere():
 
 def test_owners_exist():
     import kernel_forms
-    checks = _functions(os.path.join(ROOT, "tests", "kernel_checks.py"))
-    listed = open(os.path.join(ROOT, "tests", "test_kernels_gpu.py")).read()
+    # (kernel_checks.py with its driver test_kernels_gpu.py; kernel_checks_envelope.py with test_kernels_envelope_gpu.py)
+    homes = [(_functions(os.path.join(ROOT, "tests", c)), open(os.path.join(ROOT, "tests", t)).read())
+             for c, t in (("kernel_checks.py", "test_kernels_gpu.py"), ("kernel_checks_envelope.py", "test_kernels_envelope_gpu.py"))]
     bad = []
     for owner in sorted(set(kernel_forms.OWNED.values())):
         if "::" in owner:
@@ -53,9 +54,9 @@ def test_owners_exist():
             full = os.path.join(ROOT, path)
             if not (path.startswith("tests/") and os.path.isfile(full) and test.split("[")[0] in _functions(full)):
                 bad.append(owner)
-        elif not (owner.startswith("check_") and owner in checks and '"%s"' % owner in listed):
+        elif not (owner.startswith("check_") and any(owner in checks and '"%s"' % owner in listed for checks, listed in homes)):
             bad.append(owner)
-    assert not bad, "owners that are neither a check_* run by test_kernels_gpu.py nor an existing test: %s" % bad
+    assert not bad, "owners that are neither a check_* run by its driver test nor an existing test: %s" % bad
 
 
 def test_owned_by_partitions_the_table():

@@ -54,6 +54,7 @@ def _run_loss(lg, y, wce, wdice, eps, gscale=None):
 
 @pytest.mark.parametrize("C", [5, 6, 7, 9, 14, 33, 64])
 def test_general_c_loss_vs_f64(C):
+    from kernel_forms import launched, owned_by
     B, H, W = 2, 37, 45                              # 1665 pixels per image: not a multiple of 64 or 256
     for eps in (0.0, 1e-3):
         key = "mc_k/%d/%g" % (C, eps)
@@ -67,7 +68,9 @@ def test_general_c_loss_vs_f64(C):
         g_ref = l64.grad
         for gs in (None, 0.37):                      # (the second call gets sums / coef workspaces that held other values)
             gst = None if gs is None else torch.tensor([gs], device="cuda")
-            loss, d = _run_loss(lg, y, wce, wdice, eps, gst)
+            (loss, d), names = launched(lambda: _run_loss(lg, y, wce, wdice, eps, gst))
+            # (the general-C kernels of a step with other class counts than 2: this test owns them, tests/kernel_forms.py)
+            assert {"segloss_sums_gen_kernel", "segloss_bwd_gen_kernel"} <= owned_by("tests/test_multiclass_kernels_gpu.py::test_general_c_loss_vs_f64") <= names, names
             assert abs(float(loss) - float(ref)) < 1e-5 * abs(float(ref)), (C, eps, float(loss), float(ref))
             expect = g_ref * (1.0 if gs is None else gs)
             err = float((d.double() - expect).abs().max())

@@ -15,6 +15,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kernel_forms import launched, owned_by
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,6 +64,22 @@ def _na_run(qkv, rpb, dout, dt):
     return out, dqkv, drpb
 
 
+NA_OWNER = "tests/test_wide_kernels_gpu.py::test_na_general_head_dims_vs_oracle_f64"
+GATTN_OWNER = "tests/test_wide_kernels_gpu.py::test_gattn_wide_head_dim_vs_f64"
+LN_OWNER = "tests/test_wide_kernels_gpu.py::test_layernorm_wide_rows_vs_f64"
+
+
+def _na_any_instances(hd, dt):
+    """The three na_any_* instances csrc/na_gen.hip (LMN_NG_SELECT) picks for a head dim: lanes per head, vector width of a lane's
+    loads, size of its register array."""
+    lanes = 2 if hd > 16 and hd % 2 == 0 else 1
+    hl = hd // lanes
+    vw = 4 if hl % 4 == 0 else 2 if hl % 2 == 0 else 1
+    hm = 16 if lanes == 2 else 8 if hl <= 8 else 16 if hl <= 16 else 32
+    t = "float" if dt == torch.float32 else "__bf16"
+    return {"na_any_%s_kernel<%d, %d, %d, %s>" % (k, lanes, vw, hm, t) for k in ("fwd", "bwd_q", "bwd_kv")}
+
+
 # maps with partial tiles / blocks and maps no larger than K + 1
 NA_MAPS = {3: [(2, 13, 11), (1, 4, 4)], 5: [(1, 13, 10), (1, 6, 6)], 7: [(1, 15, 9), (1, 8, 8)]}
 
@@ -79,8 +97,10 @@ def test_na_general_head_dims_vs_oracle_f64(hd, K):
             else:
                 o_ref_b, dq_ref_b, drpb_ref_b = o_ref, dq_ref, drpb_ref
                 tol_o, tol_g = 1e-5, 2e-4
-            out, dqkv, drpb = _na_run(qkv, rpb, dout, dt)
+            (out, dqkv, drpb), names = launched(lambda: _na_run(qkv, rpb, dout, dt))
             tag = "hd=%d K=%d %dx%dx%d %s" % (hd, K, B, H, W, dt)
+            want = _na_any_instances(hd, dt)          # this test owns them (tests/kernel_forms.py): it must launch them, and only them
+            assert want <= owned_by(NA_OWNER) and want == {n for n in names if n.startswith("na_")}, (tag, sorted(names), sorted(want))
             assert _rel(out, o_ref_b) < tol_o, (tag, "out", _rel(out, o_ref_b))
             assert _rel(dqkv, dq_ref_b) < tol_g, (tag, "dqkv", _rel(dqkv, dq_ref_b))
             assert _rel(drpb, drpb_ref_b) < tol_g, (tag, "drpb", _rel(drpb, drpb_ref_b))
@@ -182,11 +202,12 @@ def test_gattn_wide_head_dim_vs_f64(hd, N):
     qd = qkv.detach().float().to(DEV)
     out = torch.full((B, N, C), float("nan"), device=DEV)
     lse = torch.empty(B, HEADS, N, device=DEV)
-    hip.gattn_fwd(qd, out, lse, HEADS)
     dqkv = torch.full((B, N, 3 * C), float("nan"), device=DEV)
     delta = torch.empty(B, HEADS, N, device=DEV)
-    hip.gattn_bwd(qd, out, do.float().to(DEV), lse, dqkv, delta, HEADS)
-    torch.cuda.synchronize()
+    dod = do.float().to(DEV)
+    _, names = launched(lambda: (hip.gattn_fwd(qd, out, lse, HEADS), hip.gattn_bwd(qd, out, dod, lse, dqkv, delta, HEADS)))
+    want = {"gattn_%s_kernel<%d, float>" % (k, 64 if hd <= 64 else 128) for k in ("fwd", "bwd_q", "bwd_kv")}
+    assert want <= owned_by(GATTN_OWNER) and names == want, (sorted(names), sorted(want))     # (this test owns them: tests/kernel_forms.py)
     assert _rel(out, o_ref) < 1e-5, _rel(out, o_ref)
     assert _rel(dqkv, qkv.grad) < 2e-4, _rel(dqkv, qkv.grad)
 
@@ -202,11 +223,11 @@ def test_layernorm_wide_rows_vs_f64(C):
     y_ref.backward(dy)
     f = lambda t: t.detach().float().to(DEV)
     y = torch.full((n, C), float("nan"), device=DEV)
-    hip.ln_fwd(f(x), f(g), f(b), y)
     dx = torch.full((n, C), float("nan"), device=DEV)
     dg, db = torch.zeros(C, device=DEV), torch.zeros(C, device=DEV)
-    hip.ln_bwd(f(x), f(g), f(dy), f(dres), dx, dg, db)
-    torch.cuda.synchronize()
+    _, names = launched(lambda: (hip.ln_fwd(f(x), f(g), f(b), y), hip.ln_bwd(f(x), f(g), f(dy), f(dres), dx, dg, db)))
+    want = {"ln_fwd_wide_kernel<float>", "ln_bwd_wide_kernel<float>"}
+    assert want == owned_by(LN_OWNER) and want <= names, (sorted(names), sorted(want))        # (this test owns them: tests/kernel_forms.py)
     assert _rel(y, y_ref) < 1e-5
     assert _rel(dx, x.grad + dres) < 1e-5
     assert _rel(dg, g.grad) < 2e-4

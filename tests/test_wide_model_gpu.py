@@ -194,6 +194,41 @@ def test_wide_plan_replay_equals_host_launch_deterministic_and_graph_step():
     assert torch.isfinite(yg).all()
 
 
+@pytest.mark.parametrize("name", ["W3", "Wodd"])
+def test_wide_bf16_step_deterministic_twice_bit_identical(name):
+    """bf16 storage on the wide instances (general neighbourhood attention, VALU global attention at head dim 93 / 26, wide
+    LayerNorm rows), deterministic mode: two steps from one state agree bit for bit -- logits, input gradient, every parameter
+    gradient.  Float-atomic noise is switched off here, so a difference is a race or an uninitialised read (DESIGN, wide variants:
+    the default-mode spread of the bf16 gradients)."""
+    from lm_net_amd import hip
+    x = det_input((2, 3, 64, 64), "wide_det16/x").cuda()
+    G = det_input((2, 2, 64, 64), "wide_det16/G").cuda()
+    hip.set_deterministic(True)
+    try:
+        _, m = _pair(WIDE[name], 21)
+        m.train()
+        m.deterministic = True
+        m.compute_dtype = "bf16"
+        sd = {k: v.clone() for k, v in m.state_dict().items()}
+        runs = []
+        for _ in range(2):
+            m.load_state_dict(sd)
+            m.zero_grad(set_to_none=True)
+            xg = x.clone().requires_grad_(True)
+            y = m(xg)
+            (y * G).sum().backward()
+            torch.cuda.synchronize()
+            runs.append((y.detach().clone(), xg.grad.detach().clone(), [(k, p.grad.detach().clone()) for k, p in m.named_parameters()]))
+    finally:
+        hip.set_deterministic(False)
+    (ya, gxa, ga), (yb, gxb, gb) = runs
+    assert torch.isfinite(ya).all() and float(ya.abs().max()) > 0
+    assert torch.equal(ya, yb), "logits differ"
+    assert torch.equal(gxa, gxb), "input gradient differs"
+    differ = [k for (k, u), (_, v) in zip(ga, gb) if not torch.equal(u, v)]
+    assert not differ, "%d of %d parameter gradients differ between two deterministic bf16 steps: %s" % (len(differ), len(ga), differ[:8])
+
+
 @pytest.mark.parametrize("filters", [[12, 24, 48, 396, 192], [48, 96, 192, 384, 828]])
 def test_outside_envelope_raises_before_launch(filters):
     from lm_net_amd import LM_Net, hip
