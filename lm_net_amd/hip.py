@@ -342,6 +342,19 @@ DISTMAP_BOUNDARY = 0
 DISTMAP_HAUSDORFF = 1
 DISTMAP_SUMS_WORDS = 4
 
+# include/lovasz/lmnet_lovasz.h: the Lovasz-Softmax loss and the Lovasz hinge on a stable segmented device sort (lm_net_amd.loss.
+# LovaszLoss, lovasz_ranks).  A list of its own for the same reason, and no struct; tests/test_lovasz_cpu.py checks it against the
+# header and ties the three device entries to tests/test_guard_lovasz_gpu.py.
+SYMBOLS_LOVASZ = ["lmn_lovasz_workspace", "lmn_lovasz_order", "lmn_lovasz_fwd", "lmn_lovasz_bwd"]
+LOVASZ_TILE = 2048           # LMN_LOVASZ_* of the header
+LOVASZ_SCAN_THREADS = 64
+LOVASZ_MAX_SEGMENTS = 65535
+LOVASZ_LABELS_U8 = 0
+LOVASZ_LABELS_I64 = 1
+LOVASZ_SOFTMAX = 0
+LOVASZ_SIGMOID = 1
+LOVASZ_SUMS_WORDS = 4
+
 _lib = None
 
 
@@ -355,7 +368,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -370,6 +383,7 @@ def load():
     lib.lmn_volpost_workspace.restype = C.c_int64
     lib.lmn_lesion_workspace.restype = C.c_int64
     lib.lmn_dist_workspace.restype = C.c_int64
+    lib.lmn_lovasz_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1581,6 +1595,83 @@ def dist_loss_bwd(logits, target, head, term, alpha, class_mask, sd2_g, sd2_p, s
                                     B, Cn, H, W, C.c_uint64(int(class_mask)), _raw(sd2_g, torch.int32, "dist_loss_bwd"),
                                     _raw(sd2_p, torch.int32, "dist_loss_bwd"), _raw(sums, torch.int32, "dist_loss_bwd"), _p(gscale),
                                     _p(dlogits), _stream()), "dist_loss_bwd")
+
+
+def lovasz_workspace(S, P):
+    """Bytes of scratch lmn_lovasz_order / lmn_lovasz_fwd need for S segments of P elements, exactly (host arithmetic, no GPU)."""
+    n = int(load().lmn_lovasz_workspace(int(S), _i64(P)))
+    if n < 0:
+        raise ValueError("lm_net_amd.lovasz_workspace: " + load().lmn_last_error().decode())
+    return n
+
+
+def lovasz_label_kind(t):
+    """LMN_LOVASZ_LABELS_* of a target tensor: uint8 or int64."""
+    if t.dtype == torch.uint8:
+        return LOVASZ_LABELS_U8
+    if t.dtype == torch.int64:
+        return LOVASZ_LABELS_I64
+    raise ValueError("lm_net_amd: a uint8 or int64 target required, got %s" % t.dtype)
+
+
+def lovasz_order(keys, workspace, perm):
+    """perm int32 [S, P]: the stable ascending order of every row of keys [S, P] (lmn_lovasz_order): perm[s][r] is the index of the
+    r-th smallest key of row s, ties by index ascending.  keys: an int32 device tensor whose bits are read as uint32; workspace: uint8
+    device tensor of at least lovasz_workspace(S, P) bytes."""
+    if keys.dim() != 2 or tuple(perm.shape) != tuple(keys.shape):
+        raise ValueError("lm_net_amd.lovasz_order: keys %s and perm %s must both be [S, P]" % (tuple(keys.shape), tuple(perm.shape)))
+    S, P = keys.shape
+    _check(load().lmn_lovasz_order(_raw(keys, torch.int32, "lovasz_order"), int(S), _i64(P), _raw(workspace, torch.uint8, "lovasz_order"),
+                                   _i64(workspace.numel()), _raw(perm, torch.int32, "lovasz_order"), _stream()), "lovasz_order")
+
+
+def lovasz_segments(B, nk, H, W, per_image):
+    """(S, P) of a batch: one segment per scored class over the batch's pixels, or per (image, class) with per_image."""
+    return (B * nk, H * W) if per_image else (nk, B * H * W)
+
+
+def _lovasz_dims(what, logits, target, head, class_mask, coef):
+    if logits.dim() != 4:
+        raise ValueError("lm_net_amd.%s: logits must be [B, C, H, W], got %s" % (what, tuple(logits.shape)))
+    B, Cn, H, W = logits.shape
+    want = (B, H, W) if head == LOVASZ_SOFTMAX else (B, Cn, H, W)
+    if tuple(target.shape) != want or not target.is_cuda or not target.is_contiguous():
+        raise ValueError("lm_net_amd.%s: target %s, expected a contiguous device tensor %s" % (what, tuple(target.shape), want))
+    nk = bin(int(class_mask)).count("1")
+    if tuple(coef.shape) != (B, nk, H, W):
+        raise ValueError("lm_net_amd.%s: coef %s, expected %s" % (what, tuple(coef.shape), (B, nk, H, W)))
+    return B, Cn, H, W, nk
+
+
+def lovasz_fwd(logits, target, head, per_image, present, class_mask, scale, workspace, errors, perm, counts, coef, sums, loss):
+    """loss[0] = scale * the Lovasz-Softmax loss (LOVASZ_SOFTMAX: target a label map [B, H, W]) or the Lovasz hinge (LOVASZ_SIGMOID:
+    target planes [B, C, H, W]) of fp32 logits [B, C, H, W] over the classes of class_mask (lmn_lovasz_fwd).  With (S, P) =
+    lovasz_segments(...): errors fp32 [S, P], perm int32 [S, P], counts int32 [S, 2], coef fp32 [B, nk, H, W], sums int32 workspace of
+    LOVASZ_SUMS_WORDS words (read by lovasz_bwd), workspace uint8 of at least lovasz_workspace(S, P) bytes."""
+    B, Cn, H, W, nk = _lovasz_dims("lovasz_fwd", logits, target, head, class_mask, coef)
+    S, P = lovasz_segments(B, nk, H, W, per_image)
+    if tuple(errors.shape) != (S, P) or tuple(perm.shape) != (S, P) or tuple(counts.shape) != (S, 2):
+        raise ValueError("lm_net_amd.lovasz_fwd: errors %s / perm %s / counts %s do not hold [%d, %d] / [%d, %d] / [%d, 2]"
+                         % (tuple(errors.shape), tuple(perm.shape), tuple(counts.shape), S, P, S, P, S))
+    if sums.numel() < LOVASZ_SUMS_WORDS or loss.numel() < 1:
+        raise ValueError("lm_net_amd.lovasz_fwd: sums needs %d words and loss one float" % LOVASZ_SUMS_WORDS)
+    _check(load().lmn_lovasz_fwd(_p(logits), C.c_void_p(target.data_ptr()), lovasz_label_kind(target), int(head), int(bool(per_image)),
+                                 int(bool(present)), _f(scale), B, Cn, H, W, C.c_uint64(int(class_mask)),
+                                 _raw(workspace, torch.uint8, "lovasz_fwd"), _i64(workspace.numel()), _raw(errors, torch.float32, "lovasz_fwd"),
+                                 _raw(perm, torch.int32, "lovasz_fwd"), _raw(counts, torch.int32, "lovasz_fwd"),
+                                 _raw(coef, torch.float32, "lovasz_fwd"), _raw(sums, torch.int32, "lovasz_fwd"), _p(loss), _stream()),
+           "lovasz_fwd")
+
+
+def lovasz_bwd(logits, target, head, class_mask, coef, sums, gscale, dlogits):
+    """dlogits = gscale[0] * d loss / d logits (gscale None: 1) from the coef and sums of lovasz_fwd on the same arguments
+    (lmn_lovasz_bwd); every element of dlogits is written."""
+    B, Cn, H, W, nk = _lovasz_dims("lovasz_bwd", logits, target, head, class_mask, coef)
+    if sums.numel() < LOVASZ_SUMS_WORDS or tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous():
+        raise ValueError("lm_net_amd.lovasz_bwd: sums needs %d words and dlogits the logits' shape" % LOVASZ_SUMS_WORDS)
+    _check(load().lmn_lovasz_bwd(_p(logits), C.c_void_p(target.data_ptr()), lovasz_label_kind(target), int(head), B, Cn, H, W,
+                                 C.c_uint64(int(class_mask)), _raw(coef, torch.float32, "lovasz_bwd"), _raw(sums, torch.int32, "lovasz_bwd"),
+                                 _p(gscale), _p(dlogits), _stream()), "lovasz_bwd")
 
 
 def _raw(t, dt, what):

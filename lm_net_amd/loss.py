@@ -467,3 +467,150 @@ class HausdorffDTLoss(_DistLoss):
     def _prediction_maps(self, logits):
         self.pred_maps = distance_maps(logits, self.n_classes, self.classes, mode=self.head)[0]
         return self.pred_maps
+
+
+# ------------------------------------------------------------------------------------------------------------------------ Lovasz
+# The Lovasz-Softmax loss and the Lovasz hinge (include/lovasz/lmnet_lovasz.h): a stable segmented sort of the errors on the device,
+# an integer scan of the foreground over the sorted order and the closed form of Berman's lovasz_grad.
+_LOVASZ_HEADS = {"softmax": hip.LOVASZ_SOFTMAX, "sigmoid": hip.LOVASZ_SIGMOID}
+
+
+def _lovasz_config(what, n_classes, head, classes):
+    """(sorted class ids, class_mask, present) of the constructor arguments."""
+    if head not in _LOVASZ_HEADS:
+        raise ValueError("%s: head = %r, expected 'softmax' or 'sigmoid'" % (what, head))
+    if int(n_classes) != n_classes or not 1 <= n_classes <= 64:
+        raise ValueError("%s: n_classes = %r outside [1, 64]" % (what, n_classes))
+    if head == "softmax" and n_classes < 2:
+        raise ValueError("%s: a softmax head needs n_classes >= 2 (one logit: head='sigmoid')" % what)
+    if isinstance(classes, str):
+        if classes not in ("present", "all"):
+            raise ValueError("%s: classes = %r, expected 'present', 'all' or a list of class ids" % (what, classes))
+        if head == "sigmoid" and classes == "present":
+            classes = "all"                                # Berman's hinge skips no plane
+        ids = list(range(int(n_classes)))
+    else:
+        ids = [int(k) for k in classes]
+        if not ids or len(set(ids)) != len(ids) or any(k != c for k, c in zip(ids, classes)) or min(ids) < 0 or max(ids) >= n_classes:
+            raise ValueError("%s: classes %r must be distinct integers in [0, %d)" % (what, list(classes), n_classes))
+        ids.sort()
+    return ids, sum(1 << k for k in ids), classes == "present"
+
+
+def _lovasz_check(what, n_classes, head, nk, per_image, logits, target):
+    """-> (fp32 contiguous logits, contiguous target of the head's shape)"""
+    if logits.dim() != 4 or logits.shape[1] != n_classes or not logits.is_floating_point():
+        raise ValueError("%s: logits must be floating point [B, %d, H, W], got %s %s" % (what, n_classes, logits.dtype, tuple(logits.shape)))
+    B, Cn, H, W = logits.shape
+    if min(B, H, W) < 1 or B * Cn * H * W >= 1 << 31:
+        raise ValueError("%s: B * C * H * W = %d outside the limit [1, 2^31)" % (what, B * Cn * H * W))
+    if per_image and B * nk > hip.LOVASZ_MAX_SEGMENTS:
+        raise ValueError("%s: per_image: B * classes = %d segments above the limit %d" % (what, B * nk, hip.LOVASZ_MAX_SEGMENTS))
+    if target.dtype == torch.bool:
+        target = target.to(torch.uint8)
+    if target.dtype not in (torch.uint8, torch.int64):
+        raise ValueError("%s: target must be uint8, bool or int64, got %s" % (what, target.dtype))
+    if head == "softmax":
+        if target.dim() == 4 and target.shape[1] == 1:
+            target = target[:, 0]
+        ok = tuple(target.shape) == (B, H, W)
+    else:
+        if Cn == 1 and tuple(target.shape) == (B, H, W):
+            target = target[:, None]
+        ok = tuple(target.shape) == (B, Cn, H, W)
+    if not ok:
+        raise ValueError("%s: target %s does not match logits %s under a %s head" % (what, tuple(target.shape), tuple(logits.shape), head))
+    if not logits.is_cuda or not target.is_cuda:
+        raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % what)
+    return logits.float().contiguous(), target.contiguous()
+
+
+def _lovasz_buffers(device, B, nk, H, W, per_image):
+    """The scratch of one geometry: workspace, errors, perm, counts."""
+    S, P = hip.lovasz_segments(B, nk, H, W, per_image)
+    return (torch.empty(hip.lovasz_workspace(S, P), device=device, dtype=torch.uint8), torch.empty((S, P), device=device),
+            torch.empty((S, P), device=device, dtype=torch.int32), torch.empty((S, 2), device=device, dtype=torch.int32))
+
+
+class _LovaszFn(torch.autograd.Function):
+    """The loss entries of include/lovasz/lmnet_lovasz.h.  cfg = (head, per_image, present, class_mask, scale, buffers)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, cfg):
+        head, per_image, present, class_mask, scale, (ws, errors, perm, counts) = cfg
+        B, _, H, W = logits.shape
+        coef = torch.empty((B, errors.shape[0] * errors.shape[1] // (B * H * W), H, W), device=logits.device)
+        sums = torch.empty(hip.LOVASZ_SUMS_WORDS, device=logits.device, dtype=torch.int32)
+        loss = torch.empty(1, device=logits.device)
+        hip.lovasz_fwd(logits, target, head, per_image, present, class_mask, scale, ws, errors, perm, counts, coef, sums, loss)
+        ctx.save_for_backward(logits, target, coef, sums)
+        ctx.cfg = (head, class_mask)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, coef, sums = ctx.saved_tensors
+        head, class_mask = ctx.cfg
+        d = torch.empty_like(logits)
+        hip.lovasz_bwd(logits, target, head, class_mask, coef, sums, g.reshape(1).contiguous().float(), d)
+        return d, None, None
+
+
+class LovaszLoss(torch.nn.Module):
+    """The Lovasz-Softmax loss and, with ``head="sigmoid"``, the Lovasz hinge of Berman, Triki and Blaschko (CVPR 2018): the convex
+    Lovasz extension of the Jaccard loss, the one criterion of the package that trains against the mIoU column itself.  Per scored
+    class the errors ``|fg - softmax(z)_k|`` (hinge: ``1 - z (2 t - 1)``, entering as ``relu``) are sorted descending on the device
+    -- a stable segmented radix sort, ties by pixel index -- and weighted by the gradient of the Jaccard index along that order, taken
+    in closed form from an integer scan; ``scale`` times the class mean is returned.
+
+    ``classes="present"`` (Berman's default) averages over the classes that occur in the batch (in the image with ``per_image``),
+    ``"all"`` or a list of class ids over all of the scored ones; the hinge skips no plane.  ``per_image=True`` takes the extension
+    per image and averages over the images.  ``scale`` is a plain attribute read at every call, so ``seg(l, y) + lov(l, y)`` works as
+    it stands.  ``head="softmax"``: fp32 logits ``[B, C, H, W]`` and an int64 / uint8 label map ``[B, H, W]`` (``[B, 1, H, W]``
+    accepted), a pixel is valid when its label is in ``[0, C)`` and void otherwise, ``ignore_index`` or not.  ``head="sigmoid"``:
+    1 .. 64 planes, target planes ``[B, C, H, W]`` (or ``[B, H, W]`` at C = 1) of uint8 / bool / int64, an element is valid when its
+    target is 0 or 1.  Device tensors only; nothing synchronises; the scratch of a geometry (workspace, errors, order, counts) is kept
+    and the per-call tensors (coefficients, sums, loss, gradient) come from torch's caching allocator, so nothing is allocated on the
+    device after the first call of a geometry (``ranks`` holds the last ``(errors, perm, counts)``: they are overwritten by the next
+    call).  No float atomics: loss and gradient are bit-identical from call to call in either deterministic mode.
+    Deliberate difference from torch: a segment without a valid element contributes 0 and an average over no segment is 0 with an
+    all-zero gradient, never NaN; every void position has gradient +0.  Limits: B * C * H * W < 2^31, at most 65535 segments."""
+
+    def __init__(self, n_classes, head="softmax", classes="present", per_image=False, scale=1.0):
+        super().__init__()
+        self.classes, self.class_mask, self.present = _lovasz_config("LovaszLoss", n_classes, head, classes)
+        self.n_classes, self.head, self.per_image = int(n_classes), head, bool(per_image)
+        self.scale = float(scale)
+        self.ranks = None
+        self._buffers = {}
+
+    def forward(self, logits, target):
+        if not (self.scale - self.scale == 0.0):
+            raise ValueError("LovaszLoss: scale = %r is not finite" % self.scale)
+        nk = len(self.classes)
+        logits, target = _lovasz_check("LovaszLoss", self.n_classes, self.head, nk, self.per_image, logits, target)
+        B, _, H, W = logits.shape
+        key = (logits.device, B, H, W)
+        if key not in self._buffers:
+            self._buffers[key] = _lovasz_buffers(logits.device, B, nk, H, W, self.per_image)
+        buf = self._buffers[key]
+        self.ranks = buf[1:]
+        cfg = (_LOVASZ_HEADS[self.head], self.per_image, self.present, self.class_mask, self.scale, buf)
+        return _LovaszFn.apply(logits, target, cfg)
+
+
+def lovasz_ranks(logits, target, n_classes, head="softmax", classes="present", per_image=False):
+    """``(errors, perm, counts)`` of the Lovasz losses: with one segment per scored class over the ``P = B*H*W`` pixels of the batch
+    (``per_image``: per (image, class), ``s = b * nk + kk``, ``P = H*W``), ``errors`` fp32 ``[S, P]`` (0 at a void element), ``perm``
+    int32 ``[S, P]`` the stable order -- the valid elements by error descending, ties by element index ascending, the void elements
+    after them -- and ``counts`` int32 ``[S, 2]`` the valid and the valid foreground elements of every segment.  The arguments are
+    those of ``LovaszLoss``; fresh tensors are returned.  Device tensors only; nothing synchronises."""
+    ids, mask, present = _lovasz_config("lovasz_ranks", n_classes, head, classes)
+    logits, target = _lovasz_check("lovasz_ranks", int(n_classes), head, len(ids), per_image, logits.detach(), target)
+    B, _, H, W = logits.shape
+    ws, errors, perm, counts = _lovasz_buffers(logits.device, B, len(ids), H, W, bool(per_image))
+    coef = torch.empty((B, len(ids), H, W), device=logits.device)
+    sums = torch.empty(hip.LOVASZ_SUMS_WORDS, device=logits.device, dtype=torch.int32)
+    loss = torch.empty(1, device=logits.device)
+    hip.lovasz_fwd(logits, target, _LOVASZ_HEADS[head], bool(per_image), present, mask, 1.0, ws, errors, perm, counts, coef, sums, loss)
+    return errors, perm, counts
