@@ -355,6 +355,22 @@ LOVASZ_SOFTMAX = 0
 LOVASZ_SIGMOID = 1
 LOVASZ_SUMS_WORDS = 4
 
+# include/region/lmnet_region.h: the region-overlap losses -- Dice, Jaccard, Tversky and generalized Dice, per batch or per image
+# (lm_net_amd.loss.RegionLoss, region_sums).  A list of its own for the same reason, and no struct; tests/test_region_cpu.py checks
+# it against the header and ties the two device entries to tests/test_guard_region_gpu.py.
+SYMBOLS_REGION = ["lmn_region_workspace", "lmn_region_fwd", "lmn_region_bwd"]
+REGION_DICE = 0              # LMN_REGION_* of the header
+REGION_JACCARD = 1
+REGION_TVERSKY = 2
+REGION_GDICE = 3
+REGION_LINEAR = 0
+REGION_SQUARED = 1
+REGION_SOFTMAX = 0
+REGION_SIGMOID = 1
+REGION_LABELS_U8 = 0
+REGION_LABELS_I64 = 1
+REGION_MAX_BATCH = 65535
+
 _lib = None
 
 
@@ -368,7 +384,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ + SYMBOLS_REGION:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -384,6 +400,7 @@ def load():
     lib.lmn_lesion_workspace.restype = C.c_int64
     lib.lmn_dist_workspace.restype = C.c_int64
     lib.lmn_lovasz_workspace.restype = C.c_int64
+    lib.lmn_region_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1672,6 +1689,68 @@ def lovasz_bwd(logits, target, head, class_mask, coef, sums, gscale, dlogits):
     _check(load().lmn_lovasz_bwd(_p(logits), C.c_void_p(target.data_ptr()), lovasz_label_kind(target), int(head), B, Cn, H, W,
                                  C.c_uint64(int(class_mask)), _raw(coef, torch.float32, "lovasz_bwd"), _raw(sums, torch.int32, "lovasz_bwd"),
                                  _p(gscale), _p(dlogits), _stream()), "lovasz_bwd")
+
+
+def region_workspace(head, B, Cn, H, W, class_mask):
+    """Bytes of the deterministic-mode slots of lmn_region_fwd, exactly (host arithmetic, no GPU)."""
+    n = int(load().lmn_region_workspace(int(head), int(B), int(Cn), int(H), int(W), C.c_uint64(int(class_mask))))
+    if n < 0:
+        raise ValueError("lm_net_amd.region_workspace: " + load().lmn_last_error().decode())
+    return n
+
+
+def region_label_kind(t):
+    """LMN_REGION_LABELS_* of a target tensor: uint8 or int64."""
+    if t.dtype == torch.uint8:
+        return REGION_LABELS_U8
+    if t.dtype == torch.int64:
+        return REGION_LABELS_I64
+    raise ValueError("lm_net_amd: a uint8 or int64 target required, got %s" % t.dtype)
+
+
+def _region_dims(what, logits, target, head, per_image, class_mask, coef):
+    if logits.dim() != 4:
+        raise ValueError("lm_net_amd.%s: logits must be [B, C, H, W], got %s" % (what, tuple(logits.shape)))
+    B, Cn, H, W = logits.shape
+    want = (B, H, W) if head == REGION_SOFTMAX else (B, Cn, H, W)
+    if tuple(target.shape) != want or not target.is_cuda or not target.is_contiguous():
+        raise ValueError("lm_net_amd.%s: target %s, expected a contiguous device tensor %s" % (what, tuple(target.shape), want))
+    nk = bin(int(class_mask)).count("1")
+    G = B if per_image else 1
+    if tuple(coef.shape) != (G, nk, 3):
+        raise ValueError("lm_net_amd.%s: coef %s, expected %s" % (what, tuple(coef.shape), (G, nk, 3)))
+    return B, Cn, H, W, G, nk
+
+
+def region_fwd(logits, target, head, kind, denominator, per_image, alpha, beta, smooth, exponent, scale, class_mask, weight, workspace,
+               sums, counts, coef, per_class, loss):
+    """loss[0] = the region-overlap loss (lmn_region_fwd) of fp32 logits [B, C, H, W] under REGION_SOFTMAX (target a label map
+    [B, H, W]) or REGION_SIGMOID (target planes [B, C, H, W]) over the classes of class_mask.  With G = B (per_image) or 1: sums fp32
+    [G, nk, 3] (I, P1, P2), counts int32 [G, nk, 2] (T, N), coef fp32 [G, nk, 3] (read by region_bwd), per_class fp32 [G, nk]; weight
+    fp32 [nk] or None; workspace uint8 of at least region_workspace(...) bytes (None outside deterministic mode)."""
+    B, Cn, H, W, G, nk = _region_dims("region_fwd", logits, target, head, per_image, class_mask, coef)
+    if tuple(sums.shape) != (G, nk, 3) or tuple(counts.shape) != (G, nk, 2) or tuple(per_class.shape) != (G, nk) or loss.numel() < 1:
+        raise ValueError("lm_net_amd.region_fwd: sums %s / counts %s / per_class %s do not hold [%d, %d, 3] / [%d, %d, 2] / [%d, %d]"
+                         % (tuple(sums.shape), tuple(counts.shape), tuple(per_class.shape), G, nk, G, nk, G, nk))
+    if weight is not None and weight.numel() != nk:
+        raise ValueError("lm_net_amd.region_fwd: weight holds %d values for %d scored classes" % (weight.numel(), nk))
+    _check(load().lmn_region_fwd(_p(logits), C.c_void_p(target.data_ptr()), region_label_kind(target), int(head), int(kind), int(denominator),
+                                 int(bool(per_image)), _f(alpha), _f(beta), _f(smooth), _f(exponent), _f(scale), B, Cn, H, W,
+                                 C.c_uint64(int(class_mask)), _raw(weight, torch.float32, "region_fwd"), _raw(workspace, torch.uint8, "region_fwd"),
+                                 _i64(0 if workspace is None else workspace.numel()), _raw(sums, torch.float32, "region_fwd"),
+                                 _raw(counts, torch.int32, "region_fwd"), _raw(coef, torch.float32, "region_fwd"),
+                                 _raw(per_class, torch.float32, "region_fwd"), _p(loss), _stream()), "region_fwd")
+
+
+def region_bwd(logits, target, head, per_image, class_mask, coef, gscale, dlogits):
+    """dlogits = gscale[0] * d loss / d logits (gscale None: 1) from the coef of region_fwd on the same arguments (lmn_region_bwd);
+    every element of dlogits is written."""
+    B, Cn, H, W, G, nk = _region_dims("region_bwd", logits, target, head, per_image, class_mask, coef)
+    if tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous():
+        raise ValueError("lm_net_amd.region_bwd: dlogits needs the logits' shape")
+    _check(load().lmn_region_bwd(_p(logits), C.c_void_p(target.data_ptr()), region_label_kind(target), int(head), int(bool(per_image)), B, Cn,
+                                 H, W, C.c_uint64(int(class_mask)), _raw(coef, torch.float32, "region_bwd"), _p(gscale), _p(dlogits), _stream()),
+           "region_bwd")
 
 
 def _raw(t, dt, what):

@@ -614,3 +614,184 @@ def lovasz_ranks(logits, target, n_classes, head="softmax", classes="present", p
     loss = torch.empty(1, device=logits.device)
     hip.lovasz_fwd(logits, target, _LOVASZ_HEADS[head], bool(per_image), present, mask, 1.0, ws, errors, perm, counts, coef, sums, loss)
     return errors, perm, counts
+
+
+# ------------------------------------------------------------------------------------------------------------------------ region overlap
+# Dice, Jaccard, Tversky / focal Tversky and generalized Dice, per batch or per image (include/region/lmnet_region.h): one sums pass
+# over logits and labels, a one-block finish in fp64, one pointwise backward.
+_REGION_HEADS = {"softmax": hip.REGION_SOFTMAX, "sigmoid": hip.REGION_SIGMOID}
+_REGION_KINDS = {"dice": hip.REGION_DICE, "jaccard": hip.REGION_JACCARD, "tversky": hip.REGION_TVERSKY, "generalized_dice": hip.REGION_GDICE}
+_REGION_DENOMINATORS = {"linear": hip.REGION_LINEAR, "squared": hip.REGION_SQUARED}
+
+
+def _region_config(what, n_classes, head, classes):
+    """(sorted class ids, class_mask) of the constructor arguments."""
+    if head not in _REGION_HEADS:
+        raise ValueError("%s: head = %r, expected 'softmax' or 'sigmoid'" % (what, head))
+    if int(n_classes) != n_classes or not 1 <= n_classes <= 64:
+        raise ValueError("%s: n_classes = %r outside [1, 64]" % (what, n_classes))
+    if head == "softmax" and n_classes < 2:
+        raise ValueError("%s: a softmax head needs n_classes >= 2 (one logit: head='sigmoid')" % what)
+    if classes is None:
+        ids = list(range(int(n_classes)))
+    else:
+        if isinstance(classes, str):
+            raise ValueError("%s: classes = %r, expected None or a list of class ids" % (what, classes))
+        ids = [int(k) for k in classes]
+        if not ids or len(set(ids)) != len(ids) or any(k != c for k, c in zip(ids, classes)) or min(ids) < 0 or max(ids) >= n_classes:
+            raise ValueError("%s: classes %r must be distinct integers in [0, %d)" % (what, list(classes), n_classes))
+        ids.sort()
+    return ids, sum(1 << k for k in ids)
+
+
+def _region_check(what, n_classes, head, logits, target):
+    """-> (fp32 contiguous logits, contiguous target of the head's shape)"""
+    if logits.dim() != 4 or logits.shape[1] != n_classes or not logits.is_floating_point():
+        raise ValueError("%s: logits must be floating point [B, %d, H, W], got %s %s" % (what, n_classes, logits.dtype, tuple(logits.shape)))
+    B, Cn, H, W = logits.shape
+    if min(B, H, W) < 1 or B * Cn * H * W >= 1 << 31:
+        raise ValueError("%s: B * C * H * W = %d outside the limit [1, 2^31)" % (what, B * Cn * H * W))
+    if B > hip.REGION_MAX_BATCH:
+        raise ValueError("%s: B = %d above the limit %d" % (what, B, hip.REGION_MAX_BATCH))
+    if target.dtype == torch.bool:
+        target = target.to(torch.uint8)
+    if target.dtype not in (torch.uint8, torch.int64):
+        raise ValueError("%s: target must be uint8, bool or int64, got %s" % (what, target.dtype))
+    if head == "softmax":
+        if target.dim() == 4 and target.shape[1] == 1:
+            target = target[:, 0]
+        ok = tuple(target.shape) == (B, H, W)
+    else:
+        if Cn == 1 and tuple(target.shape) == (B, H, W):
+            target = target[:, None]
+        ok = tuple(target.shape) == (B, Cn, H, W)
+    if not ok:
+        raise ValueError("%s: target %s does not match logits %s under a %s head" % (what, tuple(target.shape), tuple(logits.shape), head))
+    if not logits.is_cuda or not target.is_cuda:
+        raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % what)
+    return logits.float().contiguous(), target.contiguous()
+
+
+def _region_buffers(device, head, B, Cn, H, W, class_mask, nk, per_image):
+    """The scratch of one geometry: workspace (the deterministic-mode slots), sums, counts, per_class."""
+    G = B if per_image else 1
+    return (torch.empty(hip.region_workspace(_REGION_HEADS[head], B, Cn, H, W, class_mask), device=device, dtype=torch.uint8),
+            torch.empty((G, nk, 3), device=device), torch.empty((G, nk, 2), device=device, dtype=torch.int32), torch.empty((G, nk), device=device))
+
+
+class _RegionFn(torch.autograd.Function):
+    """The loss entries of include/region/lmnet_region.h.  cfg = (head, kind, denominator, per_image, alpha, beta, smooth, exponent,
+    scale, class_mask, weight, buffers)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, cfg):
+        head, kind, den, per_image, alpha, beta, smooth, exponent, scale, class_mask, weight, (ws, sums, counts, per_class) = cfg
+        coef = torch.empty_like(sums)
+        loss = torch.empty(1, device=logits.device)
+        hip.region_fwd(logits, target, head, kind, den, per_image, alpha, beta, smooth, exponent, scale, class_mask, weight, ws, sums, counts,
+                       coef, per_class, loss)
+        ctx.save_for_backward(logits, target, coef)
+        ctx.cfg = (head, per_image, class_mask)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, coef = ctx.saved_tensors
+        head, per_image, class_mask = ctx.cfg
+        d = torch.empty_like(logits)
+        hip.region_bwd(logits, target, head, per_image, class_mask, coef, g.reshape(1).contiguous().float(), d)
+        return d, None, None
+
+
+class RegionLoss(torch.nn.Module):
+    """The region-overlap losses: soft Dice, soft Jaccard, Tversky / focal Tversky (Salehi et al. 2017; Abraham and Khan 2019) and the
+    generalized Dice loss (Sudre et al. 2017), per batch or per image (nnU-Net's ``batch_dice=False``), under a softmax or a sigmoid
+    head.  With the sums of a group (one image with ``per_image``, else the batch) and a scored class, ``I = sum p t``, ``P1 = sum p``,
+    ``P2 = sum p^2``, ``T = sum t`` over the valid elements, ``D = P2 + T`` (``denominator="squared"``) or ``P1 + T`` (``"linear"``),
+    ``s = smooth``:
+
+      ``dice``              ``R = (2 I + s) / (D + s)``
+      ``jaccard``           ``R = (I + s) / (D - I + s)``
+      ``tversky``           ``R = (I + s) / (I + alpha (P1 - I) + beta (T - I) + s)``; linear only
+      ``generalized_dice``  ``R_g = (2 sum_k v_k I_k + s) / (sum_k v_k (P1_k + T_k) + s)``, ``v_k = 1 / T_k^2``, a class absent from the
+                            group takes the group's largest finite ``v`` (MONAI's rule); linear only, no ``weight``
+
+    ``L = (1 - R) ** exponent`` (``exponent=0.75`` is the focal Tversky loss at gamma = 4/3) and the result is
+    ``scale / (G nk) * sum_g sum_k weight_k L_gk``.  ``classes=None`` scores all classes, the background included (the reference's
+    ``DiceLoss``); a list of ids scores those (nnU-Net's ``do_bg=False``).  ``denominator=None`` means ``"squared"`` for dice and jaccard,
+    the reference's form, and ``"linear"`` for the other two kinds.  ``scale`` is a plain attribute read at every call, so
+    ``seg(l, y) + reg(l, y)`` works as it stands.  ``per_class`` holds the device tensor ``[G, nk]`` of ``L_gk`` (unweighted, unscaled)
+    of the last call, ``sums`` / ``counts`` its ``[G, nk, 3]`` / ``[G, nk, 2]`` overlaps (I, P1, P2 / T, N); they are overwritten by the
+    next call of the same geometry.
+
+    ``head="softmax"``: fp32 logits ``[B, C, H, W]`` and an int64 / uint8 label map ``[B, H, W]`` (``[B, 1, H, W]`` accepted), a pixel is
+    valid when its label is in ``[0, C)`` and void otherwise, ``ignore_index`` or not.  ``head="sigmoid"``: 1 .. 64 planes, target planes
+    ``[B, C, H, W]`` (or ``[B, H, W]`` at C = 1) of uint8 / bool / int64, an element is valid when its target is 0 or 1.  Device tensors
+    only; nothing synchronises; the scratch of a geometry is kept and the per-call tensors come from torch's caching allocator, so
+    nothing is allocated on the device after the first call of a geometry.
+    Deliberate difference from torch: a denominator that is exactly 0 gives R = 1, a group without a valid element contributes 0, the
+    loss is never NaN, ``u = 1 - R <= 0`` under ``exponent != 1`` gives 0 with a zero gradient, and every void position has gradient
+    +0.  Limits: B <= 65535, B * C * H * W < 2^31."""
+
+    def __init__(self, n_classes, kind="dice", head="softmax", classes=None, weight=None, per_image=False, denominator=None, smooth=1e-5,
+                 alpha=0.5, beta=0.5, exponent=1.0, scale=1.0):
+        super().__init__()
+        self.classes, self.class_mask = _region_config("RegionLoss", n_classes, head, classes)
+        if kind not in _REGION_KINDS:
+            raise ValueError("RegionLoss: kind = %r, expected one of %s" % (kind, sorted(_REGION_KINDS)))
+        if denominator is None:
+            denominator = "squared" if kind in ("dice", "jaccard") else "linear"
+        if denominator not in _REGION_DENOMINATORS:
+            raise ValueError("RegionLoss: denominator = %r, expected 'linear' or 'squared'" % (denominator,))
+        if denominator == "squared" and kind not in ("dice", "jaccard"):
+            raise ValueError("RegionLoss: the squared denominator exists for dice and jaccard only, not for %s" % kind)
+        if not (0.0 <= alpha < float("inf") and 0.0 <= beta < float("inf")):
+            raise ValueError("RegionLoss: alpha = %r, beta = %r must be finite and >= 0" % (alpha, beta))
+        if not 0.0 <= smooth < float("inf"):
+            raise ValueError("RegionLoss: smooth = %r must be finite and >= 0" % (smooth,))
+        if not 0.0 < exponent <= 8.0:
+            raise ValueError("RegionLoss: exponent = %r outside (0, 8]" % (exponent,))
+        if weight is not None:
+            if kind == "generalized_dice":
+                raise ValueError("RegionLoss: generalized_dice takes no class weight (its weights are 1 / T_k^2)")
+            weight = torch.as_tensor(weight, dtype=torch.float32).reshape(-1)
+            if weight.numel() != len(self.classes) or not bool(torch.isfinite(weight).all()):
+                raise ValueError("RegionLoss: weight needs %d finite values, one per scored class" % len(self.classes))
+        self.register_buffer("weight", weight)
+        self.n_classes, self.kind, self.head, self.per_image, self.denominator = int(n_classes), kind, head, bool(per_image), denominator
+        self.smooth, self.alpha, self.beta, self.exponent = float(smooth), float(alpha), float(beta), float(exponent)
+        self.scale = float(scale)
+        self.per_class = self.sums = self.counts = None
+        self._scratch = {}            # (not _buffers: that is torch.nn.Module's own registry)
+
+    def forward(self, logits, target):
+        if not (self.scale - self.scale == 0.0):
+            raise ValueError("RegionLoss: scale = %r is not finite" % self.scale)
+        logits, target = _region_check("RegionLoss", self.n_classes, self.head, logits, target)
+        B, Cn, H, W = logits.shape
+        key = (logits.device, B, H, W)
+        if key not in self._scratch:
+            self._scratch[key] = _region_buffers(logits.device, self.head, B, Cn, H, W, self.class_mask, len(self.classes), self.per_image)
+        buf = self._scratch[key]
+        if self.weight is not None and self.weight.device != logits.device:
+            self.weight = self.weight.to(logits.device)
+        self.sums, self.counts, self.per_class = buf[1:]
+        cfg = (_REGION_HEADS[self.head], _REGION_KINDS[self.kind], _REGION_DENOMINATORS[self.denominator], self.per_image, self.alpha, self.beta,
+               self.smooth, self.exponent, self.scale, self.class_mask, self.weight, buf)
+        return _RegionFn.apply(logits, target, cfg)
+
+
+def region_sums(logits, target, n_classes, head="softmax", classes=None, per_image=False):
+    """``(sums, counts)``: the soft overlaps of every (group, scored class) -- ``sums`` fp32 ``[G, nk, 3]`` = ``sum p t``, ``sum p``,
+    ``sum p^2`` and ``counts`` int32 ``[G, nk, 2]`` = ``sum t`` and the number of valid elements, ``G = B`` with ``per_image``, else 1
+    -- for monitoring a soft Dice without a synchronisation.  The arguments are those of ``RegionLoss``; fresh tensors are returned.
+    Device tensors only; nothing synchronises."""
+    ids, mask = _region_config("region_sums", n_classes, head, classes)
+    logits, target = _region_check("region_sums", int(n_classes), head, logits.detach(), target)
+    B, Cn, H, W = logits.shape
+    ws, sums, counts, per_class = _region_buffers(logits.device, head, B, Cn, H, W, mask, len(ids), bool(per_image))
+    coef = torch.empty_like(sums)
+    loss = torch.empty(1, device=logits.device)
+    hip.region_fwd(logits, target, _REGION_HEADS[head], hip.REGION_DICE, hip.REGION_SQUARED, bool(per_image), 0.5, 0.5, 1e-5, 1.0, 1.0, mask,
+                   None, ws, sums, counts, coef, per_class, loss)
+    return sums, counts
