@@ -23,27 +23,22 @@
 #define DM_MAXSIDE LMN_DISTMAP_MAX_SIDE
 #define DM_SEG 16                 // row segments per block of dm_col_kernel: ceil(1024 / 16) = 64 rows fit one 64-bit mask
 #define DM_MAXC 64
+static_assert(LMN_DISTMAP_LABELS_U8 == LOSS_LABELS_U8 && LMN_DISTMAP_LABELS_I64 == LOSS_LABELS_I64 && LMN_DISTMAP_SOFTMAX == LOSS_SOFTMAX &&
+              LMN_DISTMAP_SIGMOID == LOSS_SIGMOID, "loss_common.h reads the label kinds and heads of lmnet_distmap.h");
 
 namespace {
 
-struct DmCls { uint8_t id[64]; };
-
-// a label as int64 (a uint8 value is never negative); KIND: LMN_DISTMAP_LABELS_*
-__device__ __forceinline__ int64_t dm_label(const void* __restrict__ p, int kind, int64_t i) {
-  return kind == LMN_DISTMAP_LABELS_I64 ? ((const int64_t*)p)[i] : (int64_t)((const uint8_t*)p)[i];
-}
-
-__global__ __launch_bounds__(256) void dm_mask_labels_kernel(const void* __restrict__ labels, int kind, int nk, DmCls cls, int64_t hw,
+__global__ __launch_bounds__(256) void dm_mask_labels_kernel(const void* __restrict__ labels, int kind, int nk, LossCls cls, int64_t hw,
                                                              int64_t total, uint8_t* __restrict__ mask) {
   for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t b = idx / hw, i = idx - b * hw;
-    const int64_t y = dm_label(labels, kind, idx);      // (a value outside [0, C) equals no class id)
+    const int64_t y = loss_label(labels, kind, idx);      // (a value outside [0, C) equals no class id)
     for (int kk = 0; kk < nk; ++kk) mask[(b * nk + kk) * hw + i] = (uint8_t)(y == (int64_t)cls.id[kk]);
   }
 }
 
 template <int MODE>
-__global__ __launch_bounds__(256) void dm_mask_logits_kernel(const float* __restrict__ logits, float thr, int C, int nk, DmCls cls,
+__global__ __launch_bounds__(256) void dm_mask_logits_kernel(const float* __restrict__ logits, float thr, int C, int nk, LossCls cls,
                                                              int64_t hw, int64_t total, uint8_t* __restrict__ mask) {
   for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t b = idx / hw, i = idx - b * hw;
@@ -239,7 +234,7 @@ __global__ __launch_bounds__(256) void dl_softmax_kernel(DlArgs a, uint32_t* __r
       else zs[c * 256] = v;
       mx = fmaxf(mx, v);
     }
-    const int64_t yl = dm_label(a.target, a.kind, idx);
+    const int64_t yl = loss_label(a.target, a.kind, idx);
     if ((uint64_t)yl >= (uint64_t)C) {                    // void: adds to no sum, +0 in every class
       if constexpr (BWD) {
         float* d = dlogits + b * C * hw + i;
@@ -307,7 +302,7 @@ __global__ __launch_bounds__(256) void dl_sigmoid_kernel(DlArgs a, uint32_t* __r
     const int c = (int)(plane - b * a.C);
     float d = 0.f;                                        // unscored plane, void element: +0
     if ((a.cmask >> c) & 1) {
-      const int64_t t = dm_label(a.target, a.kind, idx);
+      const int64_t t = loss_label(a.target, a.kind, idx);
       if ((uint64_t)t <= 1ull) {
         const int kk = __popcll(a.cmask & ((1ull << c) - 1ull));
         const SigPoint s = sig_point(a.logits[idx]);
@@ -341,26 +336,13 @@ int64_t dm_mask_bytes(int64_t np, int64_t HW) { return lmn_up256(np * HW); }
 int64_t dm_g_bytes(int64_t np, int64_t HW) { return lmn_up256(np * HW * (int64_t)sizeof(uint16_t)); }
 int64_t dm_count_bytes(int64_t np) { return lmn_up256(np * (int64_t)sizeof(int32_t)); }
 
-// the classes of a mask in ascending order; the number of them
-int dm_classes(uint64_t class_mask, DmCls* cls) {
-  int nk = 0;
-  memset(cls, 0, sizeof(*cls));
-  for (int c = 0; c < 64; ++c)
-    if ((class_mask >> c) & 1) cls->id[nk++] = (uint8_t)c;
-  return nk;
-}
-
 // the argument checks the three device entries share
 int dm_check(const char* what, int B, int C, int H, int W, uint64_t class_mask, int kind, bool softmax) {
   LMN_REQUIRE(B >= 1, "%s: B=%d < 1", what, B);
-  LMN_REQUIRE(C >= 1 && C <= DM_MAXC, "%s: C=%d not in [1, %d]", what, C, DM_MAXC);
-  LMN_REQUIRE(C >= 2 || !softmax, "%s: C=1 needs a sigmoid head (softmax over one class is constant)", what);
+  if (int rc = loss_check_head(what, C, softmax, class_mask, kind)) return rc;
   LMN_REQUIRE(H >= 2 && H <= DM_MAXSIDE && W >= 2 && W <= DM_MAXSIDE, "%s: size %dx%d outside [2, %d]", what, H, W, DM_MAXSIDE);
-  const uint64_t all = C == 64 ? ~0ull : ((1ull << C) - 1);
-  LMN_REQUIRE(class_mask != 0 && !(class_mask & ~all), "%s: class_mask is empty or names a class >= C=%d", what, C);
   LMN_REQUIRE((int64_t)B * __builtin_popcountll(class_mask) * H * W < (1LL << 31), "%s: B * nk * H * W = %lld not below 2^31", what,
               (long long)B * __builtin_popcountll(class_mask) * H * W);
-  LMN_REQUIRE(kind == LMN_DISTMAP_LABELS_U8 || kind == LMN_DISTMAP_LABELS_I64, "%s: unknown label kind %d", what, kind);
   return 0;
 }
 
@@ -446,8 +428,8 @@ int lmn_dist_map(const float* logits, const void* labels, int label_kind, float 
   if (int rc = dm_check("dist_map", B, C, H, W, class_mask, labels ? label_kind : LMN_DISTMAP_LABELS_U8,
                         logits && mode == LMN_DISTMAP_SOFTMAX))
     return rc;
-  DmCls cls;
-  const int nk = dm_classes(class_mask, &cls);
+  LossCls cls;
+  const int nk = loss_classes(class_mask, &cls);
   const int64_t need = lmn_dist_workspace(B, nk, H, W);
   LMN_REQUIRE(need >= 0 && ws_bytes >= need, "dist_map: workspace of %lld bytes too small, %lld needed", (long long)ws_bytes, (long long)need);
   const int64_t HW = (int64_t)H * W, total = (int64_t)B * HW;

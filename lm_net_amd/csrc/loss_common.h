@@ -2,10 +2,44 @@
 // reductions, the sigmoid focal term and its derivative, the zero-fill of a reduction's start, the capped grid and the checks of the
 // scalar parameters both param structs carry.  Everything else -- the sums and dlogits kernels, the two finish kernels (which treat
 // dice_scale = 0 and the pixel counts differently on purpose) -- stays in its own file.  metrics.hip takes the zero fill and the grid.
+// The three criteria, distmap.hip, lovasz.hip and region.hip, take the wave sum, the sigmoid point, the zero fill and the grid too,
+// and share the front end of their entries: the class list of a
+// class_mask (LossCls, loss_classes), the run-time-kind reader of a label (loss_label; region.hip's clamped, vectorised readers are its
+// own) and the four argument rules on C, the head, class_mask and the label kind (loss_check_head).  Each keeps its own B, size and
+// product rules, its kernels and the way it gets its deterministic slots.
 #pragma once
 #include "common.h"
 
 namespace {
+
+// what the headers of the three criteria name LMN_*_LABELS_U8 / _I64 and LMN_*_SOFTMAX / _SIGMOID: every source static_asserts it
+constexpr int LOSS_LABELS_U8 = 0, LOSS_LABELS_I64 = 1, LOSS_SOFTMAX = 0, LOSS_SIGMOID = 1;
+
+// the scored classes in ascending order; kernels take it by value
+struct LossCls { uint8_t id[64]; };
+// fills cls from a class_mask; the number of classes
+inline int loss_classes(uint64_t class_mask, LossCls* cls) {
+  int nk = 0;
+  memset(cls, 0, sizeof(*cls));
+  for (int c = 0; c < 64; ++c)
+    if ((class_mask >> c) & 1) cls->id[nk++] = (uint8_t)c;
+  return nk;
+}
+
+// a label or target element as int64 (a uint8 value is never negative); kind: LOSS_LABELS_*
+__device__ __forceinline__ int64_t loss_label(const void* __restrict__ p, int kind, int64_t i) {
+  return kind == LOSS_LABELS_I64 ? ((const int64_t*)p)[i] : (int64_t)((const uint8_t*)p)[i];
+}
+
+// the rules on the class count, the head, class_mask and the label kind that the entries of the three criteria share
+inline int loss_check_head(const char* what, int C, bool softmax, uint64_t class_mask, int label_kind) {
+  LMN_REQUIRE(C >= 1 && C <= 64, "%s: C=%d not in [1, 64]", what, C);
+  LMN_REQUIRE(C >= 2 || !softmax, "%s: C=1 needs a sigmoid head (softmax over one class is constant)", what);
+  const uint64_t all = C == 64 ? ~0ull : ((1ull << C) - 1);
+  LMN_REQUIRE(class_mask != 0 && !(class_mask & ~all), "%s: class_mask is empty or names a class >= C=%d", what, C);
+  LMN_REQUIRE(label_kind == LOSS_LABELS_U8 || label_kind == LOSS_LABELS_I64, "%s: unknown label kind %d", what, label_kind);
+  return 0;
+}
 
 // 64-lane sum, butterfly m = 1 ... 32.  (lmn_wave_sum of common.h runs m = 32 ... 1 and rounds differently: the deterministic-mode
 // results of the losses are pinned to this order.)

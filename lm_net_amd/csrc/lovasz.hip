@@ -28,12 +28,11 @@
 #define LV_FG 0x80000000u
 #define LV_SCAN_THREADS LMN_LOVASZ_SCAN_THREADS
 static_assert(LV_SCAN_THREADS == 64 && LV_TILE % LV_THREADS == 0, "tile");
+static_assert(LMN_LOVASZ_LABELS_U8 == LOSS_LABELS_U8 && LMN_LOVASZ_LABELS_I64 == LOSS_LABELS_I64 && LMN_LOVASZ_SOFTMAX == LOSS_SOFTMAX &&
+              LMN_LOVASZ_SIGMOID == LOSS_SIGMOID, "loss_common.h reads the label kinds and heads of lmnet_lovasz.h");
 
 namespace {
 
-__device__ __forceinline__ int64_t lv_label(const void* __restrict__ p, int kind, int64_t i) {
-  return kind == LMN_LOVASZ_LABELS_I64 ? ((const int64_t*)p)[i] : (int64_t)((const uint8_t*)p)[i];
-}
 // descending float order as ascending unsigned order; -0 never reaches here (lv_canon)
 __device__ __forceinline__ uint32_t lv_key(float e) {
   const uint32_t b = __float_as_uint(e);
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_key_softmax_kernel(const float*
   const int64_t pix = (int64_t)(blockIdx.x - b * nbx) * LV_THREADS + threadIdx.x;
   if (pix < g.hw) {
     const float* lg = logits + b * g.C * g.hw + pix;
-    const int64_t yl = lv_label(target, g.kind, b * g.hw + pix);
+    const int64_t yl = loss_label(target, g.kind, b * g.hw + pix);
     const bool valid = (uint64_t)yl < (uint64_t)g.C;
     float mx = -3.0e38f, den = 0.f;
     for (int c = 0; c < g.C; ++c) mx = fmaxf(mx, lg[c * g.hw]);
@@ -118,9 +117,8 @@ __global__ __launch_bounds__(LV_THREADS) void lv_key_softmax_kernel(const float*
 }
 
 // blockIdx.x = (b * nk + kk) * nbx + (block of 256 elements of the plane); cls: the scored planes in ascending order
-struct LvCls { uint8_t id[64]; };
 __global__ __launch_bounds__(LV_THREADS) void lv_key_sigmoid_kernel(const float* __restrict__ logits, const void* __restrict__ target,
-                                                                    LvGeo g, LvCls cls, int nbx, float* __restrict__ errors,
+                                                                    LvGeo g, LossCls cls, int nbx, float* __restrict__ errors,
                                                                     uint32_t* __restrict__ keys, uint32_t* __restrict__ pay,
                                                                     int32_t* __restrict__ counts) {
   __shared__ int s_cnt[2];
@@ -136,7 +134,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_key_sigmoid_kernel(const float*
   bool valid = false, fg = false;
   if (pix < g.hw) {
     const int64_t src = (b * g.C + cls.id[kk]) * g.hw + pix;
-    const int64_t t = lv_label(target, g.kind, src);
+    const int64_t t = loss_label(target, g.kind, src);
     valid = (uint64_t)t <= 1ull;
     fg = t == 1;
     const float z = logits[src];
@@ -379,7 +377,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_bwd_softmax_kernel(const float*
     const int64_t b = idx / hw, pix = idx - b * hw;
     const float* lg = logits + b * g.C * hw + pix;
     float* d = dlogits + b * g.C * hw + pix;
-    const int64_t yl = lv_label(target, g.kind, idx);
+    const int64_t yl = loss_label(target, g.kind, idx);
     if ((uint64_t)yl >= (uint64_t)g.C) {                  // void: +0 in every class
       for (int c = 0; c < g.C; ++c) d[c * hw] = 0.f;
       continue;
@@ -423,7 +421,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_bwd_sigmoid_kernel(const void* 
     const int c = (int)(plane - b * g.C);
     float d = 0.f;                                        // unscored plane, void element: +0
     if ((g.cmask >> c) & 1) {
-      const int64_t t = lv_label(target, g.kind, idx);
+      const int64_t t = loss_label(target, g.kind, idx);
       if ((uint64_t)t <= 1ull) {
         const int kk = __popcll(g.cmask & ((1ull << c) - 1ull));
         const float v = coef[(b * g.nk + kk) * hw + pix];
@@ -487,13 +485,9 @@ void lv_sort(hipStream_t st, const uint32_t* k0, const uint32_t* p0, int S, int6
 int lv_check(const char* what, int target_kind, int head, int B, int C, int H, int W, uint64_t class_mask) {
   LMN_REQUIRE(head == LMN_LOVASZ_SOFTMAX || head == LMN_LOVASZ_SIGMOID, "%s: unknown head %d", what, head);
   LMN_REQUIRE(B >= 1, "%s: B=%d < 1", what, B);
-  LMN_REQUIRE(C >= 1 && C <= 64, "%s: C=%d not in [1, 64]", what, C);
-  LMN_REQUIRE(C >= 2 || head == LMN_LOVASZ_SIGMOID, "%s: C=1 needs a sigmoid head (softmax over one class is constant)", what);
+  if (int rc = loss_check_head(what, C, head == LMN_LOVASZ_SOFTMAX, class_mask, target_kind)) return rc;
   LMN_REQUIRE(H >= 1 && W >= 1, "%s: size %dx%d below 1", what, H, W);
   LMN_REQUIRE((int64_t)B * C * H * W < (1LL << 31), "%s: B * C * H * W = %lld not below 2^31", what, (long long)B * C * H * W);
-  const uint64_t all = C == 64 ? ~0ull : ((1ull << C) - 1);
-  LMN_REQUIRE(class_mask != 0 && !(class_mask & ~all), "%s: class_mask is empty or names a class >= C=%d", what, C);
-  LMN_REQUIRE(target_kind == LMN_LOVASZ_LABELS_U8 || target_kind == LMN_LOVASZ_LABELS_I64, "%s: unknown label kind %d", what, target_kind);
   return 0;
 }
 
@@ -552,10 +546,8 @@ int lmn_lovasz_fwd(const float* logits, const void* target, int target_kind, int
   if (head == LMN_LOVASZ_SOFTMAX) {
     LMN_LAUNCH(lv_key_softmax_kernel, dim3((unsigned)((int64_t)B * nbx)), dim3(LV_THREADS), 0, st, logits, target, g, nbx, errors, w.kB, w.pB, counts);
   } else {
-    LvCls cls;
-    memset(&cls, 0, sizeof(cls));
-    for (int c = 0, kk = 0; c < 64; ++c)
-      if ((class_mask >> c) & 1) cls.id[kk++] = (uint8_t)c;
+    LossCls cls;
+    loss_classes(class_mask, &cls);
     LMN_LAUNCH(lv_key_sigmoid_kernel, dim3((unsigned)((int64_t)B * g.nk * nbx)), dim3(LV_THREADS), 0, st, logits, target, g, cls, nbx, errors, w.kB,
                w.pB, counts);
   }

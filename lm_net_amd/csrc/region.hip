@@ -10,6 +10,8 @@
 //   coef   fp32 [G, nk, 3]: a, b, c with d loss / dp_k = a t + b + c p
 #include "loss_common.h"
 #include "../../include/region/lmnet_region.h"
+static_assert(LMN_REGION_LABELS_U8 == LOSS_LABELS_U8 && LMN_REGION_LABELS_I64 == LOSS_LABELS_I64 && LMN_REGION_SOFTMAX == LOSS_SOFTMAX &&
+              LMN_REGION_SIGMOID == LOSS_SIGMOID, "loss_common.h reads the label kinds and heads of lmnet_region.h");
 
 namespace {
 
@@ -17,14 +19,12 @@ constexpr int RG_STRIDE = 65;   // row stride of the staged tile of the general 
 constexpr int RG_MAXC = 64;
 constexpr int RG_CNT0 = 192;    // the first thread of a block that adds the integer counts (3 * RG_MAXC float sums come before it)
 
-struct RgCls { uint8_t id[RG_MAXC]; };   // the scored classes in ascending order
-
 // where a block of the sums pass adds its partial sums
 struct RgOut {
   float* sums;
   int32_t* counts;
   float* slots;   // deterministic mode, else NULL
-  RgCls cls;
+  LossCls cls;
   int nk, per_image;
 };
 
@@ -405,7 +405,7 @@ __global__ __launch_bounds__(256) void rg_finish_kernel(RgFin f, const float* __
 // the coefficients of the C classes of group g, 0 for an unscored class
 struct RgIn {
   const float* coef;
-  RgCls cls;
+  LossCls cls;
   int nk, per_image;
 };
 
@@ -556,22 +556,10 @@ inline int64_t rg_ws_bytes(int head, int B, int C, int64_t HW, int nk) {
 int rg_check(const char* what, int target_kind, int head, int B, int C, int H, int W, uint64_t class_mask) {
   LMN_REQUIRE(head == LMN_REGION_SOFTMAX || head == LMN_REGION_SIGMOID, "%s: unknown head %d", what, head);
   LMN_REQUIRE(B >= 1 && B <= LMN_REGION_MAX_BATCH, "%s: B=%d not in [1, %d]", what, B, LMN_REGION_MAX_BATCH);
-  LMN_REQUIRE(C >= 1 && C <= RG_MAXC, "%s: C=%d not in [1, %d]", what, C, RG_MAXC);
-  LMN_REQUIRE(C >= 2 || head == LMN_REGION_SIGMOID, "%s: C=1 needs a sigmoid head (softmax over one class is constant)", what);
+  if (int rc = loss_check_head(what, C, head == LMN_REGION_SOFTMAX, class_mask, target_kind)) return rc;
   LMN_REQUIRE(H >= 1 && W >= 1, "%s: size %dx%d below 1", what, H, W);
   LMN_REQUIRE((int64_t)B * C * H * W < (1LL << 31), "%s: B * C * H * W = %lld not below 2^31", what, (long long)B * C * H * W);
-  const uint64_t all = C == 64 ? ~0ull : ((1ull << C) - 1);
-  LMN_REQUIRE(class_mask != 0 && !(class_mask & ~all), "%s: class_mask is empty or names a class >= C=%d", what, C);
-  LMN_REQUIRE(target_kind == LMN_REGION_LABELS_U8 || target_kind == LMN_REGION_LABELS_I64, "%s: unknown label kind %d", what, target_kind);
   return 0;
-}
-
-RgCls rg_classes(uint64_t class_mask) {
-  RgCls cls;
-  memset(&cls, 0, sizeof(cls));
-  for (int c = 0, kk = 0; c < 64; ++c)
-    if ((class_mask >> c) & 1) cls.id[kk++] = (uint8_t)c;
-  return cls;
 }
 
 // run `...` once with the compile-time constants KIND and FLAG of the call
@@ -629,7 +617,7 @@ int lmn_region_fwd(const float* logits, const void* target, int target_kind, int
   o.sums = sums;
   o.counts = counts;
   o.slots = g_lmn_det ? (float*)workspace : nullptr;
-  o.cls = rg_classes(class_mask);
+  loss_classes(class_mask, &o.cls);
   o.nk = nk;
   o.per_image = per_image ? 1 : 0;
   const int64_t words = (int64_t)G * nk;
@@ -671,7 +659,7 @@ int lmn_region_bwd(const float* logits, const void* target, int target_kind, int
   const int64_t HW = (int64_t)H * W;
   RgIn in;
   in.coef = coef;
-  in.cls = rg_classes(class_mask);
+  loss_classes(class_mask, &in.cls);
   in.nk = __builtin_popcountll(class_mask);
   in.per_image = per_image ? 1 : 0;
   if (head == LMN_REGION_SOFTMAX) {

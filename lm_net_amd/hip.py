@@ -421,6 +421,13 @@ def _check(rc, what):
         raise RuntimeError("lm_net_amd.%s failed (code %d): %s" % (what, rc, load().lmn_last_error().decode()))
 
 
+def _host_size(name, n):
+    """The result of a size entry that is host arithmetic: negative means refused, with the reason in lmn_last_error."""
+    if n < 0:
+        raise ValueError("lm_net_amd.%s: " % name + load().lmn_last_error().decode())
+    return int(n)
+
+
 def _p(t):
     """fp32 device pointer (parameters, statistics, workspaces, fp32 boundary tensors)."""
     if t is None:
@@ -1346,10 +1353,7 @@ def curve_edges(thresholds, kind):
 
 def curve_workspace(score_kind, B, hw):
     """Bytes of scratch lmn_curve_hist needs: 0 for CURVE_RAW, 4 * B * hw for CURVE_SOFTMAX (host arithmetic, no GPU)."""
-    n = int(load().lmn_curve_workspace(int(score_kind), int(B), _i64(hw)))
-    if n < 0:
-        raise ValueError("lm_net_amd.curve_workspace: " + load().lmn_last_error().decode())
-    return n
+    return _host_size("curve_workspace", load().lmn_curve_workspace(int(score_kind), int(B), _i64(hw)))
 
 
 def curve_hist(values, target, target_form, score_kind, edges, hist, workspace=None):
@@ -1377,10 +1381,7 @@ def curve_hist(values, target, target_form, score_kind, edges, hist, workspace=N
 
 def surface_workspace(B, nk, H, W):
     """Bytes of scratch lmn_surface_dist needs for B samples x nk classes of H x W pixels (host arithmetic, no GPU)."""
-    n = int(load().lmn_surface_workspace(int(B), int(nk), int(H), int(W)))
-    if n < 0:
-        raise ValueError("lm_net_amd.surface_workspace: " + load().lmn_last_error().decode())
-    return n
+    return _host_size("surface_workspace", load().lmn_surface_workspace(int(B), int(nk), int(H), int(W)))
 
 
 def surface_dist(pred, target, n_classes, classes, workspace, stats_i, stats_f):
@@ -1408,10 +1409,7 @@ def surface_dist(pred, target, n_classes, classes, workspace, stats_i, stats_f):
 
 def volume_workspace(D, H, W, nk):
     """Bytes of scratch lmn_volume_dist needs for nk classes of a D x H x W volume, exactly (host arithmetic, no GPU)."""
-    n = int(load().lmn_volume_workspace(int(D), int(H), int(W), int(nk)))
-    if n < 0:
-        raise ValueError("lm_net_amd.volume_workspace: " + load().lmn_last_error().decode())
-    return n
+    return _host_size("volume_workspace", load().lmn_volume_workspace(int(D), int(H), int(W), int(nk)))
 
 
 def volume_span(shape, spacing):
@@ -1467,10 +1465,7 @@ def volume_dist(lab_pred, lab_target, n_classes, classes, spacing, workspace, st
 
 def volpost_workspace(D, H, W):
     """Bytes of scratch lmn_volpost_clean needs for a D x H x W volume, exactly (host arithmetic, no GPU)."""
-    n = int(load().lmn_volpost_workspace(int(D), int(H), int(W)))
-    if n < 0:
-        raise ValueError("lm_net_amd.volpost_workspace: " + load().lmn_last_error().decode())
-    return n
+    return _host_size("volpost_workspace", load().lmn_volpost_workspace(int(D), int(H), int(W)))
 
 
 def cc3d_label(labels, connectivity, roots, sizes):
@@ -1504,10 +1499,7 @@ def volpost_clean(labels, n_classes, connectivity, class_mask, keep_largest, min
 
 def lesion_workspace(D, H, W):
     """Bytes of scratch lmn_lesion_match needs for a D x H x W volume, exactly (host arithmetic, no GPU)."""
-    n = int(load().lmn_lesion_workspace(int(D), int(H), int(W)))
-    if n < 0:
-        raise ValueError("lm_net_amd.lesion_workspace: " + load().lmn_last_error().decode())
-    return n
+    return _host_size("lesion_workspace", load().lmn_lesion_workspace(int(D), int(H), int(W)))
 
 
 def lesion_match(pred, target, n_classes, connectivity, class_mask, workspace, comp_keys, comp_sizes, pair_keys, pair_counts, ctrl):
@@ -1533,32 +1525,46 @@ def lesion_match(pred, target, n_classes, connectivity, class_mask, workspace, c
                                    int(pair_keys.numel()), _raw(ctrl, torch.int32, "lesion_match"), _stream()), "lesion_match")
 
 
+# ---- what the wrappers of the three criteria (distance maps, Lovasz, region overlap) share
+assert (DISTMAP_LABELS_U8, LOVASZ_LABELS_U8, REGION_LABELS_U8, DISTMAP_LABELS_I64, LOVASZ_LABELS_I64, REGION_LABELS_I64) == (0, 0, 0, 1, 1, 1)
+
+
+def label_kind(t):
+    """LMN_*_LABELS_U8 / _I64 (0 / 1 in each of the three headers) of a label or target tensor: uint8 or int64."""
+    if t.dtype == torch.uint8:
+        return 0
+    if t.dtype == torch.int64:
+        return 1
+    raise ValueError("lm_net_amd: a uint8 or int64 target required, got %s" % t.dtype)
+
+
+def _nk(class_mask):
+    """the number of classes a class_mask scores"""
+    return bin(int(class_mask) & (2 ** 64 - 1)).count("1")
+
+
+def _loss_dims(what, logits, target, softmax):
+    """(B, C, H, W) of contiguous logits [B, C, H, W] and their contiguous device target: a label map [B, H, W] under a softmax head,
+    planes [B, C, H, W] under a sigmoid head."""
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise ValueError("lm_net_amd.%s: contiguous logits [B, C, H, W] required, got %s" % (what, tuple(logits.shape)))
+    B, Cn, H, W = logits.shape
+    want = (B, H, W) if softmax else (B, Cn, H, W)
+    if tuple(target.shape) != want or not target.is_cuda or not target.is_contiguous():
+        raise ValueError("lm_net_amd.%s: target %s, expected a contiguous device tensor %s" % (what, tuple(target.shape), want))
+    return B, Cn, H, W
+
+
 def dist_workspace(B, nk, H, W):
     """Bytes of scratch lmn_dist_map needs for B samples x nk classes of H x W pixels, exactly (host arithmetic, no GPU)."""
-    n = int(load().lmn_dist_workspace(int(B), int(nk), int(H), int(W)))
-    if n < 0:
-        raise ValueError("lm_net_amd.dist_workspace: " + load().lmn_last_error().decode())
-    return n
-
-
-def dist_label_kind(t):
-    """LMN_DISTMAP_LABELS_* of a label tensor: uint8 or int64."""
-    if t.dtype == torch.uint8:
-        return DISTMAP_LABELS_U8
-    if t.dtype == torch.int64:
-        return DISTMAP_LABELS_I64
-    raise ValueError("lm_net_amd: labels are uint8 or int64, got %s" % t.dtype)
-
-
-def _dist_nk(class_mask):
-    return bin(int(class_mask) & (2 ** 64 - 1)).count("1")
+    return _host_size("dist_workspace", load().lmn_dist_workspace(int(B), int(nk), int(H), int(W)))
 
 
 def dist_map(src, n_classes, class_mask, workspace, sd2, flags, mode=None, threshold=0.0):
     """sd2 int32 [B, nk, H, W] and flags int32 [B, nk] of the masks of the classes of class_mask (lmn_dist_map).  src: a uint8 / int64
     label map [B, H, W] (mode None), or fp32 logits [B, C, H, W] with mode DISTMAP_SOFTMAX (threshold: a probability) or
     DISTMAP_SIGMOID (threshold: a logit); workspace: uint8 device tensor of at least dist_workspace(B, nk, H, W) bytes."""
-    nk = _dist_nk(class_mask)
+    nk = _nk(class_mask)
     from_logits = mode is not None
     if src.dim() != (4 if from_logits else 3) or not src.is_contiguous() or (from_logits and src.shape[1] != n_classes):
         want = "logits [B, %d, H, W]" % n_classes if from_logits else "labels [B, H, W]"
@@ -1569,20 +1575,15 @@ def dist_map(src, n_classes, class_mask, workspace, sd2, flags, mode=None, thres
                          % (tuple(sd2.shape), tuple(flags.shape), B, nk, H, W, B, nk))
     logits = _p(src) if from_logits else None
     labels = None if from_logits else _raw(src, src.dtype, "dist_map")
-    kind = DISTMAP_LABELS_U8 if from_logits else dist_label_kind(src)
+    kind = DISTMAP_LABELS_U8 if from_logits else label_kind(src)
     _check(load().lmn_dist_map(logits, labels, kind, _f(threshold), int(mode or 0), B, int(n_classes), H, W, C.c_uint64(int(class_mask)),
                                _raw(workspace, torch.uint8, "dist_map"), _i64(workspace.numel()), _raw(sd2, torch.int32, "dist_map"),
                                _raw(flags, torch.int32, "dist_map"), _stream()), "dist_map")
 
 
 def _dist_loss_dims(what, logits, target, head, class_mask, sd2_g, sd2_p):
-    if logits.dim() != 4 or not logits.is_contiguous():
-        raise ValueError("lm_net_amd.%s: contiguous logits [B, C, H, W] required, got %s" % (what, tuple(logits.shape)))
-    B, Cn, H, W = logits.shape
-    want = (B, H, W) if head == DISTMAP_SOFTMAX else (B, Cn, H, W)
-    if tuple(target.shape) != want or not target.is_contiguous() or not target.is_cuda:
-        raise ValueError("lm_net_amd.%s: target %s: a contiguous device tensor %s required" % (what, tuple(target.shape), want))
-    nk = _dist_nk(class_mask)
+    B, Cn, H, W = _loss_dims(what, logits, target, head == DISTMAP_SOFTMAX)
+    nk = _nk(class_mask)
     for m in (sd2_g, sd2_p):
         if m is not None and tuple(m.shape) != (B, nk, H, W):
             raise ValueError("lm_net_amd.%s: distance map %s, expected %s" % (what, tuple(m.shape), (B, nk, H, W)))
@@ -1596,7 +1597,7 @@ def dist_loss_fwd(logits, target, head, term, alpha, scale, class_mask, sd2_g, s
     B, Cn, H, W = _dist_loss_dims("dist_loss_fwd", logits, target, head, class_mask, sd2_g, sd2_p)
     if sums.numel() < DISTMAP_SUMS_WORDS or loss.numel() < 1:
         raise ValueError("lm_net_amd.dist_loss_fwd: sums needs %d words and loss one float" % DISTMAP_SUMS_WORDS)
-    _check(load().lmn_dist_loss_fwd(_p(logits), C.c_void_p(target.data_ptr()), dist_label_kind(target), int(head), int(term), _f(alpha),
+    _check(load().lmn_dist_loss_fwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), int(term), _f(alpha),
                                     _f(scale), B, Cn, H, W, C.c_uint64(int(class_mask)), _raw(sd2_g, torch.int32, "dist_loss_fwd"),
                                     _raw(sd2_p, torch.int32, "dist_loss_fwd"), _raw(sums, torch.int32, "dist_loss_fwd"), _p(loss),
                                     _stream()), "dist_loss_fwd")
@@ -1608,7 +1609,7 @@ def dist_loss_bwd(logits, target, head, term, alpha, class_mask, sd2_g, sd2_p, s
     B, Cn, H, W = _dist_loss_dims("dist_loss_bwd", logits, target, head, class_mask, sd2_g, sd2_p)
     if sums.numel() < DISTMAP_SUMS_WORDS or tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous():
         raise ValueError("lm_net_amd.dist_loss_bwd: sums needs %d words and dlogits the logits' shape" % DISTMAP_SUMS_WORDS)
-    _check(load().lmn_dist_loss_bwd(_p(logits), C.c_void_p(target.data_ptr()), dist_label_kind(target), int(head), int(term), _f(alpha),
+    _check(load().lmn_dist_loss_bwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), int(term), _f(alpha),
                                     B, Cn, H, W, C.c_uint64(int(class_mask)), _raw(sd2_g, torch.int32, "dist_loss_bwd"),
                                     _raw(sd2_p, torch.int32, "dist_loss_bwd"), _raw(sums, torch.int32, "dist_loss_bwd"), _p(gscale),
                                     _p(dlogits), _stream()), "dist_loss_bwd")
@@ -1616,19 +1617,7 @@ def dist_loss_bwd(logits, target, head, term, alpha, class_mask, sd2_g, sd2_p, s
 
 def lovasz_workspace(S, P):
     """Bytes of scratch lmn_lovasz_order / lmn_lovasz_fwd need for S segments of P elements, exactly (host arithmetic, no GPU)."""
-    n = int(load().lmn_lovasz_workspace(int(S), _i64(P)))
-    if n < 0:
-        raise ValueError("lm_net_amd.lovasz_workspace: " + load().lmn_last_error().decode())
-    return n
-
-
-def lovasz_label_kind(t):
-    """LMN_LOVASZ_LABELS_* of a target tensor: uint8 or int64."""
-    if t.dtype == torch.uint8:
-        return LOVASZ_LABELS_U8
-    if t.dtype == torch.int64:
-        return LOVASZ_LABELS_I64
-    raise ValueError("lm_net_amd: a uint8 or int64 target required, got %s" % t.dtype)
+    return _host_size("lovasz_workspace", load().lmn_lovasz_workspace(int(S), _i64(P)))
 
 
 def lovasz_order(keys, workspace, perm):
@@ -1648,13 +1637,8 @@ def lovasz_segments(B, nk, H, W, per_image):
 
 
 def _lovasz_dims(what, logits, target, head, class_mask, coef):
-    if logits.dim() != 4:
-        raise ValueError("lm_net_amd.%s: logits must be [B, C, H, W], got %s" % (what, tuple(logits.shape)))
-    B, Cn, H, W = logits.shape
-    want = (B, H, W) if head == LOVASZ_SOFTMAX else (B, Cn, H, W)
-    if tuple(target.shape) != want or not target.is_cuda or not target.is_contiguous():
-        raise ValueError("lm_net_amd.%s: target %s, expected a contiguous device tensor %s" % (what, tuple(target.shape), want))
-    nk = bin(int(class_mask)).count("1")
+    B, Cn, H, W = _loss_dims(what, logits, target, head == LOVASZ_SOFTMAX)
+    nk = _nk(class_mask)
     if tuple(coef.shape) != (B, nk, H, W):
         raise ValueError("lm_net_amd.%s: coef %s, expected %s" % (what, tuple(coef.shape), (B, nk, H, W)))
     return B, Cn, H, W, nk
@@ -1672,7 +1656,7 @@ def lovasz_fwd(logits, target, head, per_image, present, class_mask, scale, work
                          % (tuple(errors.shape), tuple(perm.shape), tuple(counts.shape), S, P, S, P, S))
     if sums.numel() < LOVASZ_SUMS_WORDS or loss.numel() < 1:
         raise ValueError("lm_net_amd.lovasz_fwd: sums needs %d words and loss one float" % LOVASZ_SUMS_WORDS)
-    _check(load().lmn_lovasz_fwd(_p(logits), C.c_void_p(target.data_ptr()), lovasz_label_kind(target), int(head), int(bool(per_image)),
+    _check(load().lmn_lovasz_fwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), int(bool(per_image)),
                                  int(bool(present)), _f(scale), B, Cn, H, W, C.c_uint64(int(class_mask)),
                                  _raw(workspace, torch.uint8, "lovasz_fwd"), _i64(workspace.numel()), _raw(errors, torch.float32, "lovasz_fwd"),
                                  _raw(perm, torch.int32, "lovasz_fwd"), _raw(counts, torch.int32, "lovasz_fwd"),
@@ -1686,36 +1670,19 @@ def lovasz_bwd(logits, target, head, class_mask, coef, sums, gscale, dlogits):
     B, Cn, H, W, nk = _lovasz_dims("lovasz_bwd", logits, target, head, class_mask, coef)
     if sums.numel() < LOVASZ_SUMS_WORDS or tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous():
         raise ValueError("lm_net_amd.lovasz_bwd: sums needs %d words and dlogits the logits' shape" % LOVASZ_SUMS_WORDS)
-    _check(load().lmn_lovasz_bwd(_p(logits), C.c_void_p(target.data_ptr()), lovasz_label_kind(target), int(head), B, Cn, H, W,
+    _check(load().lmn_lovasz_bwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), B, Cn, H, W,
                                  C.c_uint64(int(class_mask)), _raw(coef, torch.float32, "lovasz_bwd"), _raw(sums, torch.int32, "lovasz_bwd"),
                                  _p(gscale), _p(dlogits), _stream()), "lovasz_bwd")
 
 
 def region_workspace(head, B, Cn, H, W, class_mask):
     """Bytes of the deterministic-mode slots of lmn_region_fwd, exactly (host arithmetic, no GPU)."""
-    n = int(load().lmn_region_workspace(int(head), int(B), int(Cn), int(H), int(W), C.c_uint64(int(class_mask))))
-    if n < 0:
-        raise ValueError("lm_net_amd.region_workspace: " + load().lmn_last_error().decode())
-    return n
-
-
-def region_label_kind(t):
-    """LMN_REGION_LABELS_* of a target tensor: uint8 or int64."""
-    if t.dtype == torch.uint8:
-        return REGION_LABELS_U8
-    if t.dtype == torch.int64:
-        return REGION_LABELS_I64
-    raise ValueError("lm_net_amd: a uint8 or int64 target required, got %s" % t.dtype)
+    return _host_size("region_workspace", load().lmn_region_workspace(int(head), int(B), int(Cn), int(H), int(W), C.c_uint64(int(class_mask))))
 
 
 def _region_dims(what, logits, target, head, per_image, class_mask, coef):
-    if logits.dim() != 4:
-        raise ValueError("lm_net_amd.%s: logits must be [B, C, H, W], got %s" % (what, tuple(logits.shape)))
-    B, Cn, H, W = logits.shape
-    want = (B, H, W) if head == REGION_SOFTMAX else (B, Cn, H, W)
-    if tuple(target.shape) != want or not target.is_cuda or not target.is_contiguous():
-        raise ValueError("lm_net_amd.%s: target %s, expected a contiguous device tensor %s" % (what, tuple(target.shape), want))
-    nk = bin(int(class_mask)).count("1")
+    B, Cn, H, W = _loss_dims(what, logits, target, head == REGION_SOFTMAX)
+    nk = _nk(class_mask)
     G = B if per_image else 1
     if tuple(coef.shape) != (G, nk, 3):
         raise ValueError("lm_net_amd.%s: coef %s, expected %s" % (what, tuple(coef.shape), (G, nk, 3)))
@@ -1734,7 +1701,7 @@ def region_fwd(logits, target, head, kind, denominator, per_image, alpha, beta, 
                          % (tuple(sums.shape), tuple(counts.shape), tuple(per_class.shape), G, nk, G, nk, G, nk))
     if weight is not None and weight.numel() != nk:
         raise ValueError("lm_net_amd.region_fwd: weight holds %d values for %d scored classes" % (weight.numel(), nk))
-    _check(load().lmn_region_fwd(_p(logits), C.c_void_p(target.data_ptr()), region_label_kind(target), int(head), int(kind), int(denominator),
+    _check(load().lmn_region_fwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), int(kind), int(denominator),
                                  int(bool(per_image)), _f(alpha), _f(beta), _f(smooth), _f(exponent), _f(scale), B, Cn, H, W,
                                  C.c_uint64(int(class_mask)), _raw(weight, torch.float32, "region_fwd"), _raw(workspace, torch.uint8, "region_fwd"),
                                  _i64(0 if workspace is None else workspace.numel()), _raw(sums, torch.float32, "region_fwd"),
@@ -1748,7 +1715,7 @@ def region_bwd(logits, target, head, per_image, class_mask, coef, gscale, dlogit
     B, Cn, H, W, G, nk = _region_dims("region_bwd", logits, target, head, per_image, class_mask, coef)
     if tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous():
         raise ValueError("lm_net_amd.region_bwd: dlogits needs the logits' shape")
-    _check(load().lmn_region_bwd(_p(logits), C.c_void_p(target.data_ptr()), region_label_kind(target), int(head), int(bool(per_image)), B, Cn,
+    _check(load().lmn_region_bwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), int(bool(per_image)), B, Cn,
                                  H, W, C.c_uint64(int(class_mask)), _raw(coef, torch.float32, "region_bwd"), _p(gscale), _p(dlogits), _stream()),
            "region_bwd")
 
@@ -1777,10 +1744,7 @@ def confusion_labels(pred, target, counts):
 
 def post_workspace(B, H, W):
     """Bytes of scratch lmn_post_clean needs for B samples of H x W pixels (host arithmetic, no GPU)."""
-    n = int(load().lmn_post_workspace(int(B), int(H), int(W)))
-    if n < 0:
-        raise ValueError("lm_net_amd.post_workspace: " + load().lmn_last_error().decode())
-    return n
+    return _host_size("post_workspace", load().lmn_post_workspace(int(B), int(H), int(W)))
 
 
 def cc_label(labels, connectivity, roots, areas):

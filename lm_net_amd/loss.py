@@ -243,24 +243,95 @@ class SigmoidSegLoss(torch.nn.Module):
         return _SigmoidSegLossFn.apply(logits.float().contiguous(), target.contiguous(), w_bce, pos_w, w_dice, param, self)
 
 
-# ---------------------------------------------------------------------------------------------------------------- distance maps
-# Boundary and Hausdorff losses on dense signed distance maps (include/distmap/lmnet_distmap.h).  The map is stored as the signed
-# SQUARED distance, an exact int32; a plane whose mask is empty or the whole image is all 0 and flagged.
-_DIST_MODES = {"labels": None, "softmax": hip.DISTMAP_SOFTMAX, "sigmoid": hip.DISTMAP_SIGMOID}
-_DIST_MAX_CLASSES = 64
+# ---------------------------------------------------------------------------------------------------------------- criteria front end
+# What BoundaryLoss / HausdorffDTLoss, LovaszLoss and RegionLoss (and distance_maps, lovasz_ranks, region_sums) share on the host: the
+# class count and class list, the head, the logits and target check, the scale test and the per-geometry scratch.  Each family keeps
+# what `classes=None` or a string means, its own limits and its kernels.
+_MAX_CLASSES = 64
+_HEADS = ("softmax", "sigmoid")
 
 
-def _dist_classes(what, n_classes, classes):
-    """(sorted class ids, class_mask).  None: 1 .. n_classes - 1, or class 0 when there is one class only."""
-    if int(n_classes) != n_classes or not 1 <= n_classes <= _DIST_MAX_CLASSES:
-        raise ValueError("%s: n_classes = %r outside [1, %d]" % (what, n_classes, _DIST_MAX_CLASSES))
-    if classes is None:
-        classes = list(range(1, n_classes)) if n_classes > 1 else [0]
+def _check_n_classes(what, n_classes):
+    if int(n_classes) != n_classes or not 1 <= n_classes <= _MAX_CLASSES:
+        raise ValueError("%s: n_classes = %r outside [1, %d]" % (what, n_classes, _MAX_CLASSES))
+
+
+def _check_head(what, head, n_classes):
+    if head not in _HEADS:
+        raise ValueError("%s: head = %r, expected 'softmax' or 'sigmoid'" % (what, head))
+    _check_n_classes(what, n_classes)
+    if head == "softmax" and n_classes < 2:
+        raise ValueError("%s: a softmax head needs n_classes >= 2 (one logit: head='sigmoid')" % what)
+
+
+def _parse_classes(what, n_classes, classes, none=None):
+    """(sorted class ids, class_mask) of distinct integers in [0, n_classes).  `none(n_classes)`: the ids that classes=None stands for."""
+    _check_n_classes(what, n_classes)
+    if classes is None and none is not None:
+        classes = none(int(n_classes))
     ids = [int(k) for k in classes]
     if not ids or len(set(ids)) != len(ids) or any(k != c for k, c in zip(ids, classes)) or min(ids) < 0 or max(ids) >= n_classes:
         raise ValueError("%s: classes %r must be distinct integers in [0, %d)" % (what, list(classes), n_classes))
     ids.sort()
     return ids, sum(1 << k for k in ids)
+
+
+def _check_scale(what, scale):
+    if not (scale - scale == 0.0):
+        raise ValueError("%s: scale = %r is not finite" % (what, scale))
+
+
+def _check_pair(what, n_classes, head, logits, target, float_logits, limits):
+    """-> (fp32 contiguous logits, contiguous target of the head's shape).  limits(B, C, H, W) raises the family's own limits: after the
+    logits' shape is known, before the target is looked at."""
+    if logits.dim() != 4 or logits.shape[1] != n_classes or (float_logits and not logits.is_floating_point()):
+        if float_logits:
+            raise ValueError("%s: logits must be floating point [B, %d, H, W], got %s %s" % (what, n_classes, logits.dtype, tuple(logits.shape)))
+        raise ValueError("%s: logits must be [B, %d, H, W], got %s" % (what, n_classes, tuple(logits.shape)))
+    B, Cn, H, W = logits.shape
+    limits(B, Cn, H, W)
+    if target.dtype == torch.bool:
+        target = target.to(torch.uint8)
+    if target.dtype not in (torch.uint8, torch.int64):
+        raise ValueError("%s: target must be uint8, bool or int64, got %s" % (what, target.dtype))
+    if head == "softmax":
+        if target.dim() == 4 and target.shape[1] == 1:
+            target = target[:, 0]
+        ok = tuple(target.shape) == (B, H, W)
+    else:
+        if Cn == 1 and tuple(target.shape) == (B, H, W):
+            target = target[:, None]
+        ok = tuple(target.shape) == (B, Cn, H, W)
+    if not ok:
+        raise ValueError("%s: target %s does not match logits %s under a %s head" % (what, tuple(target.shape), tuple(logits.shape), head))
+    if not logits.is_cuda or not target.is_cuda:
+        raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % what)
+    return logits.float().contiguous(), target.contiguous()
+
+
+def _check_elements(what, B, Cn, H, W):
+    if min(B, H, W) < 1 or B * Cn * H * W >= 1 << 31:
+        raise ValueError("%s: B * C * H * W = %d outside the limit [1, 2^31)" % (what, B * Cn * H * W))
+
+
+def _scratch(crit, logits, make):
+    """The scratch of the logits' geometry, made once by make() and kept in crit._scratch: a plain dict under a name that is none of
+    torch.nn.Module's registries (_parameters, _buffers, _modules), so state_dict() and .to() never see it."""
+    key = (logits.device, logits.shape[0]) + tuple(logits.shape[2:])
+    if key not in crit._scratch:
+        crit._scratch[key] = make()
+    return crit._scratch[key]
+
+
+# ---------------------------------------------------------------------------------------------------------------- distance maps
+# Boundary and Hausdorff losses on dense signed distance maps (include/distmap/lmnet_distmap.h).  The map is stored as the signed
+# SQUARED distance, an exact int32; a plane whose mask is empty or the whole image is all 0 and flagged.
+_DIST_MODES = {"labels": None, "softmax": hip.DISTMAP_SOFTMAX, "sigmoid": hip.DISTMAP_SIGMOID}
+
+
+def _dist_none(n_classes):
+    """classes=None: 1 .. n_classes - 1, or class 0 when there is one class only."""
+    return list(range(1, n_classes)) if n_classes > 1 else [0]
 
 
 def _dist_check_size(what, B, nk, H, W):
@@ -295,7 +366,7 @@ def distance_maps(labels_or_logits, n_classes, classes=None, mode="labels", thre
     what = "distance_maps"
     if mode not in _DIST_MODES:
         raise ValueError("%s: mode = %r, expected 'labels', 'softmax' or 'sigmoid'" % (what, mode))
-    ids, mask = _dist_classes(what, n_classes, classes)
+    ids, mask = _parse_classes(what, n_classes, classes, _dist_none)
     x = labels_or_logits
     if not 0.0 < float(threshold) < 1.0:
         raise ValueError("%s: threshold = %g outside (0, 1)" % (what, threshold))
@@ -344,49 +415,22 @@ class _DistLossFn(torch.autograd.Function):
 class _DistLoss(torch.nn.Module):
     """What BoundaryLoss and HausdorffDTLoss share: the classes, the head, the checks and the target's distance map."""
 
-    MAX_CLASSES = _DIST_MAX_CLASSES
+    MAX_CLASSES = _MAX_CLASSES
     TERM = None
 
     def __init__(self, n_classes, classes=None, head="softmax", scale=1.0):
         super().__init__()
         self.what = type(self).__name__
-        if head not in ("softmax", "sigmoid"):
-            raise ValueError("%s: head = %r, expected 'softmax' or 'sigmoid'" % (self.what, head))
-        self.classes, self.class_mask = _dist_classes(self.what, n_classes, classes)
-        if head == "softmax" and n_classes < 2:
-            raise ValueError("%s: a softmax head needs n_classes >= 2 (one logit: head='sigmoid')" % self.what)
+        _check_head(self.what, head, n_classes)
+        self.classes, self.class_mask = _parse_classes(self.what, n_classes, classes, _dist_none)
         self.n_classes, self.head = int(n_classes), head
         self.scale = float(scale)
         self.maps = None
 
-    def _check(self, logits, target):
-        """-> (fp32 contiguous logits, contiguous target of the head's shape)"""
-        w = self.what
-        if not (self.scale - self.scale == 0.0):
-            raise ValueError("%s: scale = %r is not finite" % (w, self.scale))
-        if logits.dim() != 4 or logits.shape[1] != self.n_classes:
-            raise ValueError("%s: logits must be [B, %d, H, W], got %s" % (w, self.n_classes, tuple(logits.shape)))
-        B, Cn, H, W = logits.shape
-        _dist_check_size(w, B, len(self.classes), H, W)
+    def _limits(self, B, Cn, H, W):
+        _dist_check_size(self.what, B, len(self.classes), H, W)
         if B * Cn * H * W >= 1 << 31:
-            raise ValueError("%s: B * C * H * W = %d beyond the limit 2^31" % (w, B * Cn * H * W))
-        if target.dtype == torch.bool:
-            target = target.to(torch.uint8)
-        if target.dtype not in (torch.uint8, torch.int64):
-            raise ValueError("%s: target must be uint8, bool or int64, got %s" % (w, target.dtype))
-        if self.head == "softmax":
-            if target.dim() == 4 and target.shape[1] == 1:
-                target = target[:, 0]
-            ok = tuple(target.shape) == (B, H, W)
-        else:
-            if Cn == 1 and tuple(target.shape) == (B, H, W):
-                target = target[:, None]
-            ok = tuple(target.shape) == (B, Cn, H, W)
-        if not ok:
-            raise ValueError("%s: target %s does not match logits %s under a %s head" % (w, tuple(target.shape), tuple(logits.shape), self.head))
-        if not logits.is_cuda or not target.is_cuda:
-            raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % w)
-        return logits.float().contiguous(), target.contiguous()
+            raise ValueError("%s: B * C * H * W = %d beyond the limit 2^31" % (self.what, B * Cn * H * W))
 
     def target_maps(self, target):
         """(sd2, flags) of the target's masks for this loss's classes and head: what ``forward(..., maps=)`` takes, so that a caller who
@@ -414,7 +458,8 @@ class _DistLoss(torch.nn.Module):
         return 2.0
 
     def forward(self, logits, target, maps=None):
-        logits, target = self._check(logits, target)
+        _check_scale(self.what, self.scale)
+        logits, target = _check_pair(self.what, self.n_classes, self.head, logits, target, False, self._limits)
         if maps is None:
             maps = self.target_maps(target)
         sd2 = maps[0]
@@ -477,52 +522,21 @@ _LOVASZ_HEADS = {"softmax": hip.LOVASZ_SOFTMAX, "sigmoid": hip.LOVASZ_SIGMOID}
 
 def _lovasz_config(what, n_classes, head, classes):
     """(sorted class ids, class_mask, present) of the constructor arguments."""
-    if head not in _LOVASZ_HEADS:
-        raise ValueError("%s: head = %r, expected 'softmax' or 'sigmoid'" % (what, head))
-    if int(n_classes) != n_classes or not 1 <= n_classes <= 64:
-        raise ValueError("%s: n_classes = %r outside [1, 64]" % (what, n_classes))
-    if head == "softmax" and n_classes < 2:
-        raise ValueError("%s: a softmax head needs n_classes >= 2 (one logit: head='sigmoid')" % what)
-    if isinstance(classes, str):
-        if classes not in ("present", "all"):
-            raise ValueError("%s: classes = %r, expected 'present', 'all' or a list of class ids" % (what, classes))
-        if head == "sigmoid" and classes == "present":
-            classes = "all"                                # Berman's hinge skips no plane
-        ids = list(range(int(n_classes)))
-    else:
-        ids = [int(k) for k in classes]
-        if not ids or len(set(ids)) != len(ids) or any(k != c for k, c in zip(ids, classes)) or min(ids) < 0 or max(ids) >= n_classes:
-            raise ValueError("%s: classes %r must be distinct integers in [0, %d)" % (what, list(classes), n_classes))
-        ids.sort()
-    return ids, sum(1 << k for k in ids), classes == "present"
+    _check_head(what, head, n_classes)
+    if not isinstance(classes, str):
+        return _parse_classes(what, n_classes, classes) + (False,)
+    if classes not in ("present", "all"):
+        raise ValueError("%s: classes = %r, expected 'present', 'all' or a list of class ids" % (what, classes))
+    present = classes == "present" and head == "softmax"          # Berman's hinge skips no plane
+    return _parse_classes(what, n_classes, None, range) + (present,)
 
 
 def _lovasz_check(what, n_classes, head, nk, per_image, logits, target):
-    """-> (fp32 contiguous logits, contiguous target of the head's shape)"""
-    if logits.dim() != 4 or logits.shape[1] != n_classes or not logits.is_floating_point():
-        raise ValueError("%s: logits must be floating point [B, %d, H, W], got %s %s" % (what, n_classes, logits.dtype, tuple(logits.shape)))
-    B, Cn, H, W = logits.shape
-    if min(B, H, W) < 1 or B * Cn * H * W >= 1 << 31:
-        raise ValueError("%s: B * C * H * W = %d outside the limit [1, 2^31)" % (what, B * Cn * H * W))
-    if per_image and B * nk > hip.LOVASZ_MAX_SEGMENTS:
-        raise ValueError("%s: per_image: B * classes = %d segments above the limit %d" % (what, B * nk, hip.LOVASZ_MAX_SEGMENTS))
-    if target.dtype == torch.bool:
-        target = target.to(torch.uint8)
-    if target.dtype not in (torch.uint8, torch.int64):
-        raise ValueError("%s: target must be uint8, bool or int64, got %s" % (what, target.dtype))
-    if head == "softmax":
-        if target.dim() == 4 and target.shape[1] == 1:
-            target = target[:, 0]
-        ok = tuple(target.shape) == (B, H, W)
-    else:
-        if Cn == 1 and tuple(target.shape) == (B, H, W):
-            target = target[:, None]
-        ok = tuple(target.shape) == (B, Cn, H, W)
-    if not ok:
-        raise ValueError("%s: target %s does not match logits %s under a %s head" % (what, tuple(target.shape), tuple(logits.shape), head))
-    if not logits.is_cuda or not target.is_cuda:
-        raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % what)
-    return logits.float().contiguous(), target.contiguous()
+    def limits(B, Cn, H, W):
+        _check_elements(what, B, Cn, H, W)
+        if per_image and B * nk > hip.LOVASZ_MAX_SEGMENTS:
+            raise ValueError("%s: per_image: B * classes = %d segments above the limit %d" % (what, B * nk, hip.LOVASZ_MAX_SEGMENTS))
+    return _check_pair(what, n_classes, head, logits, target, True, limits)
 
 
 def _lovasz_buffers(device, B, nk, H, W, per_image):
@@ -582,18 +596,14 @@ class LovaszLoss(torch.nn.Module):
         self.n_classes, self.head, self.per_image = int(n_classes), head, bool(per_image)
         self.scale = float(scale)
         self.ranks = None
-        self._buffers = {}
+        self._scratch = {}
 
     def forward(self, logits, target):
-        if not (self.scale - self.scale == 0.0):
-            raise ValueError("LovaszLoss: scale = %r is not finite" % self.scale)
+        _check_scale("LovaszLoss", self.scale)
         nk = len(self.classes)
         logits, target = _lovasz_check("LovaszLoss", self.n_classes, self.head, nk, self.per_image, logits, target)
         B, _, H, W = logits.shape
-        key = (logits.device, B, H, W)
-        if key not in self._buffers:
-            self._buffers[key] = _lovasz_buffers(logits.device, B, nk, H, W, self.per_image)
-        buf = self._buffers[key]
+        buf = _scratch(self, logits, lambda: _lovasz_buffers(logits.device, B, nk, H, W, self.per_image))
         self.ranks = buf[1:]
         cfg = (_LOVASZ_HEADS[self.head], self.per_image, self.present, self.class_mask, self.scale, buf)
         return _LovaszFn.apply(logits, target, cfg)
@@ -626,50 +636,18 @@ _REGION_DENOMINATORS = {"linear": hip.REGION_LINEAR, "squared": hip.REGION_SQUAR
 
 def _region_config(what, n_classes, head, classes):
     """(sorted class ids, class_mask) of the constructor arguments."""
-    if head not in _REGION_HEADS:
-        raise ValueError("%s: head = %r, expected 'softmax' or 'sigmoid'" % (what, head))
-    if int(n_classes) != n_classes or not 1 <= n_classes <= 64:
-        raise ValueError("%s: n_classes = %r outside [1, 64]" % (what, n_classes))
-    if head == "softmax" and n_classes < 2:
-        raise ValueError("%s: a softmax head needs n_classes >= 2 (one logit: head='sigmoid')" % what)
-    if classes is None:
-        ids = list(range(int(n_classes)))
-    else:
-        if isinstance(classes, str):
-            raise ValueError("%s: classes = %r, expected None or a list of class ids" % (what, classes))
-        ids = [int(k) for k in classes]
-        if not ids or len(set(ids)) != len(ids) or any(k != c for k, c in zip(ids, classes)) or min(ids) < 0 or max(ids) >= n_classes:
-            raise ValueError("%s: classes %r must be distinct integers in [0, %d)" % (what, list(classes), n_classes))
-        ids.sort()
-    return ids, sum(1 << k for k in ids)
+    _check_head(what, head, n_classes)
+    if isinstance(classes, str):
+        raise ValueError("%s: classes = %r, expected None or a list of class ids" % (what, classes))
+    return _parse_classes(what, n_classes, classes, range)
 
 
 def _region_check(what, n_classes, head, logits, target):
-    """-> (fp32 contiguous logits, contiguous target of the head's shape)"""
-    if logits.dim() != 4 or logits.shape[1] != n_classes or not logits.is_floating_point():
-        raise ValueError("%s: logits must be floating point [B, %d, H, W], got %s %s" % (what, n_classes, logits.dtype, tuple(logits.shape)))
-    B, Cn, H, W = logits.shape
-    if min(B, H, W) < 1 or B * Cn * H * W >= 1 << 31:
-        raise ValueError("%s: B * C * H * W = %d outside the limit [1, 2^31)" % (what, B * Cn * H * W))
-    if B > hip.REGION_MAX_BATCH:
-        raise ValueError("%s: B = %d above the limit %d" % (what, B, hip.REGION_MAX_BATCH))
-    if target.dtype == torch.bool:
-        target = target.to(torch.uint8)
-    if target.dtype not in (torch.uint8, torch.int64):
-        raise ValueError("%s: target must be uint8, bool or int64, got %s" % (what, target.dtype))
-    if head == "softmax":
-        if target.dim() == 4 and target.shape[1] == 1:
-            target = target[:, 0]
-        ok = tuple(target.shape) == (B, H, W)
-    else:
-        if Cn == 1 and tuple(target.shape) == (B, H, W):
-            target = target[:, None]
-        ok = tuple(target.shape) == (B, Cn, H, W)
-    if not ok:
-        raise ValueError("%s: target %s does not match logits %s under a %s head" % (what, tuple(target.shape), tuple(logits.shape), head))
-    if not logits.is_cuda or not target.is_cuda:
-        raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % what)
-    return logits.float().contiguous(), target.contiguous()
+    def limits(B, Cn, H, W):
+        _check_elements(what, B, Cn, H, W)
+        if B > hip.REGION_MAX_BATCH:
+            raise ValueError("%s: B = %d above the limit %d" % (what, B, hip.REGION_MAX_BATCH))
+    return _check_pair(what, n_classes, head, logits, target, True, limits)
 
 
 def _region_buffers(device, head, B, Cn, H, W, class_mask, nk, per_image):
@@ -762,17 +740,14 @@ class RegionLoss(torch.nn.Module):
         self.smooth, self.alpha, self.beta, self.exponent = float(smooth), float(alpha), float(beta), float(exponent)
         self.scale = float(scale)
         self.per_class = self.sums = self.counts = None
-        self._scratch = {}            # (not _buffers: that is torch.nn.Module's own registry)
+        self._scratch = {}
 
     def forward(self, logits, target):
-        if not (self.scale - self.scale == 0.0):
-            raise ValueError("RegionLoss: scale = %r is not finite" % self.scale)
+        _check_scale("RegionLoss", self.scale)
         logits, target = _region_check("RegionLoss", self.n_classes, self.head, logits, target)
         B, Cn, H, W = logits.shape
-        key = (logits.device, B, H, W)
-        if key not in self._scratch:
-            self._scratch[key] = _region_buffers(logits.device, self.head, B, Cn, H, W, self.class_mask, len(self.classes), self.per_image)
-        buf = self._scratch[key]
+        buf = _scratch(self, logits, lambda: _region_buffers(logits.device, self.head, B, Cn, H, W, self.class_mask, len(self.classes),
+                                                             self.per_image))
         if self.weight is not None and self.weight.device != logits.device:
             self.weight = self.weight.to(logits.device)
         self.sums, self.counts, self.per_class = buf[1:]

@@ -108,3 +108,28 @@ def test_no_host_synchronisation_between_forward_and_backward(C):
             torch.cuda.set_sync_debug_mode("default")
     torch.cuda.synchronize()
     assert bool(torch.isfinite(z.grad).all()) and float(z.grad.abs().max()) > 0
+
+
+def test_the_last_maps_are_not_registered_buffers():
+    """After a step the module that holds the criteria still has an empty state_dict and still moves: the maps the criteria keep are
+    plain attributes outside torch.nn.Module's registries.  A second forward gives the same bits (deterministic mode)."""
+    from lm_net_amd import BoundaryLoss, HausdorffDTLoss, hip
+    g = torch.Generator().manual_seed(3)
+    y = torch.randint(0, 3, (2, 5, 7), generator=g).to(DEV)
+    was = hip.get_deterministic()
+    hip.set_deterministic(True)
+    try:
+        for cls in (BoundaryLoss, HausdorffDTLoss):
+            z = torch.randn(2, 3, 5, 7, generator=g).to(DEV).requires_grad_(True)
+            crit = cls(3)
+            first = crit(z, y)
+            first.backward()
+            holder = torch.nn.ModuleList([crit])
+            assert list(holder.state_dict()) == [] and list(crit.state_dict()) == []
+            assert holder.to(DEV) is holder
+            second = crit(z.detach(), y)
+            torch.cuda.synchronize()
+            assert bool(torch.isfinite(z.grad).all()) and float(z.grad.abs().max()) > 0
+            assert first.detach().view(torch.int32).item() == second.view(torch.int32).item()
+    finally:
+        hip.set_deterministic(was)

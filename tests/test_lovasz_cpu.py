@@ -168,29 +168,11 @@ def test_workspace_is_host_arithmetic():
 
 
 def test_python_refuses_what_it_cannot_run():
-    from lm_net_amd import LovaszLoss, lovasz_ranks
-    y = torch.zeros(2, 8, 9, dtype=torch.int64)
-    z = torch.zeros(2, 3, 8, 9)
-    for kw, msg in ((dict(n_classes=0), "n_classes"), (dict(n_classes=65), "n_classes"), (dict(n_classes=3, head="tanh"), "head"),
-                    (dict(n_classes=1), "head='sigmoid'"), (dict(n_classes=3, classes=[0, 0]), "distinct"), (dict(n_classes=3, classes=[5]), "distinct"),
-                    (dict(n_classes=3, classes=[]), "distinct"), (dict(n_classes=3, classes=[1.5]), "distinct"),
-                    (dict(n_classes=3, classes="some"), "'present', 'all'")):
-        with pytest.raises(ValueError, match=msg):
-            LovaszLoss(**kw)
-    crit = LovaszLoss(3)
-    for args, msg in (((z[:, :2], y), "logits must be"), ((z, y[:, :4]), "does not match"), ((z, y.float()), "uint8, bool or int64"),
-                      ((z[0], y), "logits must be"), ((z, torch.zeros(2, 3, 8, 9, dtype=torch.int64)), "does not match")):
-        with pytest.raises(ValueError, match=msg):
-            crit(*args)
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        crit(z, y)
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        lovasz_ranks(z, y, 3)
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        LovaszLoss(1, head="sigmoid")(z[:, :1], y.to(torch.uint8))
-    crit.scale = float("inf")
-    with pytest.raises(ValueError, match="not finite"):
-        crit(z, y)
+    """The family's own rules; what it shares with the other criteria (class count, class list, head, logits, target, scale, "no CPU
+    fallback") is in tests/test_criteria_cpu.py."""
+    from lm_net_amd import LovaszLoss
+    with pytest.raises(ValueError, match="'present', 'all'"):
+        LovaszLoss(n_classes=3, classes="some")
     with pytest.raises(ValueError, match="segments above the limit"):
         LovaszLoss(3, per_image=True)(torch.zeros(30000, 3, 1, 1), torch.zeros(30000, 1, 1, dtype=torch.uint8))
     assert (LovaszLoss(4, classes=[3, 1]).classes, LovaszLoss(4, classes=[3, 1]).class_mask, LovaszLoss(4, classes=[3, 1]).present) == ([1, 3], 0b1010, False)

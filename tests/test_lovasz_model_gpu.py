@@ -57,3 +57,22 @@ def test_training_step_with_lovasz(C):
     seg(z2, y).backward()
     both = (z2.grad + z.grad - logits.grad).abs().max()
     assert float(both) <= 1e-5 * float(logits.grad.abs().max())
+
+
+def test_scratch_is_not_a_registered_buffer():
+    """After a step the module that holds the criterion still has a state_dict and still moves: the scratch of the geometry is kept
+    outside torch.nn.Module's registries, and it is reused: a second forward gives the same bits."""
+    from lm_net_amd import LovaszLoss
+    g = torch.Generator().manual_seed(3)
+    z = torch.randn(2, 3, 5, 7, generator=g).to(DEV).requires_grad_(True)
+    y = torch.randint(0, 3, (2, 5, 7), generator=g).to(DEV)
+    crit = LovaszLoss(3)
+    first = crit(z, y)
+    first.backward()
+    holder = torch.nn.ModuleList([crit])
+    assert list(holder.state_dict()) == [] and list(crit.state_dict()) == []
+    assert holder.to(DEV) is holder
+    second = crit(z.detach(), y)
+    torch.cuda.synchronize()
+    assert float(first.detach()) > 0 and bool(torch.isfinite(z.grad).all()) and float(z.grad.abs().max()) > 0
+    assert first.detach().view(torch.int32).item() == second.view(torch.int32).item()

@@ -169,13 +169,10 @@ def test_workspace_is_host_arithmetic():
 
 
 def test_python_refuses_what_it_cannot_run():
-    from lm_net_amd import RegionLoss, region_sums
-    y = torch.zeros(2, 8, 9, dtype=torch.int64)
-    z = torch.zeros(2, 3, 8, 9)
-    for kw, msg in ((dict(n_classes=0), "n_classes"), (dict(n_classes=65), "n_classes"), (dict(n_classes=3, head="tanh"), "head"),
-                    (dict(n_classes=1), "head='sigmoid'"), (dict(n_classes=3, classes=[0, 0]), "distinct"), (dict(n_classes=3, classes=[5]), "distinct"),
-                    (dict(n_classes=3, classes=[]), "distinct"), (dict(n_classes=3, classes=[1.5]), "distinct"),
-                    (dict(n_classes=3, classes="present"), "None or a list"), (dict(n_classes=3, kind="lovasz"), "kind"),
+    """The family's own rules; what it shares with the other criteria (class count, class list, head, logits, target, scale, "no CPU
+    fallback") is in tests/test_criteria_cpu.py."""
+    from lm_net_amd import RegionLoss
+    for kw, msg in ((dict(n_classes=3, classes="present"), "None or a list"), (dict(n_classes=3, kind="lovasz"), "kind"),
                     (dict(n_classes=3, denominator="cubed"), "denominator"), (dict(n_classes=3, kind="tversky", denominator="squared"), "dice and jaccard only"),
                     (dict(n_classes=3, kind="generalized_dice", denominator="squared"), "dice and jaccard only"),
                     (dict(n_classes=3, kind="generalized_dice", weight=[1, 1, 1]), "no class weight"), (dict(n_classes=3, weight=[1, 2]), "one per scored class"),
@@ -184,22 +181,8 @@ def test_python_refuses_what_it_cannot_run():
                     (dict(n_classes=3, exponent=9), "exponent")):
         with pytest.raises(ValueError, match=msg):
             RegionLoss(**kw)
-    crit = RegionLoss(3)
-    for args, msg in (((z[:, :2], y), "logits must be"), ((z, y[:, :4]), "does not match"), ((z, y.float()), "uint8, bool or int64"),
-                      ((z[0], y), "logits must be"), ((z, torch.zeros(2, 3, 8, 9, dtype=torch.int64)), "does not match")):
-        with pytest.raises(ValueError, match=msg):
-            crit(*args)
     with pytest.raises(ValueError, match="above the limit 65535"):
-        crit(torch.zeros(65536, 3, 1, 1), torch.zeros(65536, 1, 1, dtype=torch.uint8))
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        crit(z, y)
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        region_sums(z, y, 3)
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        RegionLoss(1, head="sigmoid")(z[:, :1], y.to(torch.uint8))
-    crit.scale = float("inf")
-    with pytest.raises(ValueError, match="not finite"):
-        crit(z, y)
+        RegionLoss(3)(torch.zeros(65536, 3, 1, 1), torch.zeros(65536, 1, 1, dtype=torch.uint8))
     assert (RegionLoss(4, classes=[3, 1]).classes, RegionLoss(4, classes=[3, 1]).class_mask) == ([1, 3], 0b1010)
     assert RegionLoss(4).denominator == "squared" and RegionLoss(4, "jaccard").denominator == "squared"
     assert RegionLoss(4, "tversky").denominator == "linear" and RegionLoss(4, "generalized_dice").denominator == "linear"

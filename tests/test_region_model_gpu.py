@@ -109,3 +109,23 @@ def test_sigmoid_head_step_and_a_rising_scale(deterministic):
     full.backward()
     assert float(full.detach()) == 2.0 * float(half.detach())         # (a power of two: exact)
     assert np.array_equal(z.grad.cpu().numpy().astype(np.float64), 2.0 * d)
+
+
+def test_scratch_is_not_a_registered_buffer(deterministic):
+    """After a step the module that holds the criterion has exactly its registered buffer, the class weight, in its state_dict and still
+    moves: the scratch of the geometry is kept outside torch.nn.Module's registries, and it is reused: a second forward gives the same
+    bits."""
+    from lm_net_amd import RegionLoss
+    g = torch.Generator().manual_seed(3)
+    z = torch.randn(2, 3, 5, 7, generator=g).to(DEV).requires_grad_(True)
+    y = torch.randint(0, 3, (2, 5, 7), generator=g).to(DEV)
+    crit = RegionLoss(3, weight=[1.0, 2.0, 3.0])
+    first = crit(z, y)
+    first.backward()
+    holder = torch.nn.ModuleList([crit])
+    assert list(holder.state_dict()) == ["0.weight"] and list(crit.state_dict()) == ["weight"]
+    assert holder.to(DEV) is holder
+    second = crit(z.detach(), y)
+    torch.cuda.synchronize()
+    assert float(first.detach()) > 0 and bool(torch.isfinite(z.grad).all()) and float(z.grad.abs().max()) > 0
+    assert first.detach().view(torch.int32).item() == second.view(torch.int32).item()
