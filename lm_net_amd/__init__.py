@@ -22,10 +22,12 @@ and target in a device hash table),
 ``lm_net_amd.post.DevicePostprocess`` (on-device arg-max, connected-component cleaning, resize back to the frame, overlay),
 ``lm_net_amd.post.VolumePostprocess`` (3D connected-component cleaning of a whole case: the n largest components of an organ, a minimal
 volume, cavity filling, between the prediction and ``VolumeSurfaceMeter``),
+``lm_net_amd.data.VolumeSlicer`` (the input side of a CT / MR case: int16 volumes to windowed, z-scored 2.5D fp32 batches on the device),
 ``lm_net_amd.infer.TiledPredictor`` (frames of any size: overlapping tiles, mirrored copies and one blend launch),
 ``lm_net_amd.ddp.DistributedLMNet`` (bucketed RCCL gradient all-reduce).
 """
 from .LM_Net import LM_Net  # noqa: F401
+from .data import VolumeSlicer  # noqa: F401
 from .loss import (BoundaryLoss, FocalLoss, HausdorffDTLoss, LovaszLoss, RegionLoss, SegLoss, SigmoidSegLoss, distance_maps,  # noqa: F401
                    lovasz_ranks, region_sums)
 from .metrics import CurveMeter, ImageStatsMeter, LesionMeter, SigmoidStatsMeter, VolumeSurfaceMeter  # noqa: F401
@@ -33,4 +35,4 @@ from .post import VolumePostprocess  # noqa: F401
 
 __all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter", "VolumeSurfaceMeter", "VolumePostprocess",
            "LesionMeter", "BoundaryLoss", "HausdorffDTLoss", "distance_maps", "LovaszLoss", "lovasz_ranks", "RegionLoss",
-           "region_sums"]
+           "region_sums", "VolumeSlicer"]

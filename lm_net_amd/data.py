@@ -562,3 +562,297 @@ class DeviceAugment:
         hip.augment_oneof_u8(images.contiguous() if images is not None else None, masks.contiguous() if masks is not None else None,
                              params, hw.astype(np.int32) if hw is not None else None, pdev, scratch, gray, x, y, self.mean, self.std,
                              C, self.MASK_MODES[self.mask_mode], arr, odev, tables, tdev, lab, scratch2, ytmp, ws)
+
+
+# ---------------------------------------------------------------- the input side of a 3D case (include/slices/lmnet_slices.h)
+_SLICES_KINDS = {"window": hip.SLICES_WINDOW, "zscore": hip.SLICES_ZSCORE, "percentile": hip.SLICES_PERCENTILE}
+_SLICES_EDGES = {"replicate": hip.SLICES_EDGE_REPLICATE, "zero": hip.SLICES_EDGE_ZERO}
+_SLICES_BORDERS = {"replicate": hip.SLICES_BORDER_REPLICATE, "constant": hip.SLICES_BORDER_CONSTANT}
+
+
+def _norm_spec(spec):
+    """one norm spec -> (kind, level, width); raises ValueError"""
+    if isinstance(spec, str):
+        spec = (spec,)
+    if not isinstance(spec, tuple) or not spec or spec[0] not in _SLICES_KINDS:
+        raise ValueError("VolumeSlicer: norm spec %r is none of 'zscore', ('percentile',), ('window', level, width)" % (spec,))
+    if spec[0] == "window":
+        if len(spec) != 3 or not all(math.isfinite(float(v)) for v in spec[1:]) or abs(float(spec[1])) > 1e9 or not 0 < float(spec[2]) <= 1e9:
+            raise ValueError("VolumeSlicer: norm spec %r: ('window', level, width) with |level| <= 1e9 and 0 < width <= 1e9" % (spec,))
+        return hip.SLICES_WINDOW, float(spec[1]), float(spec[2])
+    if len(spec) != 1:
+        raise ValueError("VolumeSlicer: norm spec %r takes no values" % (spec,))
+    return _SLICES_KINDS[spec[0]], 0.0, 1.0
+
+
+def _per_modality(what, v, M):
+    v = list(v) if isinstance(v, (list, tuple)) else [v] * M
+    if len(v) != M:
+        raise ValueError("VolumeSlicer: %s needs one value or %d, one per modality" % (what, M))
+    return v
+
+
+def resize_map(dst_hw, src_hw):
+    """The inverse map of a plain resize as a 3x3 matrix in double: output pixel index -> source pixel index, s = (x + 0.5) * src /
+    dst - 0.5 per axis (align_corners=False)."""
+    (h, w), (Hs, Ws) = dst_hw, src_hw
+    ax, ay = Ws / float(w), Hs / float(h)
+    return np.array([[ax, 0.0, 0.5 * ax - 0.5], [0.0, ay, 0.5 * ay - 0.5], [0.0, 0.0, 1.0]], dtype=np.float64)
+
+
+def slice_param_row(dst_hw, src_hw, M=None, flips=0, gain=1.0, bias=0.0):
+    """The fp32 row of 8 of one sample of lmn_slices_gather: the inverse map from output pixel index to source pixel index composed in
+    double -- undo the flips, then `invert_affine(M)` (M: a forward 2x3 matrix on the output grid, the convention of `ssr_matrix`;
+    None: no warp), then the plain resize -- followed by gain and bias."""
+    h, w = dst_hw
+    T = np.eye(3)
+    if flips & 1:
+        T = np.array([[-1.0, 0.0, w - 1.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]) @ T
+    if flips & 2:
+        T = np.array([[1.0, 0.0, 0.0], [0.0, -1.0, h - 1.0], [0.0, 0.0, 1.0]]) @ T
+    if M is not None:
+        iM = invert_affine([float(v) for v in np.asarray(M, dtype=np.float64).reshape(-1)])
+        T = np.array([iM[:3], iM[3:], [0.0, 0.0, 1.0]]) @ T
+    T = resize_map(dst_hw, src_hw) @ T
+    return np.array([T[0, 0], T[0, 1], T[0, 2], T[1, 0], T[1, 1], T[1, 2], gain, bias], dtype=np.float64).astype(np.float32)
+
+
+class VolumeSlicer:
+    """The first stage of a CT / MR case: an int16 (or uint8) volume already in HBM -> the fp32 2.5D batches `LM_Net.forward` and
+    `TiledPredictor` read, with windowing, z-scoring, percentile clipping, slice stacking and resizing on the device
+    (`lmn_slices_stats`, `lmn_slices_gather`; include/slices/lmnet_slices.h).  2 bytes per voxel cross PCIe, once.
+
+      open_case(volume, labels=None)   volume int16 / uint8 [D, Hs, Ws] or [M, D, Hs, Ws], labels uint8 [D, Hs, Ws]; launches the
+                                       statistics and returns without synchronising.  `stats` (device int64 [M, 8]: n, sum v,
+                                       sum v^2, min, max, v_lo, v_hi, 0 of the foreground) and `table` (device fp32 [S, 4]: lo, hi,
+                                       a, b per norm spec) belong to the open case.
+      slices(z0, z1)                   (x fp32 [n, C, h, w], y [n, h, w] or None) of the consecutive slices z0 .. z1 - 1: validation.
+      batch(z, params=None)            the same for any list (or device int32 tensor) of slice indices, repeats allowed, under the
+                                       per-sample parameters `sample(n, rng)` draws: training.
+      restore(labels_net)              uint8 [n, h, w] -> [n, Hs, Ws] by the same gather in label-only mode, for
+                                       `VolumePostprocess.push` / `VolumeSurfaceMeter.push` at native resolution.
+
+    norm: "zscore", ("window", level, width), ("percentile",), or a list with one entry per modality, each a spec or a list of specs.
+    o = (min(max(v, lo), hi) - a) * b with (lo, hi, a, b) = window: (level - width / 2, level + width / 2, lo, 1 / width); zscore:
+    (v_lo, v_hi, mean, 1 / max(std, 1e-8)), mean and population std of the unclipped foreground; percentile: (v_lo, v_hi, v_lo,
+    1 / (v_hi - v_lo)).  v_lo / v_hi are the `clip` = (q_lo, q_hi) percent order statistics of the foreground (rank q (n - 1) rounded
+    down; None: min and max); foreground: None = every voxel, or v > foreground (one value or one per modality).
+    C = sum over modalities of (its specs) x (2 context + 1), in the order modality, spec, dz = -context .. context; channel dz of
+    slice z reads slice z + dz * stride, clamped to the volume under edge="replicate", a plane of 0 (before gain and bias) under
+    edge="zero".  The image is resized bilinearly (align_corners=False), the label by the nearest pixel under the half-pixel rule
+    (torch's nearest-exact), both under one matrix; border="replicate" clamps taps to the frame, "constant" gives border_value (raw
+    units, one or one per modality) and label_border outside it.
+
+    sample(n, rng) draws per sample a ShiftScaleRotate matrix (`ssr_matrix` on the output grid, probability p_ssr), the two flips and
+    an intensity gain 1 + U[-gain_limit, gain_limit] and bias U[-bias_limit, bias_limit]; rng: None, an int seed or a numpy
+    Generator.  Nothing synchronises.  The returned tensors are the slicer's own, kept per geometry: a later call of the same
+    geometry overwrites them, and after the first call of a geometry nothing is allocated on the device."""
+
+    _SLOTS = 8
+
+    def __init__(self, size=(352, 352), norm="zscore", modalities=1, context=1, stride=1, edge="replicate", foreground=None, clip=None,
+                 border="replicate", border_value=0, label_border=0, label_dtype=torch.uint8, shift_limit=0.1, scale_limit=0.1,
+                 rotate_limit=30, p_ssr=0.5, p_hflip=0.5, p_vflip=0.5, gain_limit=0.1, bias_limit=0.1):
+        M = int(modalities)
+        if not 1 <= M <= hip.SLICES_MAX_MODALITIES:
+            raise ValueError("VolumeSlicer: modalities = %r outside the limit [1, %d]" % (modalities, hip.SLICES_MAX_MODALITIES))
+        if len(size) != 2 or not all(1 <= int(v) <= hip.SLICES_MAX_OUT for v in size):
+            raise ValueError("VolumeSlicer: size %r outside the limit [1, %d]" % (tuple(size), hip.SLICES_MAX_OUT))
+        if not 0 <= int(context) <= hip.SLICES_MAX_CONTEXT or not 1 <= int(stride) <= hip.SLICES_MAX_DEPTH:
+            raise ValueError("VolumeSlicer: context = %r outside [0, %d] or stride = %r outside [1, %d]"
+                             % (context, hip.SLICES_MAX_CONTEXT, stride, hip.SLICES_MAX_DEPTH))
+        if edge not in _SLICES_EDGES or border not in _SLICES_BORDERS:
+            raise ValueError("VolumeSlicer: edge = %r must be 'replicate' or 'zero', border = %r 'replicate' or 'constant'" % (edge, border))
+        if label_dtype not in (torch.uint8, torch.int64):
+            raise ValueError("VolumeSlicer: label_dtype %r is neither torch.uint8 nor torch.int64" % (label_dtype,))
+        if not 0 <= int(label_border) <= 255:
+            raise ValueError("VolumeSlicer: label_border = %r outside [0, 255]" % (label_border,))
+        per_mod = norm if isinstance(norm, list) else [norm] * M
+        if len(per_mod) != M:
+            raise ValueError("VolumeSlicer: norm lists %d modalities, modalities = %d" % (len(per_mod), M))
+        self.specs = []                                       # (modality, kind, level, width), modality-major
+        for m, entry in enumerate(per_mod):
+            for spec in (entry if isinstance(entry, list) else [entry]):
+                self.specs.append((m,) + _norm_spec(spec))
+        self.context, self.stride = int(context), int(stride)
+        self.channels = len(self.specs) * (2 * self.context + 1)
+        if not 1 <= self.channels <= hip.SLICES_MAX_CHANNELS:
+            raise ValueError("VolumeSlicer: %d norm specs x %d slices = %d channels, outside the limit [1, %d]"
+                             % (len(self.specs), 2 * self.context + 1, self.channels, hip.SLICES_MAX_CHANNELS))
+        fg = _per_modality("foreground", foreground, M)
+        self.foreground = [hip.SLICES_NO_FOREGROUND if v is None else int(v) for v in fg]
+        if not all(hip.SLICES_NO_FOREGROUND <= v <= 32767 for v in self.foreground):
+            raise ValueError("VolumeSlicer: foreground %r outside int16" % (foreground,))
+        if clip is None:
+            self.q_ppm = (0, 1000000)
+        else:
+            if len(clip) != 2 or not 0.0 <= float(clip[0]) <= float(clip[1]) <= 100.0:
+                raise ValueError("VolumeSlicer: clip = %r: two percentages, 0 <= q_lo <= q_hi <= 100" % (clip,))
+            self.q_ppm = (int(round(float(clip[0]) * 1e4)), int(round(float(clip[1]) * 1e4)))
+        self.border_value = [float(v) for v in _per_modality("border_value", border_value, M)]
+        if not all(abs(v) <= 65536.0 for v in self.border_value):
+            raise ValueError("VolumeSlicer: border_value %r outside [-65536, 65536]" % (border_value,))
+        for name, v in (("p_ssr", p_ssr), ("p_hflip", p_hflip), ("p_vflip", p_vflip)):
+            if not 0.0 <= v <= 1.0:
+                raise ValueError("VolumeSlicer: %s = %r outside [0, 1]" % (name, v))
+        if not (0 <= shift_limit and 0 <= scale_limit < 1 and 0 <= rotate_limit and 0 <= gain_limit < 1 and 0 <= bias_limit):
+            raise ValueError("VolumeSlicer: shift_limit, scale_limit (< 1), rotate_limit, gain_limit (< 1) and bias_limit must be non-negative")
+        self.size, self.modalities = (int(size[0]), int(size[1])), M
+        self.edge, self.border, self.label_border, self.label_dtype = edge, border, int(label_border), label_dtype
+        self.shift_limit, self.scale_limit, self.rotate_limit = float(shift_limit), float(scale_limit), float(rotate_limit)
+        self.p_ssr, self.p_hflip, self.p_vflip = float(p_ssr), float(p_hflip), float(p_vflip)
+        self.gain_limit, self.bias_limit = float(gain_limit), float(bias_limit)
+        self.volume = self.labels = self.stats = self.table = None
+        self._scratch = {}             # geometry -> device tensors, made once (a plain dict, as the criteria keep theirs)
+        self._stage = {}               # rows -> (pinned staging slots, their events, next slot)
+
+    # ------------------------------------------------------------------ parameters
+    def sample(self, n, rng=None):
+        """n per-sample dicts: "M" (forward 2x3 matrix on the output grid, `ssr_matrix`, or None), "flips" (bit 0 horizontal, bit 1
+        vertical), "gain", "bias"."""
+        rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+        h, w = self.size
+        out = []
+        for _ in range(int(n)):
+            ssr = rng.random() < self.p_ssr
+            angle = rng.uniform(-self.rotate_limit, self.rotate_limit)
+            scale = rng.uniform(1.0 - self.scale_limit, 1.0 + self.scale_limit)
+            dx = rng.uniform(-self.shift_limit, self.shift_limit)
+            dy = rng.uniform(-self.shift_limit, self.shift_limit)
+            flips = int(rng.random() < self.p_hflip) | (int(rng.random() < self.p_vflip) << 1)
+            out.append({"M": ssr_matrix(h, w, angle, scale, dx, dy) if ssr else None, "flips": flips,
+                        "gain": 1.0 + rng.uniform(-self.gain_limit, self.gain_limit), "bias": rng.uniform(-self.bias_limit, self.bias_limit)})
+        return out
+
+    def rows(self, n, params=None, dst_hw=None, src_hw=None):
+        """float32 [n, 8]: the parameter rows of n samples (params None: the plain resize, gain 1, bias 0)."""
+        dst_hw = self.size if dst_hw is None else dst_hw
+        src_hw = self._src_hw() if src_hw is None else src_hw
+        if params is None:
+            return np.tile(slice_param_row(dst_hw, src_hw), (n, 1))
+        if len(params) != n:
+            raise ValueError("VolumeSlicer: %d parameter sets for %d slices" % (len(params), n))
+        rows = np.empty((n, 8), dtype=np.float32)
+        for i, p in enumerate(params):
+            fl = int(p.get("flips", 0))
+            M = p.get("M")
+            vals = [float(p.get("gain", 1.0)), float(p.get("bias", 0.0))] + ([] if M is None else [float(v) for v in np.asarray(M).reshape(-1)])
+            if fl not in (0, 1, 2, 3) or not all(math.isfinite(v) for v in vals) or (M is not None and len(vals) != 8):
+                raise ValueError("VolumeSlicer: sample %d: flips 0..3, a finite gain and bias, M six finite values or None" % i)
+            rows[i] = slice_param_row(dst_hw, src_hw, M, fl, vals[0], vals[1])
+        return rows
+
+    # ------------------------------------------------------------------ the case
+    def _src_hw(self):
+        if self.volume is None:
+            raise ValueError("VolumeSlicer: no case is open")
+        return int(self.volume.shape[2]), int(self.volume.shape[3])
+
+    def _cached(self, key, make):
+        if key not in self._scratch:
+            self._scratch[key] = make()
+        return self._scratch[key]
+
+    def open_case(self, volume, labels=None):
+        M = self.modalities
+        if volume.dim() == 3:
+            volume = volume.unsqueeze(0)
+        if volume.dim() != 4 or volume.dtype not in (torch.int16, torch.uint8):
+            raise ValueError("VolumeSlicer.open_case: an int16 or uint8 volume [D, Hs, Ws] or [M, D, Hs, Ws] required, got %s %s"
+                             % (volume.dtype, tuple(volume.shape)))
+        Mv, D, Hs, Ws = (int(d) for d in volume.shape)
+        if Mv != M:
+            raise ValueError("VolumeSlicer.open_case: %d modalities in the volume, modalities = %d (limit [1, %d])" % (Mv, M, hip.SLICES_MAX_MODALITIES))
+        if not 1 <= D <= hip.SLICES_MAX_DEPTH:
+            raise ValueError("VolumeSlicer.open_case: D = %d outside the limit [1, %d]" % (D, hip.SLICES_MAX_DEPTH))
+        if not (2 <= Hs <= hip.SLICES_MAX_SIDE and 2 <= Ws <= hip.SLICES_MAX_SIDE):
+            raise ValueError("VolumeSlicer.open_case: slices of %d x %d outside the limit [2, %d]" % (Hs, Ws, hip.SLICES_MAX_SIDE))
+        if labels is not None and (labels.dtype != torch.uint8 or tuple(labels.shape) != (D, Hs, Ws)):
+            raise ValueError("VolumeSlicer.open_case: labels must be uint8 [D, Hs, Ws] = %s, got %s %s" % ((D, Hs, Ws), labels.dtype, tuple(labels.shape)))
+        if not volume.is_cuda or (labels is not None and not labels.is_cuda):
+            raise RuntimeError("VolumeSlicer runs on the HIP device only (got %s); there is no CPU path" % volume.device)
+        dev, S = volume.device, len(self.specs)
+        ws, stats, table = self._cached(("case", dev, M), lambda: (
+            torch.empty(hip.slices_workspace(M, D, Hs, Ws), device=dev, dtype=torch.uint8),
+            torch.empty(M, hip.SLICES_NSTAT, device=dev, dtype=torch.int64), torch.empty(S, 4, device=dev, dtype=torch.float32)))
+        self.volume = volume.contiguous()
+        self.labels = None if labels is None else labels.contiguous()
+        hip.slices_stats(self.volume, self.foreground, self.q_ppm[0], self.q_ppm[1], self.specs, ws, stats, table)
+        self.stats, self.table = stats, table
+
+    def _upload(self, dev, z, rows):
+        """(z device int32 [n], params device fp32 [n, 8]): 9 n words through a pinned staging slot and one non-blocking copy.  z None:
+        the caller has its indices on the device already."""
+        n = rows.shape[0]
+        key = (dev, n)
+        if key not in self._stage:
+            self._stage[key] = [[torch.zeros(9 * n, dtype=torch.float32).pin_memory() for _ in range(self._SLOTS)], [None] * self._SLOTS, 0]
+        slots, events, s = self._stage[key]
+        self._stage[key][2] = (s + 1) % self._SLOTS
+        if events[s] is not None and not events[s].query():
+            events[s].synchronize()                             # (the copy that read this slot _SLOTS calls ago: finished long since)
+        host = slots[s]
+        host[:8 * n] = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float32).reshape(-1))
+        if z is not None:
+            host[8 * n:].view(torch.int32)[:] = torch.from_numpy(np.ascontiguousarray(z, dtype=np.int32))
+        dbuf = self._cached(("rows", dev, n), lambda: torch.empty(9 * n, device=dev, dtype=torch.float32))
+        dbuf.copy_(host, non_blocking=True)
+        if events[s] is None:
+            events[s] = torch.cuda.Event()
+        events[s].record()
+        return dbuf[8 * n:].view(torch.int32), dbuf[:8 * n].view(n, 8)
+
+    def _gather(self, z, rows):
+        if self.volume is None:
+            raise ValueError("VolumeSlicer: no case is open")
+        dev, (h, w), n = self.volume.device, self.size, rows.shape[0]
+        if not 1 <= n <= hip.SLICES_MAX_BATCH:
+            raise ValueError("VolumeSlicer: %d slices outside the limit [1, %d]" % (n, hip.SLICES_MAX_BATCH))
+        has_y = self.labels is not None
+        x, y = self._cached(("out", dev, n, h, w, has_y), lambda: (
+            torch.empty(n, self.channels, h, w, device=dev, dtype=torch.float32),
+            torch.empty(n, h, w, device=dev, dtype=self.label_dtype) if has_y else None))
+        zdev, pdev = self._upload(dev, None if isinstance(z, torch.Tensor) else z, rows)
+        if isinstance(z, torch.Tensor):
+            zdev = z
+        hip.slices_gather(self.volume, self.labels, zdev, pdev, self.table, [s[0] for s in self.specs], self.context, self.stride,
+                          _SLICES_EDGES[self.edge], _SLICES_BORDERS[self.border], self.border_value, self.label_border, x, y)
+        return x, y
+
+    def slices(self, z0, z1):
+        D = 0 if self.volume is None else int(self.volume.shape[1])
+        if self.volume is not None and not 0 <= int(z0) < int(z1) <= D:
+            raise ValueError("VolumeSlicer.slices: [%r, %r) is not a range of slices inside [0, %d)" % (z0, z1, D))
+        z = np.arange(int(z0), int(z1), dtype=np.int32)
+        return self._gather(z, self.rows(z.size))
+
+    def batch(self, z, params=None):
+        if self.volume is None:
+            raise ValueError("VolumeSlicer: no case is open")
+        D = int(self.volume.shape[1])
+        if isinstance(z, torch.Tensor):
+            if z.dtype != torch.int32 or z.dim() != 1 or not z.is_cuda or not z.is_contiguous():
+                raise ValueError("VolumeSlicer.batch: z as a tensor must be a contiguous device int32 [n] (indices outside the volume are clamped)")
+            n = int(z.numel())
+        else:
+            z = np.asarray(z, dtype=np.int64).reshape(-1)
+            if z.size and (z.min() < 0 or z.max() >= D):
+                raise ValueError("VolumeSlicer.batch: slice indices outside [0, %d)" % D)
+            z, n = z.astype(np.int32), int(z.size)
+        return self._gather(z, self.rows(n, params))
+
+    def restore(self, labels_net):
+        if self.volume is None:
+            raise ValueError("VolumeSlicer: no case is open")
+        if labels_net.dim() != 3 or labels_net.dtype != torch.uint8 or not labels_net.is_cuda:
+            raise ValueError("VolumeSlicer.restore: uint8 device labels [n, h, w] required, got %s %s" % (labels_net.dtype, tuple(labels_net.shape)))
+        n, h, w = (int(d) for d in labels_net.shape)
+        if not 1 <= n <= hip.SLICES_MAX_DEPTH or not (2 <= h <= hip.SLICES_MAX_SIDE and 2 <= w <= hip.SLICES_MAX_SIDE):
+            raise ValueError("VolumeSlicer.restore: labels %s outside the limits n in [1, %d], h, w in [2, %d]"
+                             % (tuple(labels_net.shape), hip.SLICES_MAX_DEPTH, hip.SLICES_MAX_SIDE))
+        dev, (Hs, Ws) = labels_net.device, self._src_hw()
+        y = self._cached(("restore", dev, n, h, w, Hs, Ws), lambda: torch.empty(n, Hs, Ws, device=dev, dtype=torch.uint8))
+        zdev, pdev = self._upload(dev, np.arange(n, dtype=np.int32), self.rows(n, None, (Hs, Ws), (h, w)))
+        hip.slices_gather(None, labels_net.contiguous(), zdev, pdev, None, None, 0, 1, hip.SLICES_EDGE_REPLICATE,
+                          hip.SLICES_BORDER_REPLICATE, None, 0, None, y)
+        return y

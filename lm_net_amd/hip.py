@@ -371,6 +371,31 @@ REGION_LABELS_U8 = 0
 REGION_LABELS_I64 = 1
 REGION_MAX_BATCH = 65535
 
+# include/slices/lmnet_slices.h: the statistics of an int16 / uint8 volume and the gather into fp32 2.5D batches (lm_net_amd.data.
+# VolumeSlicer).  A list of its own for the same reason, and no struct; tests/test_slices_cpu.py checks it against the header and ties
+# the two device entries to tests/test_guard_slices_gpu.py.
+SYMBOLS_SLICES = ["lmn_slices_workspace", "lmn_slices_stats", "lmn_slices_gather"]
+SLICES_I16 = 0               # LMN_SLICES_* of the header
+SLICES_U8 = 1
+SLICES_WINDOW = 0
+SLICES_ZSCORE = 1
+SLICES_PERCENTILE = 2
+SLICES_EDGE_REPLICATE = 0
+SLICES_EDGE_ZERO = 1
+SLICES_BORDER_REPLICATE = 0
+SLICES_BORDER_CONSTANT = 1
+SLICES_LABELS_U8 = 0
+SLICES_LABELS_I64 = 1
+SLICES_MAX_DEPTH = 1024
+SLICES_MAX_SIDE = 1024
+SLICES_MAX_MODALITIES = 4
+SLICES_MAX_CHANNELS = 16
+SLICES_MAX_CONTEXT = 7
+SLICES_MAX_OUT = 4096
+SLICES_MAX_BATCH = 65535
+SLICES_NSTAT = 8
+SLICES_NO_FOREGROUND = -32769
+
 _lib = None
 
 
@@ -384,7 +409,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ + SYMBOLS_REGION:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ + SYMBOLS_REGION + SYMBOLS_SLICES:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -401,6 +426,7 @@ def load():
     lib.lmn_dist_workspace.restype = C.c_int64
     lib.lmn_lovasz_workspace.restype = C.c_int64
     lib.lmn_region_workspace.restype = C.c_int64
+    lib.lmn_slices_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1718,6 +1744,72 @@ def region_bwd(logits, target, head, per_image, class_mask, coef, gscale, dlogit
     _check(load().lmn_region_bwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), int(bool(per_image)), B, Cn,
                                  H, W, C.c_uint64(int(class_mask)), _raw(coef, torch.float32, "region_bwd"), _p(gscale), _p(dlogits), _stream()),
            "region_bwd")
+
+
+def slices_workspace(M, D, Hs, Ws):
+    """Bytes of the workspace of lmn_slices_stats for M modalities of D x Hs x Ws voxels, exactly (host arithmetic, no GPU)."""
+    return _host_size("slices_workspace", load().lmn_slices_workspace(int(M), int(D), int(Hs), int(Ws)))
+
+
+def _slices_volume(what, volume):
+    """(vol_kind, M, D, Hs, Ws) of a contiguous int16 or uint8 device volume [M, D, Hs, Ws]"""
+    if volume.dim() != 4 or volume.dtype not in (torch.int16, torch.uint8) or not volume.is_cuda or not volume.is_contiguous():
+        raise ValueError("lm_net_amd.%s: a contiguous int16 or uint8 device volume [M, D, Hs, Ws] required, got %s %s"
+                         % (what, volume.dtype, tuple(volume.shape)))
+    return (SLICES_I16 if volume.dtype == torch.int16 else SLICES_U8,) + tuple(int(d) for d in volume.shape)
+
+
+def slices_stats(volume, foreground, q_lo_ppm, q_hi_ppm, specs, workspace, stats, table):
+    """stats int64 [M, 8] (n, sum v, sum v^2, min, max, v_lo, v_hi, 0) and table fp32 [S, 4] (lo, hi, a, b) of an int16 / uint8
+    volume [M, D, Hs, Ws] (lmn_slices_stats).  foreground: M ints (SLICES_NO_FOREGROUND: every voxel); q_*_ppm: the two ranks in parts
+    per million; specs: S tuples (modality, SLICES_WINDOW / _ZSCORE / _PERCENTILE, level, width), modalities not decreasing;
+    workspace: uint8 device tensor of at least slices_workspace(...) bytes."""
+    kind, M, D, Hs, Ws = _slices_volume("slices_stats", volume)
+    S = len(specs)
+    if len(foreground) != M or tuple(stats.shape) != (M, SLICES_NSTAT) or tuple(table.shape) != (S, 4):
+        raise ValueError("lm_net_amd.slices_stats: foreground (%d) / stats %s / table %s do not hold %d / [%d, %d] / [%d, 4]"
+                         % (len(foreground), tuple(stats.shape), tuple(table.shape), M, M, SLICES_NSTAT, S))
+    fg = (C.c_int32 * M)(*[int(v) for v in foreground])
+    mod, knd = (C.c_int32 * max(S, 1))(*[int(s[0]) for s in specs]), (C.c_int32 * max(S, 1))(*[int(s[1]) for s in specs])
+    lev, wid = (C.c_double * max(S, 1))(*[float(s[2]) for s in specs]), (C.c_double * max(S, 1))(*[float(s[3]) for s in specs])
+    _check(load().lmn_slices_stats(C.c_void_p(volume.data_ptr()), kind, M, D, Hs, Ws, fg, int(q_lo_ppm), int(q_hi_ppm), S, mod, knd, lev, wid,
+                                   _raw(workspace, torch.uint8, "slices_stats"), _i64(workspace.numel()),
+                                   _raw(stats, torch.int64, "slices_stats"), _p(table), _stream()), "slices_stats")
+
+
+def slices_gather(volume, labels, z, params, table, spec_mod, context, stride, edge, border, border_value, label_border, x, y):
+    """x fp32 [n, S * (2 context + 1), h, w] from an int16 / uint8 volume [M, D, Hs, Ws] and / or y uint8 / int64 [n, h, w] from uint8
+    labels [D, Hs, Ws], at the slices z (device int32 [n]) under the rows params (device fp32 [n, 8]: the inverse map m0 .. m5, gain,
+    bias) (lmn_slices_gather).  table: fp32 [S, 4] of slices_stats; spec_mod: the modality of each of its rows; border_value: M
+    floats.  volume, table and x None: label-only mode."""
+    what = "slices_gather"
+    if (volume is None) != (x is None) or (labels is None) != (y is None) or (volume is None and labels is None):
+        raise ValueError("lm_net_amd.slices_gather: a volume needs x, labels need y, and one of the two is required")
+    if labels is not None and (labels.dim() != 3 or labels.dtype != torch.uint8 or not labels.is_cuda or not labels.is_contiguous()):
+        raise ValueError("lm_net_amd.slices_gather: contiguous uint8 device labels [D, Hs, Ws] required, got %s %s" % (labels.dtype, tuple(labels.shape)))
+    if volume is not None:
+        kind, M, D, Hs, Ws = _slices_volume(what, volume)
+        if labels is not None and tuple(labels.shape) != (D, Hs, Ws):
+            raise ValueError("lm_net_amd.slices_gather: labels %s beside a volume %s" % (tuple(labels.shape), tuple(volume.shape)))
+    else:
+        kind, M, (D, Hs, Ws) = SLICES_I16, 1, (int(d) for d in labels.shape)
+    n = int(z.numel())
+    S = 0 if volume is None else len(spec_mod)
+    K = 2 * int(context) + 1
+    dst = x if x is not None else y
+    h, w = int(dst.shape[-2]), int(dst.shape[-1])
+    if tuple(params.shape) != (n, 8) or (x is not None and tuple(x.shape) != (n, S * K, h, w)) or (y is not None and tuple(y.shape) != (n, h, w)):
+        raise ValueError("lm_net_amd.slices_gather: params %s / x %s / y %s do not hold [%d, 8] / [%d, %d, %d, %d] / [%d, %d, %d]"
+                         % (tuple(params.shape), None if x is None else tuple(x.shape), None if y is None else tuple(y.shape), n, n, S * K, h, w,
+                            n, h, w))
+    if volume is not None and (tuple(table.shape) != (S, 4) or len(border_value) != M):
+        raise ValueError("lm_net_amd.slices_gather: table %s / border_value (%d) do not hold [%d, 4] / %d" % (tuple(table.shape), len(border_value), S, M))
+    mod = None if volume is None else (C.c_int32 * max(S, 1))(*[int(v) for v in spec_mod])
+    bv = None if volume is None else (C.c_float * M)(*[float(v) for v in border_value])
+    _check(load().lmn_slices_gather(None if volume is None else C.c_void_p(volume.data_ptr()), kind, _raw(labels, torch.uint8, what), M, D, Hs, Ws,
+                                    _raw(z, torch.int32, what), _p(params), n, _p(table), S, mod, int(context), int(stride), int(edge), int(border),
+                                    bv, int(label_border), h, w, _p(x), None if y is None else _raw(y, y.dtype, what),
+                                    0 if y is None else label_kind(y), _stream()), what)
 
 
 def _raw(t, dt, what):
