@@ -475,6 +475,7 @@ int lmn_na_bwd(const void* qkv, const float* rpb, const void* dout, void* dqkv, 
  * Dense global attention of GFT (core/modules.py:267-279): qkv [B,N,3C] (channel = which*C +
  * head*hd + d), out [B,N,C].  Any N (streamed over key tiles; exercised up to 16384 tokens = 2048x2048 inputs), hd <= 128 (hd <= 32:
  * matrix-core form; 33..128: VALU form at a padded width of 64 / 128 -- the wide LM_Net variants, sum(filters) / 12).
+ * Every offset is 64-bit: no limit in bytes; B and heads are grid dimensions, at most 65535 each (more is refused).
  * ------------------------------------------------------------------------------------------ */
 int lmn_gattn_fwd(const void* qkv, void* out, float* lse, int B, int N, int heads, int hd, float scale, int act_dtype,
                   lmn_stream_t stream);
@@ -535,6 +536,8 @@ int lmn_bn_bwd_coef(const float* bstats, int nrep, float count, int batch_stats,
 /* ------------------------------------------------------------------------------------------
  * Resampling rows: bilinear x2 upsample with align_corners=True (core/LM_Net.py:59-72,
  * modules.py:94,129) and the exact f x f mean pool of PyramidPool (modules.py:496).
+ * Limits: 32-bit row indices (up2, avgpool_bwd) and a 32-bit output pixel index (avgpool_fwd: B * Hout * Wout < 2^31), refused past
+ * them; the addresses are 64-bit.
  * ------------------------------------------------------------------------------------------ */
 int lmn_up2_fwd(const void* x, void* y, int B, int Hin, int Win, int C, int x_cstride, int y_cstride, int act_dtype,
                 lmn_stream_t stream);
@@ -577,7 +580,9 @@ int lmn_segloss_bwd(const float* logits, const int64_t* target, const float* w_c
 /* On-device confusion matrix (row N2): counts[t*C + p] += #pixels with label t and argmax(logits) = p.  Dice and IoU
  * follow as 2TP/(2TP+FP+FN), TP/(TP+FP+FN) (utils/train_eval_utils.py:78-95).  C in [2, 64]: C in {2,3,4} count in registers,
  * 5..64 in a C x C int32 histogram per block in LDS.  Labels outside [0, C) are dropped (Evaluator._generate_matrix); ties of the
- * argmax go to the first maximum (torch.argmax).  Float counts: exact up to 2^24 per cell and call.                 */
+ * argmax go to the first maximum (torch.argmax).  Float counts: B * HW >= 2^24 pixels per call is refused, so a call that starts
+ * from zeroed counts is exact; counts that are carried over stay exact while every cell stays below 2^24 (the caller splits larger
+ * inputs and accumulates in a wider type, as lm_net_amd.ConfusionMeter does).                                                   */
 int lmn_confusion(const float* logits, const int64_t* target, int B, int C, int64_t HW, float* counts, lmn_stream_t stream);
 /* Device-side input pipeline (row N4): uint8 HWC images [B,Hs,Ws,3] (channel order untouched, as cv2.imread hands it
  * over) and grayscale masks [B,Hs,Ws] -> normalised fp32 NCHW images [B,3,H,W] and int64 labels [B,H,W].
@@ -701,7 +706,7 @@ int lmn_post_render(const uint8_t* labels_net, int B, int H, int W, const int32_
                     lmn_stream_t stream);
 /* lmn_confusion with the arg-max already taken: pred_labels [B,HW] uint8 (e.g. a cleaned label map), counts[t*C + p] += #pixels
  * with label t and prediction p (train_eval_utils.py:78-95 on a label map); pixels whose label or prediction is outside [0, C)
- * are dropped.  Float counts: exact up to 2^24 per cell and call.                                                                */
+ * are dropped.  Float counts: B * HW >= 2^24 pixels per call is refused, as for lmn_confusion (exact from zeroed counts).       */
 int lmn_confusion_labels(const uint8_t* pred_labels, const int64_t* target, int B, int C, int64_t HW, float* counts,
                          lmn_stream_t stream);
 /* One AdamW step over flat buffers of n floats (n % 4 == 0): replaces torch.optim.AdamW.step() of

@@ -1584,6 +1584,14 @@ static int wgrad_setup(const lmn_wgrad_args_t& A, WgradParams& P, WgGeom& G) {
   if (up2) {
     LMN_REQUIRE(A.nsrc == 1 && A.ksize == 3 && A.stride == 1 && A.Hin % 2 == 0 && A.Win % 2 == 0 && !(A.src[0].flags & ~LMN_SRC_UP2) && !A.src[0].scale,
                 "conv_wgrad: LMN_SRC_UP2 belongs to single-source 3x3 stride-1 calls (Hin x Win = the upsampled size) without other source transforms");
+    // (size is a reason of its own: a caller whose map is wide enough learns that the BYTES put the call outside the wgrad3 form)
+    int64_t big = (int64_t)A.B * A.Hout * A.Wout * A.dy_cstride * esz;
+    const int64_t xb = (int64_t)A.B * A.Hin * A.Win * A.src[0].cstride * esz;
+    if (xb > big) big = xb;
+    LMN_REQUIRE(big < 0xfffffff0LL,
+                "conv_wgrad: LMN_SRC_UP2: an operand of %lld bytes (counted at the upsampled size) is not below the 4294967280-byte limit of the wgrad3 "
+                "form's 32-bit byte offsets: upsample with lmn_up2_fwd and take the plain weight gradient (lmn_conv_wgrad_up2_ok says so beforehand)",
+                (long long)big);
     LMN_REQUIRE(v1 && (P.XH + 1) / 2 + 2 <= (NMT * NNT == 1 ? 3 : 2) * 64 / 19,
                 "conv_wgrad: LMN_SRC_UP2 needs the wgrad3 form (upsampled map >= 32 wide; lmn_conv_wgrad_up2_ok says so beforehand)");
   }

@@ -565,6 +565,7 @@ int lmn_gattn_fwd(const void* qkv, void* out, float* lse, int B, int N, int head
   LMN_REQUIRE_DT(act_dtype, "gattn_fwd");
   LMN_REQUIRE(qkv && out && lse && B > 0 && N > 0 && heads > 0, "gattn_fwd: bad argument");
   LMN_REQUIRE(hd >= 1 && hd <= GA_DMAX, "gattn_fwd: head_dim %d > %d", hd, GA_DMAX);
+  LMN_REQUIRE(B <= 65535 && heads <= 65535, "gattn_fwd: B=%d images, %d heads: the grid takes at most 65535 of either per call (every offset is 64-bit: no byte limit)", B, heads);
   GaGeom g{B, N, heads, hd, heads * hd, scale, lmn_prio_level((hipStream_t)stream)};
   if (hd > GA_D) {   // wide variants: the VALU form at padded width 64 / 128
 #define LMN_GAW(DV) LMN_LAUNCH((gattn_fwd_kernel<DV, T>), dim3(lmn_cdiv(N, GaCfg<DV>::ROWS), heads, B), dim3(256), 0, (hipStream_t)stream, (const T*)qkv, (T*)out, lse, g)
@@ -588,6 +589,7 @@ int lmn_gattn_bwd(const void* qkv, const void* out, const void* dout, const floa
   LMN_REQUIRE_DT(act_dtype, "gattn_bwd");
   LMN_REQUIRE(qkv && out && dout && lse && dqkv && delta && B > 0 && N > 0 && heads > 0, "gattn_bwd: bad argument");
   LMN_REQUIRE(hd >= 1 && hd <= GA_DMAX, "gattn_bwd: head_dim %d > %d", hd, GA_DMAX);
+  LMN_REQUIRE(B <= 65535 && heads <= 65535, "gattn_bwd: B=%d images, %d heads: the grid takes at most 65535 of either per call (every offset is 64-bit: no byte limit)", B, heads);
   GaGeom g{B, N, heads, hd, heads * hd, scale, lmn_prio_level((hipStream_t)stream)};
   if (hd > GA_D) {
 #define LMN_GAW(DV)                                                                                                             \

@@ -12,8 +12,9 @@ namespace {
 
 constexpr int MT_MAXC = 64;
 
-// Confusion matrix of argmax(logits) against the labels: counts[t*C + p] += 1 (float counts are
-// exact up to 2^24 per launch per cell; the host accumulates in int64/double).
+// Confusion matrix of argmax(logits) against the labels: counts[t*C + p] += 1.  The float cells are exact while
+// they stay below 2^24: the entries refuse B * HW >= 2^24 pixels per call, and the host (ConfusionMeter) splits larger inputs, hands
+// every call zeroed cells and accumulates in double.
 template <int C>
 __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                         int B, int64_t hw, float* __restrict__ counts) {
@@ -28,7 +29,8 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict_
     const int64_t b = idx / hw, i = idx - b * hw;
     const float* lg = logits + b * C * hw;
     const int best = pred_argmax<C>(lg + i, hw);
-    const int y = (int)target[idx];                    // (no cell k equals y * C + best for a label outside [0, C))
+    const int y = pred_class(target[idx], C, -1);      // (tested as int64: a label such as -2^40 has the low word of class 0; no cell
+                                                       //  k equals -C + best, so a label outside [0, C) is counted nowhere)
 #pragma unroll
     for (int k = 0; k < C * C; ++k) cnt[k] += (k == y * C + best) ? 1 : 0;
   }
@@ -142,7 +144,8 @@ extern "C" {
 int lmn_confusion(const float* logits, const int64_t* target, int B, int C, int64_t HW, float* counts, lmn_stream_t stream) {
   LMN_REQUIRE(logits && target && counts, "confusion: null pointer");
   LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= MT_MAXC, "confusion: C=%d not in [2, 64]", C);
-  LMN_REQUIRE((int64_t)B * HW < (1LL << 24) * 64, "confusion: more than 2^30 pixels per call");
+  LMN_REQUIRE((int64_t)B * HW < (1LL << 24), "confusion: B*HW=%lld pixels, float counts are exact below 2^24 = 16777216 pixels per call (split the call)",
+              (long long)((int64_t)B * HW));
   hipStream_t st = (hipStream_t)stream;
   const int grid = loss_grid((int64_t)B * HW, 512);
   switch (C) {
@@ -157,7 +160,8 @@ int lmn_confusion(const float* logits, const int64_t* target, int B, int C, int6
 int lmn_confusion_labels(const uint8_t* pred_labels, const int64_t* target, int B, int C, int64_t HW, float* counts, lmn_stream_t stream) {
   LMN_REQUIRE(pred_labels && target && counts, "confusion_labels: null pointer");
   LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= MT_MAXC, "confusion_labels: C=%d not in [2, 64]", C);
-  LMN_REQUIRE((int64_t)B * HW < (1LL << 24) * 64, "confusion_labels: more than 2^30 pixels per call");
+  LMN_REQUIRE((int64_t)B * HW < (1LL << 24), "confusion_labels: B*HW=%lld pixels, float counts are exact below 2^24 = 16777216 pixels per call (split the call)",
+              (long long)((int64_t)B * HW));
   const int64_t total = (int64_t)B * HW;
   LMN_LAUNCH(confusion_labels_kernel, dim3(loss_grid(total, 1024)), dim3(256), (size_t)C * C * sizeof(int), (hipStream_t)stream, pred_labels,
              target, C, total, counts);

@@ -198,21 +198,21 @@ __global__ __launch_bounds__(256) void na_bwd_q_kernel(const TA* __restrict__ qk
   const int c = (threadIdx.x % g.C4) * 4;
   const int slot = threadIdx.x / g.C4;
   const int npix = g.B * g.H * g.W;
-  const int nit = (npix + (int)gridDim.x * PB - 1) / ((int)gridDim.x * PB);
+  const int nit = (int)(((int64_t)npix + (int64_t)gridDim.x * PB - 1) / ((int64_t)gridDim.x * PB));   // (the padded count and pix * C pass 2^31 where npix does not: 64-bit)
   f32x4 bins[9];
 #pragma unroll
   for (int n = 0; n < 9; ++n) bins[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int it = 0; it < nit; ++it) {
-    int pix = (it * (int)gridDim.x + (int)blockIdx.x) * PB + slot;
-    const bool ok = slot < PB && pix < npix;
-    if (!ok) pix = npix - 1;  // keep every lane in the shuffles
+    const int64_t p64 = ((int64_t)it * gridDim.x + blockIdx.x) * PB + slot;
+    const bool ok = slot < PB && p64 < npix;
+    const int pix = ok ? (int)p64 : npix - 1;  // keep every lane in the shuffles
     const NaPix pd = na_decode_pix(g, (uint32_t)pix);
     const int x = pd.x, y = pd.y, b = pd.b;
     const int sy = wstart(y, g.H), sx = wstart(x, g.W);
     const int64_t ib = (int64_t)b * g.H * g.W * 3 * g.C;
     const TA* base = qkv + ib;
     const f32x4 q = ld4(base + ((int64_t)y * g.W + x) * 3 * g.C + c) * g.scale;
-    const f32x4 dO = ld4(dout + pix * g.C + c);
+    const f32x4 dO = ld4(dout + (int64_t)pix * g.C + c);
     int hidx[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) hidx[k] = ((c + k) / HD) * 25;
@@ -280,8 +280,8 @@ __global__ __launch_bounds__(256) void na_bwd_q_kernel(const TA* __restrict__ qk
       f32x4 lse;
 #pragma unroll
       for (int k = 0; k < 4; ++k) lse[k] = mx[k] + __logf(den[k]);
-      stat_store<HD>(stat + pix * 2 * g.heads, c, lse, ok);
-      stat_store<HD>(stat + pix * 2 * g.heads + g.heads, c, dsum, ok);
+      stat_store<HD>(stat + (int64_t)pix * 2 * g.heads, c, lse, ok);
+      stat_store<HD>(stat + (int64_t)pix * 2 * g.heads + g.heads, c, dsum, ok);
     }
   }
   // interior bins: park per thread, then one thread per (quad, neighbour, component) sums its PB pixel slots

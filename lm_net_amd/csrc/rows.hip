@@ -1476,6 +1476,9 @@ int lmn_avgpool_fwd(const void* x, void* y, int B, int Hout, int Wout, int f, in
   LMN_REC(lmn_avgpool_fwd(x, y, B, Hout, Wout, f, C, x_cstride, y_cstride, act_dtype, stream));
   LMN_REQUIRE_DT(act_dtype, "avgpool_fwd");
   LMN_REQUIRE(x && y && B > 0 && Hout > 0 && Wout > 0 && f >= 1 && C % 4 == 0 && C >= 4 && C <= 1024 && x_cstride >= C && y_cstride >= C && x_cstride % 4 == 0, "avgpool_fwd: bad argument");
+  // (both forms index output pixels in 32 bits: the wave form's `total`, the block form's grid and its blockIdx.x decode)
+  LMN_REQUIRE((int64_t)B * Hout * Wout < (1LL << 31), "avgpool_fwd: %lld output pixels exceed the 32-bit pixel index (limit 2^31 pixels per call)",
+              (long long)((int64_t)B * Hout * Wout));
   if (C <= 256 && (int64_t)B * Hout * Wout < (1LL << 30)) {   // wave per output pixel
     const int total = B * Hout * Wout;
     LMN_ACT_DISPATCH(act_dtype, LMN_LAUNCH((avgpool_fwd_wave_kernel<T>), dim3(lmn_cdiv(total, 4)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y,

@@ -1205,7 +1205,8 @@ def segloss_bwd(logits, target, w_ce, coef, gscale, dlogits):
 
 
 def confusion(logits, target, counts):
-    """counts[t*C + p] += pixels with label t and arg-max p of fp32 logits [B, C, ...] (lmn_confusion); counts: C*C floats."""
+    """counts[t*C + p] += pixels with label t and arg-max p of fp32 logits [B, C, ...] (lmn_confusion); counts: C*C floats.  The cells
+    are floats: 2^24 pixels or more in one call are refused, so a call on zeroed counts is exact (ConfusionMeter splits larger inputs)."""
     B, Cn, hw = _dims(logits)
     if counts.numel() != Cn * Cn or target.numel() != B * hw:
         raise ValueError("lm_net_amd.confusion: logits %s need %d x %d counts and %d labels, got counts %s and target %s"
@@ -1822,7 +1823,8 @@ def _raw(t, dt, what):
 
 
 def confusion_labels(pred, target, counts):
-    """counts[t*C + p] += pixels with label t and prediction p, for a uint8 label-map prediction [B,H,W] (lmn_confusion_labels)."""
+    """counts[t*C + p] += pixels with label t and prediction p, for a uint8 label-map prediction [B,H,W] (lmn_confusion_labels).
+    Float cells, as confusion(): 2^24 pixels or more in one call are refused."""
     B = pred.shape[0]
     hw = pred.numel() // B
     if target.numel() != pred.numel():

@@ -64,6 +64,27 @@ def _target(target, pred, what):
     return target
 
 
+CONFUSION_MAX_PIXELS = (1 << 24) - 1    # lmn_confusion / lmn_confusion_labels count in float cells and refuse B * HW >= 2^24 per call
+
+
+def _confusion_calls(pred, target, limit=CONFUSION_MAX_PIXELS):
+    """(pred, target) pieces of at most ``limit`` pixels each that together cover every pixel once (pure: no device check): whole images
+    while one image fits, else contiguous pixel ranges of one image ([1, C, 1, n] logits -- a copy of the slice -- or a [1, 1, n] map)."""
+    B, hw = int(target.shape[0]), int(target.shape[1] * target.shape[2])
+    if B * hw <= limit:
+        yield pred, target
+    elif hw <= limit:
+        nb = limit // hw
+        for b in range(0, B, nb):
+            yield pred[b:b + nb], target[b:b + nb]
+    else:
+        for b in range(B):                                           # (pieces keep the rank the entries' wrappers go by)
+            p = pred[b:b + 1].reshape(1, -1, 1, hw) if pred.dim() == 4 else pred[b:b + 1].reshape(1, 1, hw)
+            t = target[b:b + 1].reshape(1, 1, hw)
+            for i in range(0, hw, limit):
+                yield p[..., i:i + limit].contiguous(), t[..., i:i + limit]
+
+
 class ConfusionMeter:
     def __init__(self, n_classes=2, device="cuda"):
         if not 2 <= n_classes <= 64:
@@ -80,11 +101,12 @@ class ConfusionMeter:
         predictions outside [0, C) are not counted)."""
         if not logits.is_cuda:
             raise RuntimeError("lm_net_amd.ConfusionMeter: device tensors required (the HIP path has no CPU fallback)")
-        counts = torch.zeros(self.n, self.n, device=logits.device)      # exact: < 2^24 per cell and launch
         pred = _prediction(logits, self.n, "ConfusionMeter", torch.uint8)
         target = _target(target, pred, "ConfusionMeter")
-        (hip.confusion if pred.dim() == 4 else hip.confusion_labels)(pred, target, counts)
-        self.total += counts.double()
+        for p, t in _confusion_calls(pred, target):
+            counts = torch.zeros(self.n, self.n, device=pred.device)    # float cells, exact: every call sees < 2^24 pixels
+            (hip.confusion if p.dim() == 4 else hip.confusion_labels)(p, t, counts)
+            self.total += counts.double()
 
     def compute(self):
         """{'dice': [per class], 'iou': [per class], 'accuracy': float, 'confusion': [[...]]} -- rows = label -- and the
