@@ -353,7 +353,9 @@ class LM_Net(nn.Module):
         direct_grads=True: the backward node writes `.grad` itself instead of returning ~510 gradients to the autograd engine
         (one AccumulateGrad node each, 2.5 ms of host time per step).  `loss.backward()` then behaves as before (including
         accumulation into existing `.grad`); `torch.autograd.grad(loss, parameters)` and tensor hooks on parameters do not see
-        these gradients -- hence opt-in."""
+        these gradients -- hence opt-in.
+        A planned pass never waits for the caller's stream.  A host-launched training step does when that stream is stalled behind
+        earlier work: its weight-gradient flushes then upload new job tables with a blocking copy (hip.wgrad_reduce_flush)."""
         self.use_plans = bool(on)
         self._direct_grads = bool(on and direct_grads)
         if not on:

@@ -646,7 +646,8 @@ class VolumeSlicer:
     sample(n, rng) draws per sample a ShiftScaleRotate matrix (`ssr_matrix` on the output grid, probability p_ssr), the two flips and
     an intensity gain 1 + U[-gain_limit, gain_limit] and bias U[-bias_limit, bias_limit]; rng: None, an int seed or a numpy
     Generator.  Nothing synchronises.  The returned tensors are the slicer's own, kept per geometry: a later call of the same
-    geometry overwrites them, and after the first call of a geometry nothing is allocated on the device."""
+    geometry overwrites them, and after the first call of a geometry nothing is allocated on the device.  Outputs and staging are per
+    geometry, not per stream: use from two streams at once needs one VolumeSlicer object per stream."""
 
     _SLOTS = 8
 

@@ -874,7 +874,12 @@ def wgrad_reduce_flush():
     device job tables (the caller keeps them alive while a recorded plan references them); [] when nothing was pending.
     The batched kernel adds into its destinations with plain read-modify-writes, so two jobs of one launch must not share a
     destination (a weight used twice, a module called twice, accumulation into one explicit dW): such jobs are split into
-    consecutive launches, which the stream serialises as the per-layer reduce launches used to."""
+    consecutive launches, which the stream serialises as the per-layer reduce launches used to.
+    A job table whose bytes were not seen before is uploaded with a BLOCKING copy from pageable memory on torch's current stream:
+    the host waits for everything queued on that stream.  Pointers repeat from step to step on an idle stream, so a steady host-
+    launched step hits the cache and does not wait; behind a stalled caller's stream the allocator hands out other blocks, every
+    flush misses and the step waits for the stream (tests/test_busy_model_gpu.py pins this; recorded plans do not flush from the
+    host and never wait).  The wait is load-bearing: see DESIGN 5u before replacing it with a non-blocking copy."""
     key = stream_key()
     jobs = _RJOBS.pop(key, None)
     if not jobs:

@@ -586,7 +586,8 @@ class LovaszLoss(torch.nn.Module):
     target is 0 or 1.  Device tensors only; nothing synchronises; the scratch of a geometry (workspace, errors, order, counts) is kept
     and the per-call tensors (coefficients, sums, loss, gradient) come from torch's caching allocator, so nothing is allocated on the
     device after the first call of a geometry (``ranks`` holds the last ``(errors, perm, counts)``: they are overwritten by the next
-    call).  No float atomics: loss and gradient are bit-identical from call to call in either deterministic mode.
+    call).  The scratch is per geometry, not per stream: use from two streams at once needs one LovaszLoss object per stream.
+    No float atomics: loss and gradient are bit-identical from call to call in either deterministic mode.
     Deliberate difference from torch: a segment without a valid element contributes 0 and an average over no segment is 0 with an
     all-zero gradient, never NaN; every void position has gradient +0.  Limits: B * C * H * W < 2^31, at most 65535 segments."""
 
@@ -706,7 +707,8 @@ class RegionLoss(torch.nn.Module):
     valid when its label is in ``[0, C)`` and void otherwise, ``ignore_index`` or not.  ``head="sigmoid"``: 1 .. 64 planes, target planes
     ``[B, C, H, W]`` (or ``[B, H, W]`` at C = 1) of uint8 / bool / int64, an element is valid when its target is 0 or 1.  Device tensors
     only; nothing synchronises; the scratch of a geometry is kept and the per-call tensors come from torch's caching allocator, so
-    nothing is allocated on the device after the first call of a geometry.
+    nothing is allocated on the device after the first call of a geometry.  The scratch is per geometry, not per stream: use from two
+    streams at once needs one RegionLoss object per stream.
     Deliberate difference from torch: a denominator that is exactly 0 gives R = 1, a group without a valid element contributes 0, the
     loss is never NaN, ``u = 1 - R <= 0`` under ``exponent != 1`` gives 0 with a zero gradient, and every void position has gradient
     +0.  Limits: B <= 65535, B * C * H * W < 2^31."""

@@ -209,16 +209,15 @@ def test_repeatable_and_on_a_side_stream():
     p = _dev(pred)
     a, b = post(p, src_hw, frames), post(p, src_hw, frames)
     ra, rb = post.components(p), post.components(p)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        c = post(p, src_hw, frames)
-        rc = post.components(p)
-    torch.cuda.current_stream().wait_stream(side)
-    for other in (b, c):
-        assert all(torch.equal(x, y) for x, y in zip(a, other))
-    for other in (rb, rc):
-        assert torch.equal(ra[0], other[0]) and torch.equal(ra[1], other[1])
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
+    assert torch.equal(ra[0], rb[0]) and torch.equal(ra[1], rb[1])
+    # a side stream that is still busy when the calls are issued (tests/busy.py): cleaning, ragged contour overlays and components of
+    # inputs that reach the buffers only in stream order -- a launch, memset or copy on any other stream sees another case -- with no
+    # wait for the stream and the bits of a default-stream call
+    import busy
+    import busy_cases as K
+    from test_busy_data_gpu import _make, _side
+    busy.run(K.subjects()["DevicePostprocess"], _make("DevicePostprocess"), _side())
 
 
 def test_meters_take_cleaned_label_maps():
