@@ -13,6 +13,8 @@ maps made on the device at every step; ``lm_net_amd.loss.distance_maps``),
 segmented device sort; ``lm_net_amd.loss.lovasz_ranks``),
 ``lm_net_amd.loss.RegionLoss`` (Dice, Jaccard, Tversky / focal Tversky and generalized Dice, per batch or per image, from one sums
 pass; ``lm_net_amd.loss.region_sums``),
+``lm_net_amd.loss.SoftSegLoss`` / ``DistillLoss`` (cross entropy + Dice against a distribution per pixel and the distillation term
+against a teacher's logits) with ``lm_net_amd.data.DeviceMix`` (Mixup / CutMix of a device batch; ``MixedTarget``),
 ``lm_net_amd.optim.FusedAdamW`` (one-launch AdamW; parameter groups, gradient clipping, the GradScaler skip and an EMA of the weights
 without a host decision; ``lm_net_amd.optim.decay_groups``), ``lm_net_amd.metrics.ConfusionMeter`` (on-device Dice / IoU),
 ``lm_net_amd.metrics.SurfaceDistanceMeter`` (on-device HD / HD95 / ASSD / RVD),
@@ -27,12 +29,12 @@ volume, cavity filling, between the prediction and ``VolumeSurfaceMeter``),
 ``lm_net_amd.ddp.DistributedLMNet`` (bucketed RCCL gradient all-reduce).
 """
 from .LM_Net import LM_Net  # noqa: F401
-from .data import VolumeSlicer  # noqa: F401
-from .loss import (BoundaryLoss, FocalLoss, HausdorffDTLoss, LovaszLoss, RegionLoss, SegLoss, SigmoidSegLoss, distance_maps,  # noqa: F401
-                   lovasz_ranks, region_sums)
+from .data import DeviceMix, VolumeSlicer  # noqa: F401
+from .loss import (BoundaryLoss, DistillLoss, FocalLoss, HausdorffDTLoss, LovaszLoss, MixedTarget, RegionLoss, SegLoss,  # noqa: F401
+                   SigmoidSegLoss, SoftSegLoss, distance_maps, lovasz_ranks, region_sums)
 from .metrics import CurveMeter, ImageStatsMeter, LesionMeter, SigmoidStatsMeter, VolumeSurfaceMeter  # noqa: F401
 from .post import VolumePostprocess  # noqa: F401
 
 __all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter", "VolumeSurfaceMeter", "VolumePostprocess",
            "LesionMeter", "BoundaryLoss", "HausdorffDTLoss", "distance_maps", "LovaszLoss", "lovasz_ranks", "RegionLoss",
-           "region_sums", "VolumeSlicer"]
+           "region_sums", "VolumeSlicer", "SoftSegLoss", "DistillLoss", "MixedTarget", "DeviceMix"]

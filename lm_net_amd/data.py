@@ -857,3 +857,102 @@ class VolumeSlicer:
         hip.slices_gather(None, labels_net.contiguous(), zdev, pdev, None, None, 0, 1, hip.SLICES_EDGE_REPLICATE,
                           hip.SLICES_BORDER_REPLICATE, None, 0, None, y)
         return y
+
+
+class DeviceMix:
+    """Mixup (Zhang et al. 2018) and CutMix (Yun et al. 2019) of a batch that is already on the device -- the output of
+    ``DeviceAugment`` / ``DevicePreprocess`` -- in one pass (``lmn_mix_batch``, include/soft/lmnet_soft.h).
+
+    ``mix(x, y, rows=None) -> (x_mixed, MixedTarget(ya, yb, lam))`` for fp32 ``x`` ``[B, Cin, H, W]`` and a uint8 / int64 label map ``y``
+    ``[B, H, W]``, out of place.  A Mixup sample is ``lam * x[b] + (1 - lam) * x[partner]`` -- evaluated unfused in fp32, so numpy
+    restates it bit for bit -- with ``ya = y[b]``, ``yb = y[partner]``: the two-hot target ``SoftSegLoss`` takes.  A CutMix sample takes
+    pixels AND labels inside its box from the partner, so ``ya == yb``, ``lam == 1``, void labels travel with their pixels, and with
+    ``mixup_alpha == 0`` the result is a hard label map every criterion of the package takes (``target.labels``).
+
+    ``sample(B, H, W)`` draws the rows on the host -- ``(partner, mode, lam, boxes)`` -- by the rule timm documents for its ``Mixup``
+    (timm is not a dependency: parity with its code is not pinned): a sample is mixed with probability ``prob``; CutMix is chosen with
+    ``switch_prob`` when both alphas are positive, else whichever alpha is positive; ``lam ~ Beta(alpha, alpha)``; the CutMix box has
+    side ratio ``sqrt(1 - lam)`` and a uniform centre, is clipped to the image, and ``lam`` becomes the kept area fraction;
+    ``partner = B - 1 - b`` (``"flip"``) or a permutation (``"perm"``); ``per_sample=False`` makes one draw for the batch.
+    generator: None, an int seed, a numpy Generator or a torch.Generator, as in ``DeviceAugment``.  Device tensors only; nothing
+    synchronises; the row buffer of a geometry is kept and the outputs come from torch's caching allocator."""
+
+    MODES = {"none": hip.MIX_NONE, "mixup": hip.MIX_MIXUP, "cutmix": hip.MIX_CUTMIX}
+
+    def __init__(self, mixup_alpha=0.0, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, per_sample=True, partner="flip", generator=None):
+        if not (0.0 <= mixup_alpha < float("inf") and 0.0 <= cutmix_alpha < float("inf")):
+            raise ValueError("DeviceMix: mixup_alpha = %r, cutmix_alpha = %r must be finite and >= 0" % (mixup_alpha, cutmix_alpha))
+        if not 0.0 <= prob <= 1.0 or not 0.0 <= switch_prob <= 1.0:
+            raise ValueError("DeviceMix: prob = %r, switch_prob = %r outside [0, 1]" % (prob, switch_prob))
+        if partner not in ("flip", "perm"):
+            raise ValueError("DeviceMix: partner = %r, expected 'flip' or 'perm'" % (partner,))
+        self.mixup_alpha, self.cutmix_alpha, self.prob, self.switch_prob = float(mixup_alpha), float(cutmix_alpha), float(prob), float(switch_prob)
+        self.per_sample, self.partner = bool(per_sample), partner
+        if generator is None or isinstance(generator, (int, np.integer)):
+            self._rng = np.random.default_rng(generator)
+        elif isinstance(generator, np.random.Generator):
+            self._rng = generator
+        elif isinstance(generator, torch.Generator):
+            self._rng = None
+        else:
+            raise ValueError("DeviceMix: generator must be None, an int seed, a numpy Generator or a torch.Generator")
+        self._torch_gen = generator if self._rng is None else None
+        self.last_rows = None          # the host table of the last call (kept alive until its H2D copy has run)
+        self._scratch = {}
+
+    def _generator(self):
+        if self._rng is not None:
+            return self._rng
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=self._torch_gen))   # one numpy stream per batch, seeded from torch's
+        return np.random.default_rng(seed)
+
+    def _draw(self, rng, H, W):
+        """(mode, lam, box) of one draw"""
+        if not rng.random() < self.prob or (self.mixup_alpha <= 0.0 and self.cutmix_alpha <= 0.0):
+            return hip.MIX_NONE, np.float32(1.0), (0, 0, 0, 0)
+        cut = self.cutmix_alpha > 0.0 and (self.mixup_alpha <= 0.0 or rng.random() < self.switch_prob)
+        alpha = self.cutmix_alpha if cut else self.mixup_alpha
+        lam = np.float32(min(max(rng.beta(alpha, alpha), 0.0), 1.0))
+        if not cut:
+            return hip.MIX_MIXUP, lam, (0, 0, 0, 0)
+        ratio = math.sqrt(1.0 - float(lam))
+        ch, cw = int(H * ratio), int(W * ratio)
+        cy, cx = int(rng.integers(H)), int(rng.integers(W))
+        y0, y1 = min(max(cy - ch // 2, 0), H), min(max(cy + ch // 2, 0), H)
+        x0, x1 = min(max(cx - cw // 2, 0), W), min(max(cx + cw // 2, 0), W)
+        return hip.MIX_CUTMIX, np.float32(1.0 - (y1 - y0) * (x1 - x0) / float(H * W)), (y0, x0, y1, x1)
+
+    def sample(self, B, H, W):
+        """The host table of one batch, int32 ``[B, 8]`` (``hip.mix_rows``): partner, mode, lam, 1 - lam, y0, x0, y1, x1."""
+        rng = self._generator()
+        partner = np.arange(B - 1, -1, -1) if self.partner == "flip" else rng.permutation(B)
+        draws = [self._draw(rng, H, W) for _ in range(B)] if self.per_sample else [self._draw(rng, H, W)] * B
+        return hip.mix_rows(partner, [d[0] for d in draws], [d[1] for d in draws], [d[2] for d in draws])
+
+    def mix(self, x, y, rows=None):
+        from .loss import MixedTarget
+        if not torch.is_tensor(x) or x.dim() != 4 or x.dtype != torch.float32:
+            raise ValueError("DeviceMix: x must be an fp32 tensor [B, Cin, H, W], got %s %s" % (getattr(x, "dtype", None), tuple(getattr(x, "shape", ()))))
+        B, Cin, H, W = x.shape
+        if not torch.is_tensor(y) or tuple(y.shape) != (B, H, W) or y.dtype not in (torch.uint8, torch.int64):
+            raise ValueError("DeviceMix: y must be a uint8 or int64 label map %s, got %s %s" % ((B, H, W), getattr(y, "dtype", None), tuple(getattr(y, "shape", ()))))
+        if B > hip.SOFT_MAX_BATCH or not 1 <= Cin <= 64 or min(B, H, W) < 1 or B * Cin * H * W >= 1 << 31:
+            raise ValueError("DeviceMix: B = %d, Cin = %d, B * Cin * H * W = %d outside the limits B <= %d, Cin <= 64, B * Cin * H * W in [1, 2^31)"
+                             % (B, Cin, B * Cin * H * W, hip.SOFT_MAX_BATCH))
+        if not x.is_cuda or not y.is_cuda:
+            raise RuntimeError("lm_net_amd.DeviceMix: device tensors required (the HIP path has no CPU fallback)")
+        rows = self.sample(B, H, W) if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        if tuple(rows.shape) != (B, hip.MIX_ROW_WORDS):
+            raise ValueError("DeviceMix: rows %s, expected %s" % (tuple(rows.shape), (B, hip.MIX_ROW_WORDS)))
+        key = (x.device, B)
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty((B, hip.MIX_ROW_WORDS), device=x.device, dtype=torch.int32)
+        soft = self.mixup_alpha > 0.0 or bool((rows[:, 1] == hip.MIX_MIXUP).any())
+        x, y = x.contiguous(), y.contiguous()
+        x_out, ya, lam = torch.empty_like(x), torch.empty_like(y), torch.empty(B, device=x.device)
+        yb = torch.empty_like(y) if soft else None
+        self.last_rows = rows
+        hip.mix_batch(x, y, rows, self._scratch[key], x_out, ya, yb, lam)
+        target = MixedTarget(ya, ya if yb is None else yb, lam)
+        target.hard = not soft
+        return x_out, target

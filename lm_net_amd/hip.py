@@ -396,6 +396,25 @@ SLICES_MAX_BATCH = 65535
 SLICES_NSTAT = 8
 SLICES_NO_FOREGROUND = -32769
 
+# include/soft/lmnet_soft.h: the soft-target criteria -- cross entropy + Dice against probabilities or a Mixup pair, distillation against
+# a teacher's logits -- and the Mixup / CutMix batch mixer (lm_net_amd.loss.SoftSegLoss, DistillLoss, lm_net_amd.data.DeviceMix).  A
+# list of its own for the same reason, and no struct; tests/test_soft_cpu.py checks it against the header and ties the three device
+# entries to tests/test_guard_soft_gpu.py.
+SYMBOLS_SOFT = ["lmn_soft_workspace", "lmn_soft_fwd", "lmn_soft_bwd", "lmn_mix_batch"]
+SOFT_PROBS = 0               # LMN_SOFT_* of the header
+SOFT_PAIR = 1
+SOFT_TEACHER_F32 = 2
+SOFT_TEACHER_BF16 = 3
+SOFT_SOFTMAX = 0
+SOFT_SIGMOID = 1
+SOFT_LABELS_U8 = 0
+SOFT_LABELS_I64 = 1
+SOFT_MAX_BATCH = 65535
+MIX_NONE = 0                 # LMN_MIX_* of the header
+MIX_MIXUP = 1
+MIX_CUTMIX = 2
+MIX_ROW_WORDS = 8
+
 _lib = None
 
 
@@ -409,7 +428,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ + SYMBOLS_REGION + SYMBOLS_SLICES:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ + SYMBOLS_REGION + SYMBOLS_SLICES + SYMBOLS_SOFT:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -427,6 +446,7 @@ def load():
     lib.lmn_lovasz_workspace.restype = C.c_int64
     lib.lmn_region_workspace.restype = C.c_int64
     lib.lmn_slices_workspace.restype = C.c_int64
+    lib.lmn_soft_workspace.restype = C.c_int64
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1750,6 +1770,106 @@ def region_bwd(logits, target, head, per_image, class_mask, coef, gscale, dlogit
     _check(load().lmn_region_bwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), int(bool(per_image)), B, Cn,
                                  H, W, C.c_uint64(int(class_mask)), _raw(coef, torch.float32, "region_bwd"), _p(gscale), _p(dlogits), _stream()),
            "region_bwd")
+
+
+def soft_workspace(reader, head, B, Cn, H, W):
+    """Bytes of the deterministic-mode slots of lmn_soft_fwd, exactly (host arithmetic, no GPU)."""
+    return _host_size("soft_workspace", load().lmn_soft_workspace(int(reader), int(head), int(B), int(Cn), int(H), int(W)))
+
+
+def _soft_args(what, logits, reader, head, target, ya, yb, lam):
+    """The checked tensors of lmn_soft_fwd / _bwd -> (B, C, H, W, label kind)."""
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise ValueError("lm_net_amd.%s: contiguous logits [B, C, H, W] required, got %s" % (what, tuple(logits.shape)))
+    B, Cn, H, W = logits.shape
+    full, lab = (B, Cn, H, W), ((B, H, W) if head == SOFT_SOFTMAX else (B, Cn, H, W))
+    dev = lambda t: t.is_cuda and t.is_contiguous()
+    if reader == SOFT_PAIR:
+        if target is not None or ya is None or yb is None or lam is None:
+            raise ValueError("lm_net_amd.%s: the pair reader takes ya, yb and lam and no target" % what)
+        if tuple(ya.shape) != lab or tuple(yb.shape) != lab or ya.dtype != yb.dtype or not dev(ya) or not dev(yb):
+            raise ValueError("lm_net_amd.%s: ya %s %s / yb %s %s, expected two contiguous device label maps %s of one type"
+                             % (what, ya.dtype, tuple(ya.shape), yb.dtype, tuple(yb.shape), lab))
+        if lam.dtype != torch.float32 or tuple(lam.shape) != (B,) or not dev(lam):
+            raise ValueError("lm_net_amd.%s: lam must be a contiguous fp32 device tensor [%d]" % (what, B))
+    else:
+        want = {SOFT_PROBS: torch.float32, SOFT_TEACHER_F32: torch.float32, SOFT_TEACHER_BF16: torch.bfloat16}.get(reader)
+        if want is None:
+            raise ValueError("lm_net_amd.%s: unknown reader %r" % (what, reader))
+        if target is None or target.dtype != want or tuple(target.shape) != full or not dev(target):
+            raise ValueError("lm_net_amd.%s: reader %d takes a contiguous %s device target %s" % (what, reader, want, full))
+        if yb is not None or lam is not None or (reader == SOFT_PROBS and ya is not None):
+            raise ValueError("lm_net_amd.%s: reader %d takes neither yb nor lam (and the probability reader no label map)" % (what, reader))
+        if ya is not None and (tuple(ya.shape) != lab or not dev(ya)):
+            raise ValueError("lm_net_amd.%s: the valid map %s, expected a contiguous device tensor %s" % (what, tuple(ya.shape), lab))
+    return B, Cn, H, W, (SOFT_LABELS_U8 if ya is None else label_kind(ya))
+
+
+def _vp(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def soft_fwd(logits, reader, head, target, ya, yb, lam, temperature, eps, smooth, ce_scale, dice_scale, w_ce, w_dice, workspace, sums,
+             counts, coef, terms):
+    """terms[0:3] = the soft-target loss and its terms (lmn_soft_fwd) of fp32 logits [B, C, H, W].  reader SOFT_PROBS: target fp32 q
+    [B, C, H, W]; SOFT_PAIR: label maps ya, yb [B, H, W] and lam fp32 [B]; SOFT_TEACHER_F32 / _BF16: target the teacher's logits, ya
+    an optional valid map (a label map under SOFT_SOFTMAX, planes under SOFT_SIGMOID), ce_scale the factor of the term.  sums fp32
+    [1 + 3 C], counts int32 [1], coef fp32 [1 + 2 C] (read by soft_bwd), terms fp32 [3]; w_ce / w_dice fp32 [C] or None; workspace
+    uint8 of at least soft_workspace(...) bytes (None outside deterministic mode)."""
+    B, Cn, H, W, kind = _soft_args("soft_fwd", logits, reader, head, target, ya, yb, lam)
+    if sums.numel() != 1 + 3 * Cn or counts.numel() != 1 or coef.numel() != 1 + 2 * Cn or terms.numel() != 3:
+        raise ValueError("lm_net_amd.soft_fwd: sums %d / counts %d / coef %d / terms %d values, expected %d / 1 / %d / 3"
+                         % (sums.numel(), counts.numel(), coef.numel(), terms.numel(), 1 + 3 * Cn, 1 + 2 * Cn))
+    for w in (w_ce, w_dice):
+        if w is not None and w.numel() != Cn:
+            raise ValueError("lm_net_amd.soft_fwd: a class weight holds %d values for %d classes" % (w.numel(), Cn))
+    f32 = torch.float32
+    _check(load().lmn_soft_fwd(_p(logits), int(reader), int(head), _vp(target), _vp(ya), _vp(yb), kind, _raw(lam, f32, "soft_fwd"),
+                               _f(temperature), _f(eps), _f(smooth), _f(ce_scale), _f(dice_scale), B, Cn, H, W, _raw(w_ce, f32, "soft_fwd"),
+                               _raw(w_dice, f32, "soft_fwd"), _raw(workspace, torch.uint8, "soft_fwd"),
+                               _i64(0 if workspace is None else workspace.numel()), _raw(sums, f32, "soft_fwd"),
+                               _raw(counts, torch.int32, "soft_fwd"), _raw(coef, f32, "soft_fwd"), _raw(terms, f32, "soft_fwd"), _stream()),
+           "soft_fwd")
+
+
+def soft_bwd(logits, reader, head, target, ya, yb, lam, temperature, eps, w_ce, coef, gscale, dlogits):
+    """dlogits = gscale[0] * d loss / d logits (gscale None: 1) from the coef of soft_fwd on the same arguments (lmn_soft_bwd); every
+    element of dlogits is written."""
+    B, Cn, H, W, kind = _soft_args("soft_bwd", logits, reader, head, target, ya, yb, lam)
+    if tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous() or coef.numel() != 1 + 2 * Cn:
+        raise ValueError("lm_net_amd.soft_bwd: dlogits needs the logits' shape and coef %d values" % (1 + 2 * Cn))
+    f32 = torch.float32
+    _check(load().lmn_soft_bwd(_p(logits), int(reader), int(head), _vp(target), _vp(ya), _vp(yb), kind, _raw(lam, f32, "soft_bwd"),
+                               _f(temperature), _f(eps), B, Cn, H, W, _raw(w_ce, f32, "soft_bwd"), _raw(coef, f32, "soft_bwd"), _p(gscale),
+                               _p(dlogits), _stream()), "soft_bwd")
+
+
+def mix_rows(partner, mode, lam, boxes):
+    """The host table of lmn_mix_batch: int32 [B, MIX_ROW_WORDS] = partner, mode, lam, 1 - lam (both as fp32 bits; the difference is
+    formed in fp32 here, on the host), y0, x0, y1, x1."""
+    lam = np.asarray(lam, dtype=np.float32).reshape(-1)
+    rows = np.zeros((lam.size, MIX_ROW_WORDS), dtype=np.int32)
+    rows[:, 0], rows[:, 1] = np.asarray(partner, dtype=np.int32), np.asarray(mode, dtype=np.int32)
+    rows[:, 2], rows[:, 3] = lam.view(np.int32), (np.float32(1.0) - lam).astype(np.float32).view(np.int32)
+    rows[:, 4:] = np.asarray(boxes, dtype=np.int32).reshape(lam.size, 4)
+    return rows
+
+
+def mix_batch(x, y, rows, rows_dev, x_out, ya_out, yb_out, lam_out):
+    """Mixup / CutMix of a device batch through lmn_mix_batch: x fp32 [B, Cin, H, W] and y uint8 / int64 [B, H, W] -> x_out, ya_out,
+    yb_out (None when no row is a mixup row) and lam_out fp32 [B], out of place.  rows: the host table of mix_rows; rows_dev: int32
+    device tensor [B, MIX_ROW_WORDS] that receives it."""
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("lm_net_amd.mix_batch: contiguous x [B, Cin, H, W] required, got %s" % (tuple(x.shape),))
+    B, Cin, H, W = x.shape
+    rows = np.ascontiguousarray(rows, dtype=np.int32)            # (kept alive across the call)
+    labels = [t for t in (y, ya_out, yb_out) if t is not None]
+    if (tuple(rows.shape) != (B, MIX_ROW_WORDS) or rows_dev.numel() != B * MIX_ROW_WORDS or tuple(x_out.shape) != tuple(x.shape)
+            or not x_out.is_contiguous() or lam_out.numel() != B or y is None or ya_out is None
+            or any(tuple(t.shape) != (B, H, W) or t.dtype != y.dtype or not t.is_cuda or not t.is_contiguous() for t in labels)):
+        raise ValueError("lm_net_amd.mix_batch: tensor sizes or types do not match B=%d, %d channel(s), %dx%d" % (B, Cin, H, W))
+    _check(load().lmn_mix_batch(_p(x), _vp(y), label_kind(y), rows.ctypes.data_as(C.POINTER(C.c_int32)), _raw(rows_dev, torch.int32, "mix_batch"),
+                                B, Cin, H, W, _p(x_out), _vp(ya_out), _vp(yb_out), _p(lam_out), _stream()), "mix_batch")
 
 
 def slices_workspace(M, D, Hs, Ws):

@@ -18,6 +18,8 @@ a valid pixel gives ``0`` for the cross-entropy and focal terms (torch: NaN) and
 destroy the parameters of a loop that never synchronises.  Parity with torchvision's own ``sigmoid_focal_loss`` is not pinned by the
 tests (torchvision is not a dependency); its documented formula is.
 """
+import collections
+
 import torch
 
 from . import hip
@@ -772,3 +774,213 @@ def region_sums(logits, target, n_classes, head="softmax", classes=None, per_ima
     hip.region_fwd(logits, target, _REGION_HEADS[head], hip.REGION_DICE, hip.REGION_SQUARED, bool(per_image), 0.5, 0.5, 1e-5, 1.0, 1.0, mask,
                    None, ws, sums, counts, coef, per_class, loss)
     return sums, counts
+
+
+# ------------------------------------------------------------------------------------------------------------------------ soft targets
+# Criteria that read a distribution per pixel (include/soft/lmnet_soft.h): cross entropy + Dice against probabilities or against the
+# two-hot target of a Mixup batch, and the distillation term against a teacher's logits.  One sums pass over logits and target, a
+# one-block finish in fp64, one pointwise backward.
+_SOFT_HEADS = {"softmax": hip.SOFT_SOFTMAX, "sigmoid": hip.SOFT_SIGMOID}
+
+
+class MixedTarget(collections.namedtuple("MixedTarget", ("ya", "yb", "lam"))):
+    """The target of a ``DeviceMix`` batch: two label maps ``[B, H, W]`` of one type and ``lam`` fp32 ``[B]`` on the device, standing
+    for ``q = lam onehot(ya) + (1 - lam) onehot(yb)``.  ``SoftSegLoss`` takes it as it is.  ``labels`` is the hard label map ``ya`` for
+    the criteria that read integer labels -- it exists only when the ``DeviceMix`` that made the target cannot draw Mixup
+    (``mixup_alpha == 0``: CutMix pastes labels with the pixels, so ``ya == yb`` and ``lam == 1``); otherwise it raises."""
+
+    hard = False        # set by DeviceMix on the targets of a mixer that cannot draw Mixup
+
+    @property
+    def labels(self):
+        if not self.hard:
+            raise ValueError("MixedTarget.labels: the DeviceMix that made this target can draw Mixup (mixup_alpha > 0), so there is no "
+                             "hard label map; pass the target to SoftSegLoss")
+        return self.ya
+
+
+def _soft_limits(what):
+    def limits(B, Cn, H, W):
+        _check_elements(what, B, Cn, H, W)
+        if B > hip.SOFT_MAX_BATCH:
+            raise ValueError("%s: B = %d above the limit %d" % (what, B, hip.SOFT_MAX_BATCH))
+    return limits
+
+
+def _soft_logits(what, n_classes, logits):
+    """The checks of _check_pair on the logits alone, in its words -> (B, C, H, W)."""
+    if logits.dim() != 4 or logits.shape[1] != n_classes or not logits.is_floating_point():
+        raise ValueError("%s: logits must be floating point [B, %d, H, W], got %s %s" % (what, n_classes, logits.dtype, tuple(logits.shape)))
+    _soft_limits(what)(*logits.shape)
+    return tuple(logits.shape)
+
+
+def _soft_label_map(what, logits, target):
+    """The checks of _check_pair on a label map under a softmax head, in its words, without the device test."""
+    if not torch.is_tensor(target) or target.dtype not in (torch.uint8, torch.int64, torch.bool):
+        raise ValueError("%s: target must be uint8, bool or int64, got %s" % (what, getattr(target, "dtype", type(target).__name__)))
+    shape = tuple(target.shape[:1] + target.shape[2:]) if target.dim() == 4 and target.shape[1] == 1 else tuple(target.shape)
+    if shape != (logits.shape[0],) + tuple(logits.shape[2:]):
+        raise ValueError("%s: target %s does not match logits %s under a softmax head" % (what, tuple(target.shape), tuple(logits.shape)))
+
+
+def _soft_float_target(what, head, logits, target, name):
+    if tuple(target.shape) != tuple(logits.shape):
+        raise ValueError("%s: %s %s does not match logits %s under a %s head" % (what, name, tuple(target.shape), tuple(logits.shape), head))
+    if not logits.is_cuda or not target.is_cuda:
+        raise RuntimeError("lm_net_amd.%s: device tensors required (the HIP path has no CPU fallback)" % what)
+
+
+class _SoftFn(torch.autograd.Function):
+    """The loss entries of include/soft/lmnet_soft.h.  cfg = (reader, head, target, ya, yb, lam, temperature, eps, smooth, ce_scale,
+    dice_scale, w_ce, w_dice, (workspace, sums, counts), holder); `holder.terms` receives the device tensor of the three terms."""
+
+    @staticmethod
+    def forward(ctx, logits, cfg):
+        reader, head, target, ya, yb, lam, T, eps, smooth, ce_scale, dice_scale, w_ce, w_dice, (ws, sums, counts), holder = cfg
+        coef = torch.empty(1 + 2 * logits.shape[1], device=logits.device)
+        terms = torch.empty(3, device=logits.device)
+        hip.soft_fwd(logits, reader, head, target, ya, yb, lam, T, eps, smooth, ce_scale, dice_scale, w_ce, w_dice, ws, sums, counts, coef, terms)
+        ctx.save_for_backward(logits, coef)
+        ctx.cfg = (reader, head, target, ya, yb, lam, T, eps, w_ce)
+        holder.terms = terms
+        return terms[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, coef = ctx.saved_tensors
+        reader, head, target, ya, yb, lam, T, eps, w_ce = ctx.cfg
+        d = torch.empty_like(logits)
+        hip.soft_bwd(logits, reader, head, target, ya, yb, lam, T, eps, w_ce, coef, g.reshape(1).contiguous().float(), d)
+        return d, None
+
+
+def _soft_buffers(device, readers, head, B, Cn, H, W):
+    """The scratch of one geometry: workspace (the deterministic-mode slots, sized for every reader of the criterion), sums, counts."""
+    ws = max(hip.soft_workspace(r, _SOFT_HEADS[head], B, Cn, H, W) for r in readers)
+    return (torch.empty(ws, device=device, dtype=torch.uint8), torch.empty(1 + 3 * Cn, device=device),
+            torch.empty(1, device=device, dtype=torch.int32))
+
+
+class SoftSegLoss(torch.nn.Module):
+    """``SegLoss`` against a distribution per pixel: ``ce_scale * F.cross_entropy(logits, q, weight=ce_weight, label_smoothing) +
+    dice_scale *`` the reference's ``DiceLoss`` on the float target ``q`` (``utils/loss.py:183-206``: ``1 - (2 sum p q + s) /
+    (sum p^2 + sum q^2 + s)`` per class, weighted by ``dice_weight`` and averaged over the classes; ``q`` enters the Dice term unsmoothed).
+
+    ``target`` is a float tensor ``q`` ``[B, C, H, W]``, used as given (not renormalised, as torch), or a ``MixedTarget`` of
+    ``DeviceMix``, the two-hot ``q = lam onehot(ya) + (1 - lam) onehot(yb)`` that is never materialised.  A pixel is void when any
+    ``q_c`` is negative or not finite (fill a void pixel with NaN or -1), or when one of the two labels lies outside ``[0, C)``.  Torch's
+    probability-target cross entropy divides by the pixel count, not by the weight sum, so with non-unit weights the cross-entropy term
+    differs from the index-target ``SegLoss`` by that normalisation, on purpose; with unit weights and a one-hot ``q`` the two agree.
+    ``None`` weights mean all ones.  ``ce_scale`` / ``dice_scale`` are plain attributes read at every call.  ``terms`` holds the
+    device tensor ``[total, ce, dice]`` of the last call and ``counts`` the int32 device tensor ``[N]`` of its valid pixels (overwritten
+    by the next call of the geometry); nothing synchronises.  Softmax heads only, 2 .. 64 classes, fp32 logits.
+    Device tensors only; the scratch of a geometry is kept and the per-call tensors come from torch's caching allocator, so nothing
+    is allocated on the device after the first call of a geometry; the scratch is per geometry, not per stream.
+    Deliberate difference from torch: without a valid pixel every term is 0 with a zero gradient, never NaN; every void position has
+    gradient +0; a Dice denominator that is exactly 0 gives a ratio of 1.  Limits: B <= 65535, B * C * H * W < 2^31.
+    Out of scope: a soft BCE under sigmoid heads (``SigmoidSegLoss`` keeps refusing float targets: mix the planes in torch),
+    per-image Dice, bf16 probability targets."""
+
+    def __init__(self, n_classes, ce_weight=None, dice_weight=None, label_smoothing=0.0, smooth=1e-5, ce_scale=1.0, dice_scale=1.0):
+        super().__init__()
+        _check_head("SoftSegLoss", "softmax", n_classes)
+        if not 0.0 <= label_smoothing <= 1.0:
+            raise ValueError("SoftSegLoss: label_smoothing = %r outside [0, 1]" % (label_smoothing,))
+        if not 0.0 <= smooth < float("inf"):
+            raise ValueError("SoftSegLoss: smooth = %r must be finite and >= 0" % (smooth,))
+        for name, w in (("ce_weight", ce_weight), ("dice_weight", dice_weight)):
+            if w is not None:
+                w = torch.as_tensor(w, dtype=torch.float32).reshape(-1).clone()
+                if w.numel() != n_classes or not bool(torch.isfinite(w).all()):
+                    raise ValueError("SoftSegLoss: %s needs %d finite values, one per class" % (name, n_classes))
+            self.register_buffer(name, w)
+        self.n_classes, self.label_smoothing, self.smooth = int(n_classes), float(label_smoothing), float(smooth)
+        self.ce_scale, self.dice_scale = float(ce_scale), float(dice_scale)
+        self.terms = self.counts = None
+        self._scratch = {}
+
+    def forward(self, logits, target):
+        what = "SoftSegLoss"
+        _check_scale(what, self.ce_scale)
+        _check_scale(what, self.dice_scale)
+        ya = yb = lam = q = None
+        if isinstance(target, MixedTarget):
+            _soft_logits(what, self.n_classes, logits)
+            for t in (target.ya, target.yb):               # both maps, before the device of either is looked at
+                _soft_label_map(what, logits, t)
+            logits, ya = _check_pair(what, self.n_classes, "softmax", logits, target.ya, True, _soft_limits(what))
+            _, yb = _check_pair(what, self.n_classes, "softmax", logits, target.yb, True, _soft_limits(what))
+            lam = target.lam
+            if ya.dtype != yb.dtype:
+                raise ValueError("%s: the two label maps of a MixedTarget must share a type, got %s and %s" % (what, ya.dtype, yb.dtype))
+            if not torch.is_tensor(lam) or lam.dtype != torch.float32 or tuple(lam.shape) != (logits.shape[0],) or not lam.is_cuda:
+                raise ValueError("%s: lam of a MixedTarget must be an fp32 device tensor [%d]" % (what, logits.shape[0]))
+            reader, lam = hip.SOFT_PAIR, lam.contiguous()
+        else:
+            _soft_logits(what, self.n_classes, logits)
+            if not torch.is_tensor(target) or not target.is_floating_point():
+                raise ValueError("%s: target must be a floating-point tensor [B, C, H, W] or a MixedTarget, got %s"
+                                 % (what, target.dtype if torch.is_tensor(target) else type(target).__name__))
+            if target.dtype != torch.float32:
+                raise ValueError("%s: the probability target must be fp32, got %s (bf16 probability targets are out of scope)" % (what, target.dtype))
+            _soft_float_target(what, "softmax", logits, target, "target")
+            reader, logits, q = hip.SOFT_PROBS, logits.float().contiguous(), target.detach().contiguous()
+        B, Cn, H, W = logits.shape
+        buf = _scratch(self, logits, lambda: _soft_buffers(logits.device, (hip.SOFT_PROBS, hip.SOFT_PAIR), "softmax", B, Cn, H, W))
+        for name in ("ce_weight", "dice_weight"):
+            w = getattr(self, name)
+            if w is not None and w.device != logits.device:
+                setattr(self, name, w.to(logits.device))
+        self.counts = buf[2]
+        cfg = (reader, hip.SOFT_SOFTMAX, q, ya, yb, lam, 1.0, self.label_smoothing, self.smooth, self.ce_scale, self.dice_scale, self.ce_weight,
+               self.dice_weight, buf, self)
+        return _SoftFn.apply(logits, cfg)
+
+
+class DistillLoss(torch.nn.Module):
+    """The distillation term of Hinton et al. (2015): ``scale * T^2 / N * sum KL(q || p)`` with ``q = softmax(teacher / T)``,
+    ``p = softmax(logits / T)`` over the N valid pixels, or, with ``head="sigmoid"``, the Bernoulli divergence of
+    ``q = sigmoid(teacher / T)`` from ``p = sigmoid(logits / T)`` over the N valid elements.  A per-pixel mean, so the scale does not
+    depend on the image size; torch's ``batchmean`` is not reproduced.
+
+    ``forward(logits, teacher_logits, valid=None)``: the teacher is fp32 or bf16 ``[B, C, H, W]`` (read as it is stored), detached, and
+    gets no gradient.  ``valid`` is the batch's own target: a uint8 / int64 label map ``[B, H, W]`` under a softmax head (a pixel counts
+    when its label lies in ``[0, C)``), target planes ``[B, C, H, W]`` under a sigmoid head (an element counts when its value is 0 or
+    1); ``None`` counts everything.  ``scale`` is a plain attribute read at every call, so ``seg(l, y) + kd(l, teacher(x), y)`` is
+    Hinton's recipe with the void pixels excluded.  ``log q`` and ``log p`` come from one device routine: a teacher whose logits equal
+    the student's bit for bit gives exactly 0 and an all-zero gradient, and logits of +-100 stay finite.  ``terms`` holds the device
+    tensor ``[scale * kd, kd, 0]`` of the last call and ``counts`` the int32 device tensor ``[N]``; nothing synchronises.  Device tensors only; the scratch of a geometry is kept and
+    the per-call tensors come from torch's caching allocator; the scratch is per geometry, not per stream.
+    Deliberate difference from torch: without a valid pixel the term is 0 with a zero gradient, never NaN, and every void position has
+    gradient +0.  Limits: 1 .. 64 classes (softmax: from 2), B <= 65535, B * C * H * W < 2^31.  Out of scope: Dice against the teacher."""
+
+    def __init__(self, n_classes, temperature=1.0, head="softmax", scale=1.0):
+        super().__init__()
+        _check_head("DistillLoss", head, n_classes)
+        if not 0.0 < float(temperature) < float("inf"):
+            raise ValueError("DistillLoss: temperature = %r must be finite and > 0" % (temperature,))
+        self.n_classes, self.head, self.temperature = int(n_classes), head, float(temperature)
+        self.scale = float(scale)
+        self.terms = self.counts = None
+        self._scratch = {}
+
+    def forward(self, logits, teacher_logits, valid=None):
+        what = "DistillLoss"
+        _check_scale(what, self.scale)
+        if valid is not None:
+            logits, valid = _check_pair(what, self.n_classes, self.head, logits, valid, True, _soft_limits(what))
+        else:
+            _soft_logits(what, self.n_classes, logits)
+        if not torch.is_tensor(teacher_logits) or not teacher_logits.is_floating_point():
+            raise ValueError("%s: teacher_logits must be a floating-point tensor [B, C, H, W]" % what)
+        _soft_float_target(what, self.head, logits, teacher_logits, "teacher_logits")
+        logits = logits.float().contiguous()
+        teacher = teacher_logits.detach()
+        teacher = (teacher if teacher.dtype == torch.bfloat16 else teacher.float()).contiguous()
+        reader = hip.SOFT_TEACHER_BF16 if teacher.dtype == torch.bfloat16 else hip.SOFT_TEACHER_F32
+        B, Cn, H, W = logits.shape
+        buf = _scratch(self, logits, lambda: _soft_buffers(logits.device, (hip.SOFT_TEACHER_F32, hip.SOFT_TEACHER_BF16), self.head, B, Cn, H, W))
+        self.counts = buf[2]
+        cfg = (reader, _SOFT_HEADS[self.head], teacher, valid, None, None, self.temperature, 0.0, 0.0, self.scale, 0.0, None, None, buf, self)
+        return _SoftFn.apply(logits, cfg)
