@@ -15,6 +15,8 @@ segmented device sort; ``lm_net_amd.loss.lovasz_ranks``),
 pass; ``lm_net_amd.loss.region_sums``),
 ``lm_net_amd.loss.SoftSegLoss`` / ``DistillLoss`` (cross entropy + Dice against a distribution per pixel and the distillation term
 against a teacher's logits) with ``lm_net_amd.data.DeviceMix`` (Mixup / CutMix of a device batch; ``MixedTarget``),
+``lm_net_amd.loss.HardPixelLoss`` (top-k and OHEM cross entropy: the hardest pixels only, selected by an exact device radix select
+with the count formed on the device; ``lm_net_amd.loss.hard_pixel_values``),
 ``lm_net_amd.optim.FusedAdamW`` (one-launch AdamW; parameter groups, gradient clipping, the GradScaler skip and an EMA of the weights
 without a host decision; ``lm_net_amd.optim.decay_groups``), ``lm_net_amd.metrics.ConfusionMeter`` (on-device Dice / IoU),
 ``lm_net_amd.metrics.SurfaceDistanceMeter`` (on-device HD / HD95 / ASSD / RVD),
@@ -30,11 +32,12 @@ volume, cavity filling, between the prediction and ``VolumeSurfaceMeter``),
 """
 from .LM_Net import LM_Net  # noqa: F401
 from .data import DeviceMix, VolumeSlicer  # noqa: F401
-from .loss import (BoundaryLoss, DistillLoss, FocalLoss, HausdorffDTLoss, LovaszLoss, MixedTarget, RegionLoss, SegLoss,  # noqa: F401
-                   SigmoidSegLoss, SoftSegLoss, distance_maps, lovasz_ranks, region_sums)
+from .loss import (BoundaryLoss, DistillLoss, FocalLoss, HardPixelLoss, HausdorffDTLoss, LovaszLoss, MixedTarget, RegionLoss,  # noqa: F401
+                   SegLoss, SigmoidSegLoss, SoftSegLoss, distance_maps, hard_pixel_values, lovasz_ranks, region_sums)
 from .metrics import CurveMeter, ImageStatsMeter, LesionMeter, SigmoidStatsMeter, VolumeSurfaceMeter  # noqa: F401
 from .post import VolumePostprocess  # noqa: F401
 
 __all__ = ["LM_Net", "SegLoss", "FocalLoss", "ImageStatsMeter", "SigmoidSegLoss", "SigmoidStatsMeter", "CurveMeter", "VolumeSurfaceMeter", "VolumePostprocess",
            "LesionMeter", "BoundaryLoss", "HausdorffDTLoss", "distance_maps", "LovaszLoss", "lovasz_ranks", "RegionLoss",
-           "region_sums", "VolumeSlicer", "SoftSegLoss", "DistillLoss", "MixedTarget", "DeviceMix"]
+           "region_sums", "VolumeSlicer", "SoftSegLoss", "DistillLoss", "MixedTarget", "DeviceMix",
+           "HardPixelLoss", "hard_pixel_values"]

@@ -415,6 +415,20 @@ MIX_MIXUP = 1
 MIX_CUTMIX = 2
 MIX_ROW_WORDS = 8
 
+# include/hard/lmnet_hard.h: the hard-pixel criterion -- top-k and OHEM cross entropy on an exact device radix select
+# (lm_net_amd.loss.HardPixelLoss, hard_pixel_values).  A list of its own for the same reason, and no struct; tests/test_hard_cpu.py
+# checks it against the header and ties the two device entries to tests/test_guard_hard_gpu.py.
+SYMBOLS_HARD = ["lmn_hard_workspace", "lmn_hard_fwd", "lmn_hard_bwd"]
+HARD_SOFTMAX = 0             # LMN_HARD_* of the header
+HARD_SIGMOID = 1
+HARD_LABELS_U8 = 0
+HARD_LABELS_I64 = 1
+HARD_MAX_BATCH = 65535
+HARD_MAX_GROUPS = 1024
+HARD_RECORD_WORDS = 5
+HARD_BINS_HIGH = 2048
+HARD_BINS_LOW = 1024
+
 _lib = None
 
 
@@ -428,7 +442,7 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ + SYMBOLS_REGION + SYMBOLS_SLICES + SYMBOLS_SOFT:
+    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ + SYMBOLS_REGION + SYMBOLS_SLICES + SYMBOLS_SOFT + SYMBOLS_HARD:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
     lib.lmn_last_error.restype = C.c_char_p
@@ -447,6 +461,14 @@ def load():
     lib.lmn_region_workspace.restype = C.c_int64
     lib.lmn_slices_workspace.restype = C.c_int64
     lib.lmn_soft_workspace.restype = C.c_int64
+    lib.lmn_hard_workspace.restype = C.c_int64
+    # (the only entries with a 64-bit integer or a float ahead of the pointer block: declared, so that a Python int cannot be cut)
+    vp, ci, cf = C.c_void_p, C.c_int, C.c_float
+    lib.lmn_hard_workspace.argtypes = [ci] * 6
+    lib.lmn_hard_fwd.restype = ci
+    lib.lmn_hard_fwd.argtypes = [vp, vp, ci, ci, ci, cf, C.c_int64, cf, cf, ci, ci, ci, ci, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.lmn_hard_bwd.restype = ci
+    lib.lmn_hard_bwd.argtypes = [vp, vp, ci, ci, ci, cf, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     lib.lmn_plan_create.restype = C.c_void_p
     lib.lmn_plan_record_end.restype = C.c_int64
     lib.lmn_plan_size.restype = C.c_int64
@@ -1842,6 +1864,57 @@ def soft_bwd(logits, reader, head, target, ya, yb, lam, temperature, eps, w_ce, 
     _check(load().lmn_soft_bwd(_p(logits), int(reader), int(head), _vp(target), _vp(ya), _vp(yb), kind, _raw(lam, f32, "soft_bwd"),
                                _f(temperature), _f(eps), B, Cn, H, W, _raw(w_ce, f32, "soft_bwd"), _raw(coef, f32, "soft_bwd"), _p(gscale),
                                _p(dlogits), _stream()), "soft_bwd")
+
+
+def hard_workspace(head, per_image, B, Cn, H, W):
+    """Bytes of the histograms, counts and slots of lmn_hard_fwd, exactly (host arithmetic, no GPU)."""
+    return _host_size("hard_workspace", load().lmn_hard_workspace(int(head), int(bool(per_image)), int(B), int(Cn), int(H), int(W)))
+
+
+def hard_cut(thresh):
+    """The fp32 value cut of a probability threshold: float32(-log(thresh)), the logarithm taken in double; -1 (not given) for None."""
+    if thresh is None:
+        return -1.0
+    return float(np.float32(-np.log(np.float64(thresh)))) + 0.0
+
+
+def _hard_dims(what, logits, target, head, per_image, weight, values, selection):
+    B, Cn, H, W = _loss_dims(what, logits, target, head == HARD_SOFTMAX)
+    G = B if per_image else 1
+    want = (B, H, W) if head == HARD_SOFTMAX else (B, Cn, H, W)
+    if tuple(values.shape) != want or not values.is_contiguous() or tuple(selection.shape) != (G, HARD_RECORD_WORDS):
+        raise ValueError("lm_net_amd.%s: values %s / selection %s do not hold %s / [%d, %d]"
+                         % (what, tuple(values.shape), tuple(selection.shape), want, G, HARD_RECORD_WORDS))
+    if weight is not None and weight.numel() != Cn:
+        raise ValueError("lm_net_amd.%s: weight holds %d values for %d classes" % (what, weight.numel(), Cn))
+    return B, Cn, H, W, G
+
+
+def hard_fwd(logits, target, head, per_image, keep, min_kept, cut, scale, weight, workspace, values, selection, terms, loss):
+    """loss[0] = the hard-pixel loss (lmn_hard_fwd) of fp32 logits [B, C, H, W] under HARD_SOFTMAX (target a label map [B, H, W]) or
+    HARD_SIGMOID (target planes [B, C, H, W]).  keep in [0, 1] (0: not given), min_kept >= 0, cut = hard_cut(thresh).  With G = B
+    (per_image) or 1: values fp32 [B, H, W] (sigmoid: [B, C, H, W]; -1 at a void element), selection int32 [G, HARD_RECORD_WORDS]
+    (N, K, n_gt, n_eq, the bits of tau), terms fp32 [G]; weight fp32 [C] or None; workspace uint8 of at least hard_workspace(...)
+    bytes."""
+    B, Cn, H, W, G = _hard_dims("hard_fwd", logits, target, head, per_image, weight, values, selection)
+    if terms.numel() != G or loss.numel() < 1:
+        raise ValueError("lm_net_amd.hard_fwd: terms needs %d floats and loss one" % G)
+    _check(load().lmn_hard_fwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), int(bool(per_image)), float(keep),
+                               int(min_kept), float(cut), float(scale), B, Cn, H, W, _raw(weight, torch.float32, "hard_fwd"),
+                               _raw(workspace, torch.uint8, "hard_fwd"), workspace.numel(), _raw(values, torch.float32, "hard_fwd"),
+                               _raw(selection, torch.int32, "hard_fwd"), _raw(terms, torch.float32, "hard_fwd"), _p(loss), _stream()),
+           "hard_fwd")
+
+
+def hard_bwd(logits, target, head, per_image, scale, weight, values, selection, gscale, dlogits):
+    """dlogits = gscale[0] * d loss / d logits (gscale None: 1) from the values and the selection of hard_fwd on the same arguments
+    (lmn_hard_bwd); every element of dlogits is written."""
+    B, Cn, H, W, G = _hard_dims("hard_bwd", logits, target, head, per_image, weight, values, selection)
+    if tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous():
+        raise ValueError("lm_net_amd.hard_bwd: dlogits needs the logits' shape")
+    _check(load().lmn_hard_bwd(_p(logits), C.c_void_p(target.data_ptr()), label_kind(target), int(head), int(bool(per_image)), float(scale),
+                               B, Cn, H, W, _raw(weight, torch.float32, "hard_bwd"), _raw(values, torch.float32, "hard_bwd"),
+                               _raw(selection, torch.int32, "hard_bwd"), _p(gscale), _p(dlogits), _stream()), "hard_bwd")
 
 
 def mix_rows(partner, mode, lam, boxes):

@@ -984,3 +984,148 @@ class DistillLoss(torch.nn.Module):
         self.counts = buf[2]
         cfg = (reader, _SOFT_HEADS[self.head], teacher, valid, None, None, self.temperature, 0.0, 0.0, self.scale, 0.0, None, None, buf, self)
         return _SoftFn.apply(logits, cfg)
+
+
+# ------------------------------------------------------------------------------------------------------------------------ hard pixels
+# Top-k and OHEM cross entropy (include/hard/lmnet_hard.h): a values pass over logits and target, an exact three-level radix select of
+# the K-th largest value with K formed on the device, a sum pass, a one-block finish in fp64, one pointwise backward.
+_HARD_HEADS = {"softmax": hip.HARD_SOFTMAX, "sigmoid": hip.HARD_SIGMOID}
+
+
+def _hard_config(what, n_classes, head, keep, min_kept, thresh, weight):
+    """(keep or 0.0, min_kept, thresh, weight tensor or None) of the constructor arguments."""
+    _check_head(what, head, n_classes)
+    if keep is not None and not 0.0 < float(keep) <= 1.0:
+        raise ValueError("%s: keep = %r outside (0, 1]" % (what, keep))
+    if isinstance(min_kept, bool) or int(min_kept) != min_kept or not 0 <= min_kept < 1 << 62:
+        raise ValueError("%s: min_kept = %r must be an integer >= 0" % (what, min_kept))
+    if thresh is not None and not 0.0 < float(thresh) <= 1.0:
+        raise ValueError("%s: thresh = %r outside (0, 1]" % (what, thresh))
+    if keep is None and thresh is None and min_kept == 0:
+        raise ValueError("%s: one of keep, min_kept > 0 and thresh must be given" % what)
+    if weight is not None:
+        weight = torch.as_tensor(weight, dtype=torch.float32).reshape(-1).clone()
+        if weight.numel() != n_classes or not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+            raise ValueError("%s: weight needs %d finite values >= 0, one per class" % (what, n_classes))
+    return (0.0 if keep is None else float(keep)), int(min_kept), (None if thresh is None else float(thresh)), weight
+
+
+def _hard_check(what, n_classes, head, per_image, logits, target):
+    def limits(B, Cn, H, W):
+        _check_elements(what, B, Cn, H, W)
+        if B > hip.HARD_MAX_BATCH:
+            raise ValueError("%s: B = %d above the limit %d" % (what, B, hip.HARD_MAX_BATCH))
+        if per_image and B > hip.HARD_MAX_GROUPS:
+            raise ValueError("%s: per_image: B = %d groups above the limit %d" % (what, B, hip.HARD_MAX_GROUPS))
+    return _check_pair(what, n_classes, head, logits, target, True, limits)
+
+
+def _hard_workspace(device, head, per_image, B, Cn, H, W):
+    """The scratch of one geometry: the histograms, counts and slots."""
+    return torch.empty(hip.hard_workspace(_HARD_HEADS[head], per_image, B, Cn, H, W), device=device, dtype=torch.uint8)
+
+
+def _hard_outputs(logits, head, per_image):
+    """The per-call tensors: values, selection, terms, loss."""
+    B, Cn, H, W = logits.shape
+    G = B if per_image else 1
+    return (torch.empty((B, H, W) if head == "softmax" else (B, Cn, H, W), device=logits.device),
+            torch.empty((G, hip.HARD_RECORD_WORDS), device=logits.device, dtype=torch.int32), torch.empty(G, device=logits.device),
+            torch.empty(1, device=logits.device))
+
+
+class _HardFn(torch.autograd.Function):
+    """The loss entries of include/hard/lmnet_hard.h.  cfg = (head, per_image, keep, min_kept, cut, scale, weight, workspace, holder);
+    `holder.selection`, `.values` and `.terms` receive the device tensors of the call."""
+
+    @staticmethod
+    def forward(ctx, logits, target, cfg):
+        head, per_image, keep, min_kept, cut, scale, weight, ws, holder = cfg
+        values, selection, terms, loss = _hard_outputs(logits, "softmax" if head == hip.HARD_SOFTMAX else "sigmoid", per_image)
+        hip.hard_fwd(logits, target, head, per_image, keep, min_kept, cut, scale, weight, ws, values, selection, terms, loss)
+        ctx.save_for_backward(logits, target, values, selection)
+        ctx.cfg = (head, per_image, scale, weight)
+        holder.selection, holder.values, holder.terms = selection, values, terms
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, values, selection = ctx.saved_tensors
+        head, per_image, scale, weight = ctx.cfg
+        d = torch.empty_like(logits)
+        hip.hard_bwd(logits, target, head, per_image, scale, weight, values, selection, g.reshape(1).contiguous().float(), d)
+        return d, None, None
+
+
+class HardPixelLoss(torch.nn.Module):
+    """The cross entropy of the hard pixels only: nnU-Net's ``TopKLoss`` (``keep``: the mean of the worst ``keep * N`` per-pixel
+    cross entropies) and OHEM, online hard example mining (``thresh``, ``min_kept``: every pixel whose true-class probability is
+    below ``thresh``, and at least ``min_kept`` pixels), with the count formed and the cutoff selected on the device.
+
+    An ELEMENT is a pixel under ``head="softmax"`` (2 .. 64 classes, an int64 / uint8 label map ``[B, H, W]``, ``[B, 1, H, W]``
+    accepted), with value ``l = weight[y] * (logsumexp(z) - z[y])`` and void when its label lies outside ``[0, C)``; under
+    ``head="sigmoid"`` (1 .. 64 planes, target planes ``[B, C, H, W]``, ``[B, H, W]`` at C = 1, of uint8 / bool / int64) it is a
+    (pixel, class) entry with ``l = weight[c] * BCE_with_logits(z, t)``, void when its target is neither 0 nor 1.  A GROUP is the
+    batch, or one image with ``per_image=True``; under a sigmoid head the classes of a group are pooled.  For a group with N valid
+    elements
+
+      ``K = min(N, max(1, floor(float32(keep) * N), min_kept, #{l > float32(-log(thresh))}))``
+
+    (an argument that is not given counts 0; ``floor(keep * N)`` is nnU-Net's ``int(n * k / 100)``), the group's term is the mean of
+    its K largest values -- exactly ``torch.topk(l, K).values.mean()`` -- and the loss is ``scale / G`` times the sum of the terms.
+    Ties: with ``tau`` the K-th largest value, ``n_gt`` the values above it and ``n_eq`` the values equal to it, an element above
+    ``tau`` has gradient weight ``1 / K`` and the tied elements at the cutoff share the rest, ``(K - n_gt) / (n_eq K)`` each, so the
+    result is a function of the inputs alone and equals torch whenever the cutoff is not tied.  Selection and sum both use the
+    WEIGHTED value: with class weights other than 1, ``thresh`` is no longer a pure probability threshold (it compares
+    ``weight * -log p`` with ``-log(thresh)``).  At least one of ``keep``, ``min_kept > 0`` and ``thresh`` must be given;
+    ``weight`` is ``None`` (all ones) or C finite values ``>= 0``.  ``scale`` is a plain attribute read at every call, so
+    ``RegionLoss(C, classes=range(1, C))(l, y) + HardPixelLoss(C, keep=0.1)(l, y)`` is nnU-Net's ``DC_and_topk_loss`` as it stands,
+    and ``HardPixelLoss(C, thresh=0.7, min_kept=100000)`` is the usual OHEM rule.
+
+    ``selection`` holds the device int32 tensor ``[G, 5]`` of the last call -- N, K, n_gt, n_eq and the bits of ``tau`` -- so the
+    kept fraction K / N can be logged without a synchronisation; ``values`` its per-element values (-1 at a void element) and
+    ``terms`` its per-group terms.  Device tensors only; nothing synchronises; the scratch of a geometry (histograms, counts, slots)
+    is kept and the per-call tensors (values, selection, terms, loss, gradient) come from torch's caching allocator, so nothing is
+    allocated on the device after the first call of a geometry.  The scratch is per geometry, not per stream: use from two streams
+    at once needs one HardPixelLoss object per stream.  No float atomics: loss, selection and gradient are bit-identical from call
+    to call in either deterministic mode.
+    Deliberate difference from torch: a group without a valid element contributes 0, the loss is never NaN for finite logits, and
+    every void position and every unselected element has gradient +0.  Parity with nnU-Net's or mmsegmentation's code is not pinned
+    by the tests (neither is a dependency); the formulas of ``include/hard/lmnet_hard.h`` are.
+    Limits: B <= 65535, B * C * H * W < 2^31, and with ``per_image`` at most 1024 images (every group owns three histograms of the
+    scratch)."""
+
+    def __init__(self, n_classes, head="softmax", keep=None, min_kept=0, thresh=None, weight=None, per_image=False, scale=1.0):
+        super().__init__()
+        self.keep, self.min_kept, self.thresh, weight = _hard_config("HardPixelLoss", n_classes, head, keep, min_kept, thresh, weight)
+        self.register_buffer("weight", weight)
+        self.n_classes, self.head, self.per_image = int(n_classes), head, bool(per_image)
+        self.scale = float(scale)
+        self.selection = self.values = self.terms = None
+        self._scratch = {}
+
+    def forward(self, logits, target):
+        _check_scale("HardPixelLoss", self.scale)
+        logits, target = _hard_check("HardPixelLoss", self.n_classes, self.head, self.per_image, logits, target)
+        B, Cn, H, W = logits.shape
+        ws = _scratch(self, logits, lambda: _hard_workspace(logits.device, self.head, self.per_image, B, Cn, H, W))
+        if self.weight is not None and self.weight.device != logits.device:
+            self.weight = self.weight.to(logits.device)
+        cfg = (_HARD_HEADS[self.head], self.per_image, self.keep, self.min_kept, hip.hard_cut(self.thresh), self.scale, self.weight, ws, self)
+        return _HardFn.apply(logits, target, cfg)
+
+
+def hard_pixel_values(logits, target, n_classes, head="softmax", weight=None, per_image=False, keep=None, min_kept=0, thresh=None):
+    """``(values, selection)`` of ``HardPixelLoss``: ``values`` fp32, the per-element value in the layout of the logits' elements
+    (``[B, H, W]`` under a softmax head), -1 at a void element, and ``selection`` int32 ``[G, 5]`` -- N, K, n_gt, n_eq and the bits
+    of the K-th largest value ``tau`` of every group -- for monitoring the kept fraction or the cutoff without a synchronisation.
+    The arguments are those of ``HardPixelLoss``; fresh tensors are returned.  Device tensors only; nothing synchronises."""
+    what = "hard_pixel_values"
+    keep, min_kept, thresh, weight = _hard_config(what, n_classes, head, keep, min_kept, thresh, weight)
+    logits, target = _hard_check(what, int(n_classes), head, bool(per_image), logits.detach(), target)
+    B, Cn, H, W = logits.shape
+    ws = _hard_workspace(logits.device, head, bool(per_image), B, Cn, H, W)
+    values, selection, terms, loss = _hard_outputs(logits, head, bool(per_image))
+    hip.hard_fwd(logits, target, _HARD_HEADS[head], bool(per_image), keep, min_kept, hip.hard_cut(thresh), 1.0,
+                 None if weight is None else weight.to(logits.device), ws, values, selection, terms, loss)
+    return values, selection
