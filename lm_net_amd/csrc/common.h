@@ -41,6 +41,8 @@ static inline int lmn_launch_status(const char* what) {
 static inline int lmn_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // workspace regions start at multiples of 256 bytes
 static inline int64_t lmn_up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+// p is a multiple of a (a power of two): the test ahead of every vectorised instance
+static inline bool lmn_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // ---------------------------------------------------------------- runtime hooks (runtime.hip)
 // (1) in-library kernel timer (lmn_prof_begin / lmn_prof_end): HIP events around every kernel launch whose name matches

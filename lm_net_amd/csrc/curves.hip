@@ -14,6 +14,7 @@
 #include "loss_common.h"
 #include "pred_common.h"
 #include "../../include/curves/lmnet_curves.h"
+static_assert(LMN_CURVE_T_U8 == LOSS_LABELS_U8 && LMN_CURVE_T_I64 == LOSS_LABELS_I64, "loss_common.h reads the target kinds of lmnet_curves.h");
 
 namespace {
 
@@ -48,16 +49,6 @@ __device__ __forceinline__ void cv_load_t(const void* __restrict__ t, int64_t i,
   for (int j = 0; j < E; ++j) {
     if constexpr (LABELS) out[j] = pred_in_range(v[j], C) ? (v[j] == (int64_t)c ? 1 : 0) : 2;
     else out[j] = (uint64_t)v[j] <= 1ull ? (int)v[j] : 2;
-  }
-}
-template <int E>
-__device__ __forceinline__ void cv_load_f(const float* __restrict__ p, int64_t i, float (&z)[E]) {
-  if constexpr (E == 4) {
-    const f32x4 v = ld4(p + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) z[j] = v[j];
-  } else {
-    z[0] = p[i];
   }
 }
 
@@ -104,8 +95,8 @@ __global__ __launch_bounds__(256) void curve_hist_kernel(const float* __restrict
 #pragma unroll
     for (int j = 0; j < E; ++j) { z[j] = 0.f; l[j] = 0.f; t[j] = 2; }
     if (in) {
-      cv_load_f<E>(vp, q * E, z);
-      if constexpr (SOFTMAX) cv_load_f<E>(lp, q * E, l);
+      loss_load_z<E>(vp, q * E, z);
+      if constexpr (SOFTMAX) loss_load_z<E>(lp, q * E, l);
       cv_load_t<KIND, LABELS, E>(tg, q * E, c, C, t);
     }
 #pragma unroll
@@ -146,36 +137,12 @@ __global__ __launch_bounds__(256) void curve_hist_kernel(const float* __restrict
   }
 }
 
-inline bool cv_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 int cv_check_sizes(const char* what, int score_kind, int B, int64_t HW) {
   LMN_REQUIRE(score_kind == LMN_CURVE_RAW || score_kind == LMN_CURVE_SOFTMAX, "%s: unknown score_kind %d", what, score_kind);
   LMN_REQUIRE(B > 0 && HW > 0 && HW < (1LL << 31) && (int64_t)B * HW < (1LL << 31), "%s: B=%d, HW=%lld (need B >= 1, HW >= 1, B * HW < 2^31)",
               what, B, (long long)HW);
   return 0;
 }
-
-// run `...` once with the compile-time constants KIND, VEC, LABELS, SOFTMAX of the call
-#define CV_DISPATCH2(kind, vec, ...)                                                                   \
-  do {                                                                                                 \
-    if ((kind) == LMN_CURVE_T_I64) {                                                                   \
-      if (vec) { constexpr int KIND = LMN_CURVE_T_I64; constexpr bool VEC = true; __VA_ARGS__; }       \
-      else { constexpr int KIND = LMN_CURVE_T_I64; constexpr bool VEC = false; __VA_ARGS__; }          \
-    } else {                                                                                           \
-      if (vec) { constexpr int KIND = LMN_CURVE_T_U8; constexpr bool VEC = true; __VA_ARGS__; }        \
-      else { constexpr int KIND = LMN_CURVE_T_U8; constexpr bool VEC = false; __VA_ARGS__; }           \
-    }                                                                                                  \
-  } while (0)
-#define CV_DISPATCH(kind, vec, labels, softmax, ...)                                                   \
-  do {                                                                                                 \
-    if (labels) {                                                                                      \
-      if (softmax) { constexpr bool LABELS = true, SOFTMAX = true; CV_DISPATCH2(kind, vec, __VA_ARGS__); }    \
-      else { constexpr bool LABELS = true, SOFTMAX = false; CV_DISPATCH2(kind, vec, __VA_ARGS__); }           \
-    } else {                                                                                           \
-      if (softmax) { constexpr bool LABELS = false, SOFTMAX = true; CV_DISPATCH2(kind, vec, __VA_ARGS__); }   \
-      else { constexpr bool LABELS = false, SOFTMAX = false; CV_DISPATCH2(kind, vec, __VA_ARGS__); }          \
-    }                                                                                                  \
-  } while (0)
 
 }  // namespace
 
@@ -199,11 +166,11 @@ int lmn_curve_hist(const float* values, const void* target, int target_kind, int
   LMN_REQUIRE((int64_t)B * C <= 65535, "curve_hist: B * C = %lld above 65535", (long long)B * C);
   LMN_REQUIRE(!softmax || workspace, "curve_hist: null pointer (the softmax form needs its workspace)");
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = HW % 4 == 0 && cv_aligned(values, 16) && cv_aligned(target, target_kind == LMN_CURVE_T_I64 ? 16 : 4) &&
-                   (!softmax || cv_aligned(workspace, 16));
+  const bool vec = HW % 4 == 0 && lmn_aligned(values, 16) && lmn_aligned(target, target_kind == LMN_CURVE_T_I64 ? 16 : 4) &&
+                   (!softmax || lmn_aligned(workspace, 16));
   const int planes = B * C;
   const int64_t items = vec ? HW / 4 : HW;
-  const int gx = loss_grid(items, 1024 / planes > 0 ? 1024 / planes : 1);      // the whole grid stays near 1024 blocks
+  const int gx = loss_grid_per(items, 1024, planes);
   const int64_t words = (int64_t)planes * 2 * (n_edges + 1) * 2;
   LMN_LAUNCH(loss_zero_kernel, dim3(loss_grid(words, 64)), dim3(256), 0, st, (uint32_t*)hist, words);
   const float* lse = nullptr;
@@ -213,9 +180,8 @@ int lmn_curve_hist(const float* values, const void* target, int target_kind, int
     lse = (const float*)workspace;
   }
   unsigned long long* ho = (unsigned long long*)hist;
-  CV_DISPATCH(target_kind, vec, labels, softmax, {
-    LMN_LAUNCH((curve_hist_kernel<KIND, VEC, LABELS, SOFTMAX>), dim3(gx, planes), dim3(256), 0, st, values, target, edges, n_edges, C, HW, lse, ho);
-  });
+  LOSS_SWITCH_BOOL(LABELS, labels, LOSS_SWITCH_BOOL(SOFTMAX, softmax, LOSS_SWITCH_KIND(target_kind, LOSS_SWITCH_BOOL(VEC, vec,
+    LMN_LAUNCH((curve_hist_kernel<KIND, VEC, LABELS, SOFTMAX>), dim3(gx, planes), dim3(256), 0, st, values, target, edges, n_edges, C, HW, lse, ho)))));
   return lmn_launch_status("curve_hist");
 }
 

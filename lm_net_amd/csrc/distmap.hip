@@ -22,7 +22,6 @@
 #define DM_INF 32768              // column sentinel: DM_INF^2 + 1023^2 < 2^31
 #define DM_MAXSIDE LMN_DISTMAP_MAX_SIDE
 #define DM_SEG 16                 // row segments per block of dm_col_kernel: ceil(1024 / 16) = 64 rows fit one 64-bit mask
-#define DM_MAXC 64
 static_assert(LMN_DISTMAP_LABELS_U8 == LOSS_LABELS_U8 && LMN_DISTMAP_LABELS_I64 == LOSS_LABELS_I64 && LMN_DISTMAP_SOFTMAX == LOSS_SOFTMAX &&
               LMN_DISTMAP_SIGMOID == LOSS_SIGMOID, "loss_common.h reads the label kinds and heads of lmnet_distmap.h");
 
@@ -329,7 +328,7 @@ __global__ void dl_finish_kernel(uint32_t* __restrict__ sums, float scale, float
 }
 
 bool dm_dims_ok(int B, int nk, int H, int W) {
-  return B >= 1 && nk >= 1 && nk <= DM_MAXC && H >= 2 && H <= DM_MAXSIDE && W >= 2 && W <= DM_MAXSIDE &&
+  return B >= 1 && nk >= 1 && nk <= LOSS_MAXC && H >= 2 && H <= DM_MAXSIDE && W >= 2 && W <= DM_MAXSIDE &&
          (int64_t)B * nk * H * W < (1LL << 31);
 }
 int64_t dm_mask_bytes(int64_t np, int64_t HW) { return lmn_up256(np * HW); }
@@ -361,14 +360,6 @@ int dl_check(const char* what, int target_kind, int head, int term, float alpha,
     case 1: { constexpr int TERM = 1; __VA_ARGS__; } break;       \
     default: { constexpr int TERM = 2; __VA_ARGS__; } break;      \
   }
-#define DL_CTS(cc, ...)                                           \
-  switch (cc) {                                                   \
-    case 2: { constexpr int CT = 2; __VA_ARGS__; } break;         \
-    case 3: { constexpr int CT = 3; __VA_ARGS__; } break;         \
-    case 4: { constexpr int CT = 4; __VA_ARGS__; } break;         \
-    case 8: { constexpr int CT = 8; __VA_ARGS__; } break;         \
-    default: { constexpr int CT = 0; __VA_ARGS__; } break;        \
-  }
 
 // one pass of either direction over the batch
 template <bool BWD>
@@ -376,9 +367,8 @@ void dl_launch(hipStream_t st, int head, int tid, const DlArgs& a, uint32_t* sum
                int grid) {
   if (head == LMN_DISTMAP_SOFTMAX) {
     const int C = a.C;
-    const bool staged = !(C == 2 || C == 3 || C == 4 || C == 8);
-    const size_t sh = staged ? (size_t)C * 256 * sizeof(float) : 8 * sizeof(float);    // (<= 64 KiB at C = 64)
-    DL_TERMS(tid, DL_CTS(C, LMN_LAUNCH((dl_softmax_kernel<CT, TERM, BWD>), dim3(grid), dim3(256), sh, st, a, sums, slot, gscale, dlogits)));
+    const size_t sh = loss_templated(C) ? 8 * sizeof(float) : (size_t)C * 256 * sizeof(float);    // (<= 64 KiB at C = 64)
+    DL_TERMS(tid, LOSS_SWITCH_CT(C, LMN_LAUNCH((dl_softmax_kernel<CT, TERM, BWD>), dim3(grid), dim3(256), sh, st, a, sums, slot, gscale, dlogits)));
   } else {
     DL_TERMS(tid, LMN_LAUNCH((dl_sigmoid_kernel<TERM, BWD>), dim3(grid), dim3(256), 0, st, a, sums, slot, gscale, dlogits));
   }
@@ -410,7 +400,7 @@ extern "C" {
 int64_t lmn_dist_workspace(int B, int nk, int H, int W) {
   if (!dm_dims_ok(B, nk, H, W)) {
     snprintf(g_lmn_err, sizeof(g_lmn_err), "dist_workspace: B=%d nk=%d %dx%d outside B >= 1, nk in [1, %d], sides in [2, %d], B * nk * H * W < 2^31",
-             B, nk, H, W, DM_MAXC, DM_MAXSIDE);
+             B, nk, H, W, LOSS_MAXC, DM_MAXSIDE);
     return -1;
   }
   const int64_t HW = (int64_t)H * W, np = (int64_t)B * nk;
@@ -459,7 +449,7 @@ int lmn_dist_loss_fwd(const float* logits, const void* target, int target_kind, 
   LMN_REQUIRE(logits && target && sd2_g && sums && loss, "dist_loss_fwd: null pointer");
   if (int rc = dl_check("dist_loss_fwd", target_kind, head, term, alpha, B, C, H, W, class_mask)) return rc;
   LMN_REQUIRE((term == LMN_DISTMAP_HAUSDORFF) == (sd2_p != nullptr), "dist_loss_fwd: sd2_p goes with the Hausdorff term and only with it");
-  LMN_REQUIRE(scale - scale == 0.f, "dist_loss_fwd: scale=%g is not finite", (double)scale);
+  LMN_REQUIRE(loss_finite(scale), "dist_loss_fwd: scale=%g is not finite", (double)scale);
   hipStream_t st = (hipStream_t)stream;
   const DlArgs a = dl_args(logits, target, target_kind, alpha, B, C, H, W, class_mask, sd2_g, sd2_p);
   const int grid = loss_grid((head == LMN_DISTMAP_SOFTMAX ? (int64_t)B : (int64_t)B * C) * a.hw, 1024);

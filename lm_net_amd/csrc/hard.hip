@@ -70,12 +70,6 @@ __device__ __forceinline__ float hp_sigmoid_value(float w, float z, bool t) {
   return hp_clamp(w * (t ? s.sp_neg : s.sp_pos));
 }
 
-__device__ __forceinline__ double hp_wave_sum(double v) {
-#pragma unroll
-  for (int m = 1; m <= 32; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // what the values pass of a block adds to its group's tables: the LDS histogram's non-zero bins, and Nhard by one atomic per block
 template <int NT>
 __device__ __forceinline__ void hp_flush_values(const uint32_t* s_hist, unsigned nh, unsigned block, const HpWs& w, int g) {
@@ -153,13 +147,7 @@ __global__ __launch_bounds__(256) void hp_sigmoid_values_kernel(HpArgs a, HpWs w
   const int64_t items = a.hw / E;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
     float z[E], v[E];
-    if constexpr (VEC) {
-      const f32x4 r = ld4(lg + q * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) z[j] = r[j];
-    } else {
-      z[0] = lg[q];
-    }
+    loss_load_z<E>(lg, q * E, z);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       const uint64_t t = (uint64_t)loss_label(a.target, a.kind, plane + q * E + j);
@@ -170,8 +158,7 @@ __global__ __launch_bounds__(256) void hp_sigmoid_values_kernel(HpArgs a, HpWs w
         nh += (a.use_cut && v[j] > a.cut) ? 1u : 0u;
       }
     }
-    if constexpr (VEC) st4(vo + q * 4, f32x4{v[0], v[1], v[2], v[3]});
-    else vo[q] = v[0];
+    loss_store<E>(vo, q * E, v);
   }
   hp_flush_values<256>(s_hist, nh, blockIdx.x + gridDim.x * blockIdx.y, w, g);
 }
@@ -286,19 +273,13 @@ __global__ __launch_bounds__(256) void hp_level_kernel(HpWs w, HpK k, const floa
     if (s.K != 0u) {
       for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
         float v[E];
-        if constexpr (VEC) {
-          const f32x4 r = ld4(vals + q * 4);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = r[j];
-        } else {
-          v[0] = vals[q];
-        }
+        loss_load_z<E>(vals, q * E, v);
 #pragma unroll
         for (int j = 0; j < E; ++j)
           if (v[j] >= 0.f && __float_as_uint(v[j]) > s.prefix) acc += (double)v[j];
       }
     }
-    acc = hp_wave_sum(acc);
+    acc = loss_wave_sum(acc);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -315,13 +296,7 @@ __global__ __launch_bounds__(256) void hp_level_kernel(HpWs w, HpK k, const floa
     constexpr int SHIFT = LEVEL == 2 ? 21 : 10;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
       float v[E];
-      if constexpr (VEC) {
-        const f32x4 r = ld4(vals + q * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = r[j];
-      } else {
-        v[0] = vals[q];
-      }
+      loss_load_z<E>(vals, q * E, v);
 #pragma unroll
       for (int j = 0; j < E; ++j) {
         const uint32_t bits = __float_as_uint(v[j]);
@@ -347,7 +322,7 @@ __global__ __launch_bounds__(256) void hp_finish_kernel(const double* __restrict
   for (int g = wv; g < G; g += 4) {
     double v = 0.0;
     for (int j = lane; j < nbx; j += 64) v += slots[(int64_t)g * nbx + j];
-    v = hp_wave_sum(v);
+    v = loss_wave_sum(v);
     if (lane == 0) {
       const int32_t* rec = selection + LMN_HARD_RECORD_WORDS * g;
       const double K = (double)rec[1], rest = (double)(rec[1] - rec[2]), tau = (double)__int_as_float(rec[4]);
@@ -445,13 +420,8 @@ __global__ __launch_bounds__(256) void hp_sigmoid_bwd_kernel(HpArgs a, const flo
   const int64_t items = a.hw / E;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
     float z[E], v[E], d[E];
-    if constexpr (VEC) {
-      const f32x4 r = ld4(lg + q * 4), u = ld4(vs + q * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { z[j] = r[j]; v[j] = u[j]; }
-    } else {
-      z[0] = lg[q]; v[0] = vs[q];
-    }
+    loss_load_z<E>(lg, q * E, z);
+    loss_load_z<E>(vs, q * E, v);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       bool sel;
@@ -463,13 +433,10 @@ __global__ __launch_bounds__(256) void hp_sigmoid_bwd_kernel(HpArgs a, const flo
         d[j] = f * wc * (t ? -s.omp : s.p);            // sigmoid(z) - t, without cancellation
       }
     }
-    if constexpr (VEC) st4(dl + q * 4, f32x4{d[0], d[1], d[2], d[3]});
-    else dl[q] = d[0];
+    loss_store<E>(dl, q * E, d);
   }
 }
 
-inline bool hp_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-inline bool hp_templated(int C) { return C == 2 || C == 3 || C == 4 || C == 8; }
 inline int hp_groups(int per_image, int B) { return per_image ? B : 1; }
 // elements of a group in the values buffer
 inline int64_t hp_group_elems(int head, int per_image, int B, int C, int64_t HW) {
@@ -477,7 +444,7 @@ inline int64_t hp_group_elems(int head, int per_image, int B, int C, int64_t HW)
 }
 // blocks per group of the level and sum passes: a function of the geometry alone, so that lmn_hard_workspace states the slots exactly
 // (with an unaligned base the one-element instance runs on the same grid: its loop strides)
-inline int hp_nbx(int G, int64_t M) { return loss_grid(M % 4 == 0 ? M / 4 : M, 1024 / G > 0 ? 1024 / G : 1); }
+inline int hp_nbx(int G, int64_t M) { return loss_grid_per(M % 4 == 0 ? M / 4 : M, 1024, G); }
 inline int64_t hp_tables_bytes(int G) { return lmn_up256((int64_t)4 * G * hp_group_words(G)); }
 inline int64_t hp_ws_bytes(int head, int per_image, int B, int C, int64_t HW) {
   const int G = hp_groups(per_image, B);
@@ -490,26 +457,8 @@ int hp_check(const char* what, int head, int per_image, int label_kind, int B, i
   LMN_REQUIRE(B >= 1 && B <= LMN_HARD_MAX_BATCH, "%s: B=%d not in [1, %d]", what, B, LMN_HARD_MAX_BATCH);
   LMN_REQUIRE(!per_image || B <= LMN_HARD_MAX_GROUPS, "%s: per_image: B=%d groups above the limit %d", what, B, LMN_HARD_MAX_GROUPS);
   if (int rc = loss_check_head(what, C, head == LMN_HARD_SOFTMAX, 1ull, label_kind)) return rc;
-  LMN_REQUIRE(H >= 1 && W >= 1, "%s: size %dx%d below 1", what, H, W);
-  LMN_REQUIRE((int64_t)B * C * H * W < (1LL << 31), "%s: B * C * H * W = %lld not below 2^31", what, (long long)B * C * H * W);
-  return 0;
+  return loss_check_extent(what, B, C, H, W);
 }
-
-#define HP_SOFTMAX(C, ...)                                      \
-  do {                                                          \
-    switch (C) {                                                \
-      case 2: { constexpr int CT = 2; __VA_ARGS__; } break;     \
-      case 3: { constexpr int CT = 3; __VA_ARGS__; } break;     \
-      case 4: { constexpr int CT = 4; __VA_ARGS__; } break;     \
-      case 8: { constexpr int CT = 8; __VA_ARGS__; } break;     \
-      default: { constexpr int CT = 0; __VA_ARGS__; } break;    \
-    }                                                           \
-  } while (0)
-#define HP_VEC(vec, ...)                                        \
-  do {                                                          \
-    if (vec) { constexpr bool VEC = true; __VA_ARGS__; }        \
-    else { constexpr bool VEC = false; __VA_ARGS__; }           \
-  } while (0)
 
 }  // namespace
 
@@ -527,12 +476,12 @@ int lmn_hard_fwd(const float* logits, const void* target, int label_kind, int he
   if (int rc = hp_check("hard_fwd", head, per_image, label_kind, B, C, H, W)) return rc;
   LMN_REQUIRE(keep >= 0.f && keep <= 1.f, "hard_fwd: keep=%g not in [0, 1]", (double)keep);
   LMN_REQUIRE(min_kept >= 0, "hard_fwd: min_kept=%lld is negative", (long long)min_kept);
-  LMN_REQUIRE(cut < 0.f || cut - cut == 0.f, "hard_fwd: cut=%g is not finite", (double)cut);
+  LMN_REQUIRE(cut < 0.f || loss_finite(cut), "hard_fwd: cut=%g is not finite", (double)cut);
   LMN_REQUIRE(keep > 0.f || min_kept > 0 || cut >= 0.f, "hard_fwd: none of keep, min_kept and cut is given");
-  LMN_REQUIRE(scale - scale == 0.f, "hard_fwd: scale=%g is not finite", (double)scale);
+  LMN_REQUIRE(loss_finite(scale), "hard_fwd: scale=%g is not finite", (double)scale);
   const int64_t HW = (int64_t)H * W, need = hp_ws_bytes(head, per_image, B, C, HW);
   LMN_REQUIRE(ws_bytes >= need, "hard_fwd: workspace of %lld bytes too small, %lld needed", (long long)ws_bytes, (long long)need);
-  LMN_REQUIRE(hp_aligned(workspace, 8), "hard_fwd: the workspace is not 8-byte aligned");
+  LMN_REQUIRE(lmn_aligned(workspace, 8), "hard_fwd: the workspace is not 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int G = hp_groups(per_image, B);
   const int64_t M = hp_group_elems(head, per_image, B, C, HW);
@@ -547,18 +496,16 @@ int lmn_hard_fwd(const float* logits, const void* target, int label_kind, int he
   const int64_t words = (int64_t)G * hp_group_words(G);
   LMN_LAUNCH(loss_zero_kernel, dim3(loss_grid(words, 256)), dim3(256), 0, st, tab, words);
   if (head == LMN_HARD_SOFTMAX) {
-    const int64_t cap = 1024 / B > 0 ? 1024 / B : 1;
-    const dim3 grid(loss_grid(HW, cap), B);
-    HP_SOFTMAX(C, LMN_LAUNCH((hp_softmax_values_kernel<CT>), grid, dim3(256), 0, st, a, w, values));
+    const dim3 grid(loss_grid_per(HW, 1024, B), B);
+    LOSS_SWITCH_CT(C, LMN_LAUNCH((hp_softmax_values_kernel<CT>), grid, dim3(256), 0, st, a, w, values));
   } else {
-    const bool vec = HW % 4 == 0 && hp_aligned(logits, 16) && hp_aligned(values, 16);
-    const int64_t planes = (int64_t)B * C;
-    const dim3 grid(loss_grid(HW % 4 == 0 ? HW / 4 : HW, 2048 / planes > 0 ? 2048 / planes : 1), C, B);
-    HP_VEC(vec, LMN_LAUNCH((hp_sigmoid_values_kernel<VEC>), grid, dim3(256), 0, st, a, w, values));
+    const bool vec = HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(values, 16);
+    const dim3 grid(loss_grid_per(HW % 4 == 0 ? HW / 4 : HW, 2048, (int64_t)B * C), C, B);
+    LOSS_SWITCH_BOOL(VEC, vec, LMN_LAUNCH((hp_sigmoid_values_kernel<VEC>), grid, dim3(256), 0, st, a, w, values));
   }
-  const bool vec = M % 4 == 0 && hp_aligned(values, 16);
+  const bool vec = M % 4 == 0 && lmn_aligned(values, 16);
   const dim3 grid(nbx, G);
-  HP_VEC(vec, {
+  LOSS_SWITCH_BOOL(VEC, vec, {
     LMN_LAUNCH((hp_level_kernel<2, VEC>), grid, dim3(256), 0, st, w, k, (const float*)values, M, selection);
     LMN_LAUNCH((hp_level_kernel<3, VEC>), grid, dim3(256), 0, st, w, k, (const float*)values, M, selection);
     LMN_LAUNCH((hp_level_kernel<4, VEC>), grid, dim3(256), 0, st, w, k, (const float*)values, M, selection);
@@ -572,21 +519,20 @@ int lmn_hard_bwd(const float* logits, const void* target, int label_kind, int he
                  lmn_stream_t stream) {
   LMN_REQUIRE(logits && target && values && selection && dlogits, "hard_bwd: null pointer");
   if (int rc = hp_check("hard_bwd", head, per_image, label_kind, B, C, H, W)) return rc;
-  LMN_REQUIRE(scale - scale == 0.f, "hard_bwd: scale=%g is not finite", (double)scale);
+  LMN_REQUIRE(loss_finite(scale), "hard_bwd: scale=%g is not finite", (double)scale);
   hipStream_t st = (hipStream_t)stream;
   const int64_t HW = (int64_t)H * W;
   const int G = hp_groups(per_image, B);
   const HpArgs a{logits, target, weight, label_kind, C, per_image, 0, HW, 0.f};
   if (head == LMN_HARD_SOFTMAX) {
-    const int64_t cap = 4096 / B > 0 ? 4096 / B : 1;
-    const dim3 grid(hp_templated(C) ? loss_grid(HW, cap) : loss_grid(HW * 4, cap * 4), B);
-    HP_SOFTMAX(C, LMN_LAUNCH((hp_softmax_bwd_kernel<CT>), grid, dim3(CT > 0 ? 256 : 64), CT > 0 ? 0 : (size_t)C * 64 * 4, st, a, values,
+    const int64_t cap = loss_cap(4096, B);
+    const dim3 grid(loss_templated(C) ? loss_grid(HW, cap) : loss_grid(HW * 4, cap * 4), B);
+    LOSS_SWITCH_CT(C, LMN_LAUNCH((hp_softmax_bwd_kernel<CT>), grid, dim3(CT > 0 ? 256 : 64), CT > 0 ? 0 : (size_t)C * 64 * 4, st, a, values,
                              selection, G, scale, gscale, dlogits));
   } else {
-    const bool vec = HW % 4 == 0 && hp_aligned(logits, 16) && hp_aligned(values, 16) && hp_aligned(dlogits, 16);
-    const int64_t planes = (int64_t)B * C;
-    const dim3 grid(loss_grid(vec ? HW / 4 : HW, 4096 / planes > 0 ? 4096 / planes : 1), C, B);
-    HP_VEC(vec, LMN_LAUNCH((hp_sigmoid_bwd_kernel<VEC>), grid, dim3(256), 0, st, a, values, selection, G, scale, gscale, dlogits));
+    const bool vec = HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(values, 16) && lmn_aligned(dlogits, 16);
+    const dim3 grid(loss_grid_per(vec ? HW / 4 : HW, 4096, (int64_t)B * C), C, B);
+    LOSS_SWITCH_BOOL(VEC, vec, LMN_LAUNCH((hp_sigmoid_bwd_kernel<VEC>), grid, dim3(256), 0, st, a, values, selection, G, scale, gscale, dlogits));
   }
   return lmn_launch_status("hard_bwd");
 }

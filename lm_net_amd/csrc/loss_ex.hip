@@ -12,23 +12,6 @@
 
 namespace {
 
-constexpr int LX_STRIDE = 65;   // row stride of the staged tile of the general sums kernel (conflict-free row reads)
-constexpr int LX_MAXC = 64;
-
-template <int C>
-__device__ __forceinline__ void lx_softmax(const float (&z)[C], float (&p)[C], float& lse) {
-  float mx = -3.0e38f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-  float den = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) { p[c] = __expf(z[c] - mx); den += p[c]; }
-  const float r = 1.f / den;
-  lse = mx + __logf(den);
-#pragma unroll
-  for (int c = 0; c < C; ++c) p[c] *= r;
-}
-
 template <int C, bool FOCAL>
 __global__ __launch_bounds__(256) void segloss_ex_sums_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                               const float* __restrict__ wce, int B, int64_t hw, FocalK fk,
@@ -50,7 +33,7 @@ __global__ __launch_bounds__(256) void segloss_ex_sums_kernel(const float* __res
     const int64_t yl = target[idx];
     if ((uint64_t)yl >= (uint64_t)C) continue;             // void: adds to no sum
     const int y = (int)yl;
-    lx_softmax<C>(z, p, lse);
+    loss_softmax<C>(z, p, lse);
     float sm = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -136,7 +119,7 @@ __global__ __launch_bounds__(256) void segloss_ex_bwd_kernel(const float* __rest
       continue;
     }
     const int y = (int)yl;
-    lx_softmax<C>(z, p, lse);
+    loss_softmax<C>(z, p, lse);
     float wy = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) wy = (c == y) ? w[c] : wy;
@@ -165,13 +148,13 @@ template <bool FOCAL>
 __global__ __launch_bounds__(256) void segloss_ex_sums_gen_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                                   const float* __restrict__ wce, int B, int C, int64_t hw, FocalK fk,
                                                                   float* __restrict__ sums, int det) {
-  extern __shared__ float lx_tile[];                  // [4 waves][C][LX_STRIDE]
+  extern __shared__ float lx_tile[];                  // [4 waves][C][LOSS_TILE_STRIDE]
   __shared__ float s_lse[4][64];
   __shared__ int s_y[4][64];                          // label of the pixel, -1 void, -2 past the end of the batch
   __shared__ float s_part[4][3][64];
-  __shared__ float s_red[4][4 + 3 * LX_MAXC];
+  __shared__ float s_red[4][4 + 3 * LOSS_MAXC];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float* tile = lx_tile + wv * C * LX_STRIDE;
+  float* tile = lx_tile + wv * C * LOSS_TILE_STRIDE;
   const int G = 64 / C, cc = lane % C, gg = lane / C;
   float a_w = 0.f, a_nll = 0.f, a_sm = 0.f, a_f = 0.f, a_pt = 0.f, a_pp = 0.f, a_t = 0.f;
   const int64_t total = (int64_t)B * hw;
@@ -186,21 +169,21 @@ __global__ __launch_bounds__(256) void segloss_ex_sums_gen_kernel(const float* _
 #pragma unroll 8
       for (int c = 0; c < C; ++c) {                   // (staged whatever the label: the loads go out with the label load)
         const float z = lg[c * hw];
-        tile[c * LX_STRIDE + lane] = z;
+        tile[c * LOSS_TILE_STRIDE + lane] = z;
         mx = fmaxf(mx, z);
       }
       const int64_t yl = target[idx];
       y = ((uint64_t)yl < (uint64_t)C) ? (int)yl : -1;
       if (y >= 0) {
         float den = 0.f;
-        for (int c = 0; c < C; ++c) den += __expf(tile[c * LX_STRIDE + lane] - mx);
+        for (int c = 0; c < C; ++c) den += __expf(tile[c * LOSS_TILE_STRIDE + lane] - mx);
         lse = mx + __logf(den);
         float sm = 0.f;
-        for (int c = 0; c < C; ++c) sm += wce[c] * (lse - tile[c * LX_STRIDE + lane]);   // sum_c w_c * (-log p_c)
+        for (int c = 0; c < C; ++c) sm += wce[c] * (lse - tile[c * LOSS_TILE_STRIDE + lane]);   // sum_c w_c * (-log p_c)
         a_sm += sm;
         const float wy = wce[y];
         a_w += wy;
-        a_nll += wy * (lse - tile[y * LX_STRIDE + lane]);
+        a_nll += wy * (lse - tile[y * LOSS_TILE_STRIDE + lane]);
       }
     }
     s_lse[wv][lane] = lse;
@@ -211,7 +194,7 @@ __global__ __launch_bounds__(256) void segloss_ex_sums_gen_kernel(const float* _
         const int yp = s_y[wv][p];
         if (yp == -2) break;                          // (pixels past the end are the tail of the tile)
         if (yp < 0) continue;                         // void: adds to no sum
-        const float z = tile[cc * LX_STRIDE + p];
+        const float z = tile[cc * LOSS_TILE_STRIDE + p];
         const float pc = __expf(z - s_lse[wv][p]);
         const float t = (yp == cc) ? 1.f : 0.f;
         a_pt += pc * t;
@@ -300,7 +283,7 @@ __global__ __launch_bounds__(256) void segloss_ex_bwd_gen_kernel(const float* __
 
 // the argument checks shared by the two loss entries
 int lx_check(const char* what, int B, int C, int64_t HW, const lmn_loss_param_t* p) {
-  LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= LX_MAXC, "%s: C=%d not in [2, %d]", what, C, LX_MAXC);
+  LMN_REQUIRE(B > 0 && HW > 0 && C >= 2 && C <= LOSS_MAXC, "%s: C=%d not in [2, %d]", what, C, LOSS_MAXC);
   LMN_REQUIRE(!p->has_ignore || p->ignore_index < 0 || p->ignore_index >= C, "%s: ignore_index=%lld inside [0, %d)", what,
               (long long)p->ignore_index, C);
   LMN_REQUIRE(p->label_smoothing >= 0.f && p->label_smoothing <= 1.f, "%s: label_smoothing=%g not in [0, 1]", what, (double)p->label_smoothing);
@@ -332,26 +315,15 @@ int lmn_segloss_ex_fwd(const float* logits, const int64_t* target, const float* 
     sd = lmn_det_slots(st, (size_t)grid * NS);
     LMN_REQUIRE(sd, "segloss_ex_fwd: deterministic mode: no scratch");
   }
-#define LX_SUMS(CC)                                                                                                              \
-  case CC:                                                                                                                       \
-    if (focal) LMN_LAUNCH((segloss_ex_sums_kernel<CC, true>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, B, HW, fk, sd, g_lmn_det); \
-    else LMN_LAUNCH((segloss_ex_sums_kernel<CC, false>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, B, HW, fk, sd, g_lmn_det);      \
-    break;
-  switch (C) {
-    LX_SUMS(2) LX_SUMS(3) LX_SUMS(4) LX_SUMS(8)
-    default: {
-      const size_t sh = (size_t)4 * C * LX_STRIDE * sizeof(float);
-      if (focal) {
-        if (sh > 64 * 1024) (void)hipFuncSetAttribute((const void*)segloss_ex_sums_gen_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        LMN_LAUNCH((segloss_ex_sums_gen_kernel<true>), dim3(grid), dim3(256), sh, st, logits, target, w_ce, B, C, HW, fk, sd, g_lmn_det);
-      } else {
-        if (sh > 64 * 1024) (void)hipFuncSetAttribute((const void*)segloss_ex_sums_gen_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        LMN_LAUNCH((segloss_ex_sums_gen_kernel<false>), dim3(grid), dim3(256), sh, st, logits, target, w_ce, B, C, HW, fk, sd, g_lmn_det);
-      }
-      break;
+  LOSS_SWITCH_CT(C, LOSS_SWITCH_BOOL(FOCAL, focal, {
+    if constexpr (CT > 0) {
+      LMN_LAUNCH((segloss_ex_sums_kernel<CT, FOCAL>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, B, HW, fk, sd, g_lmn_det);
+    } else {
+      const size_t sh = (size_t)4 * C * LOSS_TILE_STRIDE * sizeof(float);
+      if (sh > 64 * 1024) (void)hipFuncSetAttribute((const void*)segloss_ex_sums_gen_kernel<FOCAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+      LMN_LAUNCH((segloss_ex_sums_gen_kernel<FOCAL>), dim3(grid), dim3(256), sh, st, logits, target, w_ce, B, C, HW, fk, sd, g_lmn_det);
     }
-  }
-#undef LX_SUMS
+  }));
   if (g_lmn_det) lmn_det_sum(st, sd, grid, NS, sums);
   LMN_LAUNCH(segloss_ex_finish_kernel, dim3(1), dim3(64), 0, st, sums, w_ce, w_dice, C, fin, loss4, coef);
   return lmn_launch_status("segloss_ex_fwd");
@@ -365,21 +337,14 @@ int lmn_segloss_ex_bwd(const float* logits, const int64_t* target, const float* 
   const bool focal = param->focal_scale > 0.f;
   const int grid = loss_grid((int64_t)B * HW, 4096);
   const FocalK fk{param->focal_gamma, param->focal_alpha};
-#define LX_BWD(CC)                                                                                                                 \
-  case CC:                                                                                                                         \
-    if (focal) LMN_LAUNCH((segloss_ex_bwd_kernel<CC, true>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, coef, gscale, B, HW, fk, dlogits); \
-    else LMN_LAUNCH((segloss_ex_bwd_kernel<CC, false>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, coef, gscale, B, HW, fk, dlogits);      \
-    break;
-  switch (C) {
-    LX_BWD(2) LX_BWD(3) LX_BWD(4) LX_BWD(8)
-    default: {
+  LOSS_SWITCH_CT(C, LOSS_SWITCH_BOOL(FOCAL, focal, {
+    if constexpr (CT > 0) {
+      LMN_LAUNCH((segloss_ex_bwd_kernel<CT, FOCAL>), dim3(grid), dim3(256), 0, st, logits, target, w_ce, coef, gscale, B, HW, fk, dlogits);
+    } else {
       const size_t sh = (size_t)C * 256 * sizeof(float);   // (<= 64 KB of LDS at C = 64)
-      if (focal) LMN_LAUNCH((segloss_ex_bwd_gen_kernel<true>), dim3(grid), dim3(256), sh, st, logits, target, w_ce, coef, gscale, B, C, HW, fk, dlogits);
-      else LMN_LAUNCH((segloss_ex_bwd_gen_kernel<false>), dim3(grid), dim3(256), sh, st, logits, target, w_ce, coef, gscale, B, C, HW, fk, dlogits);
-      break;
+      LMN_LAUNCH((segloss_ex_bwd_gen_kernel<FOCAL>), dim3(grid), dim3(256), sh, st, logits, target, w_ce, coef, gscale, B, C, HW, fk, dlogits);
     }
-  }
-#undef LX_BWD
+  }));
   return lmn_launch_status("segloss_ex_bwd");
 }
 

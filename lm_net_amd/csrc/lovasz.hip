@@ -486,9 +486,7 @@ int lv_check(const char* what, int target_kind, int head, int B, int C, int H, i
   LMN_REQUIRE(head == LMN_LOVASZ_SOFTMAX || head == LMN_LOVASZ_SIGMOID, "%s: unknown head %d", what, head);
   LMN_REQUIRE(B >= 1, "%s: B=%d < 1", what, B);
   if (int rc = loss_check_head(what, C, head == LMN_LOVASZ_SOFTMAX, class_mask, target_kind)) return rc;
-  LMN_REQUIRE(H >= 1 && W >= 1, "%s: size %dx%d below 1", what, H, W);
-  LMN_REQUIRE((int64_t)B * C * H * W < (1LL << 31), "%s: B * C * H * W = %lld not below 2^31", what, (long long)B * C * H * W);
-  return 0;
+  return loss_check_extent(what, B, C, H, W);
 }
 
 LvGeo lv_geo(int target_kind, int per_image, int B, int C, int H, int W, uint64_t class_mask) {
@@ -532,7 +530,7 @@ int lmn_lovasz_fwd(const float* logits, const void* target, int target_kind, int
                    int32_t* counts, float* coef, void* sums, float* loss, lmn_stream_t stream) {
   LMN_REQUIRE(logits && target && workspace && errors && perm && counts && coef && sums && loss, "lovasz_fwd: null pointer");
   if (int rc = lv_check("lovasz_fwd", target_kind, head, B, C, H, W, class_mask)) return rc;
-  LMN_REQUIRE(scale - scale == 0.f, "lovasz_fwd: scale=%g is not finite", (double)scale);
+  LMN_REQUIRE(loss_finite(scale), "lovasz_fwd: scale=%g is not finite", (double)scale);
   const LvGeo g = lv_geo(target_kind, per_image, B, C, H, W, class_mask);
   const int64_t S64 = per_image ? (int64_t)B * g.nk : g.nk;
   LMN_REQUIRE(S64 <= LMN_LOVASZ_MAX_SEGMENTS, "lovasz_fwd: %lld segments above %d", (long long)S64, LMN_LOVASZ_MAX_SEGMENTS);

@@ -15,9 +15,7 @@ static_assert(LMN_REGION_LABELS_U8 == LOSS_LABELS_U8 && LMN_REGION_LABELS_I64 ==
 
 namespace {
 
-constexpr int RG_STRIDE = 65;   // row stride of the staged tile of the general sums kernel (conflict-free row reads), as LX_STRIDE
-constexpr int RG_MAXC = 64;
-constexpr int RG_CNT0 = 192;    // the first thread of a block that adds the integer counts (3 * RG_MAXC float sums come before it)
+constexpr int RG_CNT0 = 192;    // the first thread of a block that adds the integer counts (3 * LOSS_MAXC float sums come before it)
 
 // where a block of the sums pass adds its partial sums
 struct RgOut {
@@ -37,59 +35,6 @@ __device__ __forceinline__ int rg_label(const void* __restrict__ target, int64_t
     const int64_t v = ((const int64_t*)target)[idx];
     return (uint64_t)v < (uint64_t)C ? (int)v : -1;
   }
-}
-
-// E consecutive targets of a plane as 0, 1 or 2 (void: every value but 0 and 1)
-template <int KIND, int E>
-__device__ __forceinline__ void rg_load_t(const void* __restrict__ plane, int64_t i, int (&t)[E]) {
-  if constexpr (KIND == LMN_REGION_LABELS_U8) {
-    const uint8_t* p = (const uint8_t*)plane + i;
-    if constexpr (E == 4) {
-      const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t v = (w >> (8 * j)) & 255u;
-        t[j] = v <= 1u ? (int)v : 2;
-      }
-    } else {
-      const uint32_t v = p[0];
-      t[0] = v <= 1u ? (int)v : 2;
-    }
-  } else {
-    const int64_t* p = (const int64_t*)plane + i;
-    if constexpr (E == 4) {
-      const longlong2 a = *reinterpret_cast<const longlong2*>(p), b = *reinterpret_cast<const longlong2*>(p + 2);
-      const int64_t v[4] = {a.x, a.y, b.x, b.y};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) t[j] = (uint64_t)v[j] <= 1ull ? (int)v[j] : 2;
-    } else {
-      const int64_t v = p[0];
-      t[0] = (uint64_t)v <= 1ull ? (int)v : 2;
-    }
-  }
-}
-template <int E>
-__device__ __forceinline__ void rg_load_z(const float* __restrict__ plane, int64_t i, float (&z)[E]) {
-  if constexpr (E == 4) {
-    const f32x4 v = ld4(plane + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) z[j] = v[j];
-  } else {
-    z[0] = plane[i];
-  }
-}
-
-template <int C>
-__device__ __forceinline__ void rg_softmax(const float (&z)[C], float (&p)[C]) {
-  float mx = -3.0e38f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
-  float den = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) { p[c] = __expf(z[c] - mx); den += p[c]; }
-  const float r = 1.f / den;
-#pragma unroll
-  for (int c = 0; c < C; ++c) p[c] *= r;
 }
 
 // The block's sums of the softmax kernels leave through here: red_f[wave][f * C + c], red_u[wave][c] = T_c, red_n[wave] = N.  Thread
@@ -132,7 +77,7 @@ __global__ __launch_bounds__(256) void rg_softmax_sums_kernel(const float* __res
     for (int c = 0; c < C; ++c) z[c] = lg[c * hw + i];     // (issued with the label load, not after it)
     const int y = rg_label<KIND>(target, (int64_t)b * hw + i, C);
     if (y < 0) continue;                                    // void: adds to no sum
-    rg_softmax<C>(z, p);
+    loss_softmax<C>(z, p);
     a_n += 1u;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -172,16 +117,16 @@ template <bool SQ, int KIND>
 __global__ __launch_bounds__(256) void rg_softmax_sums_gen_kernel(const float* __restrict__ logits, const void* __restrict__ target, int C,
                                                                   int64_t hw, RgOut o) {
   constexpr int NF = SQ ? 3 : 2;
-  extern __shared__ float rg_tile[];                   // [4 waves][C][RG_STRIDE]
+  extern __shared__ float rg_tile[];                   // [4 waves][C][LOSS_TILE_STRIDE]
   __shared__ float s_mx[4][64], s_ri[4][64];
   __shared__ int s_y[4][64];                           // label of the pixel, -1 void, -2 past the end of the image
   __shared__ float s_part[4][3][64];
   __shared__ unsigned s_partu[4][64];
-  __shared__ float s_red[4][3 * RG_MAXC];
-  __shared__ unsigned s_redu[4][RG_MAXC];
+  __shared__ float s_red[4][3 * LOSS_MAXC];
+  __shared__ unsigned s_redu[4][LOSS_MAXC];
   __shared__ unsigned s_redn[4];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float* tile = rg_tile + wv * C * RG_STRIDE;
+  float* tile = rg_tile + wv * C * LOSS_TILE_STRIDE;
   const int G = 64 / C, cc = lane % C, gg = lane / C;
   const int b = blockIdx.y;
   const float* lg = logits + (int64_t)b * C * hw;
@@ -195,13 +140,13 @@ __global__ __launch_bounds__(256) void rg_softmax_sums_gen_kernel(const float* _
 #pragma unroll 8
       for (int c = 0; c < C; ++c) {                    // (staged whatever the label: the loads go out with the label load)
         const float z = lg[c * hw + i];
-        tile[c * RG_STRIDE + lane] = z;
+        tile[c * LOSS_TILE_STRIDE + lane] = z;
         mx = fmaxf(mx, z);
       }
       y = rg_label<KIND>(target, (int64_t)b * hw + i, C);
       if (y >= 0) {
         float den = 0.f;
-        for (int c = 0; c < C; ++c) den += __expf(tile[c * RG_STRIDE + lane] - mx);
+        for (int c = 0; c < C; ++c) den += __expf(tile[c * LOSS_TILE_STRIDE + lane] - mx);
         ri = 1.f / den;
         a_n += 1u;
       }
@@ -215,7 +160,7 @@ __global__ __launch_bounds__(256) void rg_softmax_sums_gen_kernel(const float* _
         const int yp = s_y[wv][p];
         if (yp == -2) break;                           // (pixels past the end are the tail of the tile)
         if (yp < 0) continue;                          // void: adds to no sum
-        const float pc = __expf(tile[cc * RG_STRIDE + p] - s_mx[wv][p]) * s_ri[wv][p];
+        const float pc = __expf(tile[cc * LOSS_TILE_STRIDE + p] - s_mx[wv][p]) * s_ri[wv][p];
         const bool on = yp == cc;
         a_pt += on ? pc : 0.f;
         a_p += pc;
@@ -244,7 +189,7 @@ __global__ __launch_bounds__(256) void rg_softmax_sums_gen_kernel(const float* _
     s_redu[wv][lane] = u;
   }
   __syncthreads();
-  rg_block_out<NF>(o, C, b, &s_red[0][0], 3 * RG_MAXC, &s_redu[0][0], RG_MAXC, s_redn);
+  rg_block_out<NF>(o, C, b, &s_red[0][0], 3 * LOSS_MAXC, &s_redu[0][0], LOSS_MAXC, s_redn);
 }
 
 template <bool VEC, bool SQ, int KIND>
@@ -262,8 +207,8 @@ __global__ __launch_bounds__(256) void rg_sigmoid_sums_kernel(const float* __res
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
     float z[E];
     int t[E];
-    rg_load_z<E>(lg, q * E, z);
-    rg_load_t<KIND, E>(tg, q * E, t);
+    loss_load_z<E>(lg, q * E, z);
+    loss_load_t<KIND, E>(tg, q * E, t);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       if (t[j] > 1) continue;                          // void: adds to no sum
@@ -436,7 +381,7 @@ __global__ __launch_bounds__(256) void rg_softmax_bwd_kernel(const float* __rest
       for (int c = 0; c < C; ++c) dl[c * hw + i] = 0.f;
       continue;
     }
-    rg_softmax<C>(z, p);
+    loss_softmax<C>(z, p);
     float d[C], dp = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -455,9 +400,9 @@ __global__ __launch_bounds__(256) void rg_softmax_bwd_gen_kernel(const float* __
                                                                  int64_t hw, RgIn in, const float* __restrict__ gscale,
                                                                  float* __restrict__ dlogits) {
   extern __shared__ float rg_tile[];                   // [C][256]
-  __shared__ float s_a[RG_MAXC], s_b[RG_MAXC], s_c[RG_MAXC];
+  __shared__ float s_a[LOSS_MAXC], s_b[LOSS_MAXC], s_c[LOSS_MAXC];
   const int b = blockIdx.y;
-  if (threadIdx.x < RG_MAXC) { s_a[threadIdx.x] = 0.f; s_b[threadIdx.x] = 0.f; s_c[threadIdx.x] = 0.f; }
+  if (threadIdx.x < LOSS_MAXC) { s_a[threadIdx.x] = 0.f; s_b[threadIdx.x] = 0.f; s_c[threadIdx.x] = 0.f; }
   __syncthreads();
   if (threadIdx.x < in.nk) {
     const float* co = in.coef + ((int64_t)(in.per_image ? b : 0) * in.nk + threadIdx.x) * 3;
@@ -525,8 +470,8 @@ __global__ __launch_bounds__(256) void rg_sigmoid_bwd_kernel(const float* __rest
     if (scored) {
       float z[E];
       int t[E];
-      rg_load_z<E>(lg, q * E, z);
-      rg_load_t<KIND, E>(tg, q * E, t);
+      loss_load_z<E>(lg, q * E, z);
+      loss_load_t<KIND, E>(tg, q * E, t);
 #pragma unroll
       for (int j = 0; j < E; ++j) {
         if (t[j] > 1) continue;
@@ -534,19 +479,15 @@ __global__ __launch_bounds__(256) void rg_sigmoid_bwd_kernel(const float* __rest
         d[j] = gs * (((t[j] == 1 ? a : 0.f) + bq + cq * s.p) * (s.p * s.omp));
       }
     }
-    if constexpr (VEC) st4(dl + q * 4, f32x4{d[0], d[1], d[2], d[3]});
-    else dl[q] = d[0];
+    loss_store<E>(dl, q * E, d);
   }
 }
-
-inline bool rg_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // blocks of the sums pass per image (softmax head) or per plane (sigmoid head): a function of head, B, C and HW alone, so that
 // lmn_region_workspace can state the slots exactly
 inline int rg_nbx(int head, int B, int C, int64_t HW) {
-  if (head == LMN_REGION_SOFTMAX) return loss_grid(HW, 1024 / B > 0 ? 1024 / B : 1);
-  const int64_t planes = (int64_t)B * C;
-  return loss_grid(HW % 4 == 0 ? HW / 4 : HW, 2048 / planes > 0 ? 2048 / planes : 1);
+  if (head == LMN_REGION_SOFTMAX) return loss_grid_per(HW, 1024, B);
+  return loss_grid_per(HW % 4 == 0 ? HW / 4 : HW, 2048, (int64_t)B * C);
 }
 
 inline int64_t rg_ws_bytes(int head, int B, int C, int64_t HW, int nk) {
@@ -557,29 +498,8 @@ int rg_check(const char* what, int target_kind, int head, int B, int C, int H, i
   LMN_REQUIRE(head == LMN_REGION_SOFTMAX || head == LMN_REGION_SIGMOID, "%s: unknown head %d", what, head);
   LMN_REQUIRE(B >= 1 && B <= LMN_REGION_MAX_BATCH, "%s: B=%d not in [1, %d]", what, B, LMN_REGION_MAX_BATCH);
   if (int rc = loss_check_head(what, C, head == LMN_REGION_SOFTMAX, class_mask, target_kind)) return rc;
-  LMN_REQUIRE(H >= 1 && W >= 1, "%s: size %dx%d below 1", what, H, W);
-  LMN_REQUIRE((int64_t)B * C * H * W < (1LL << 31), "%s: B * C * H * W = %lld not below 2^31", what, (long long)B * C * H * W);
-  return 0;
+  return loss_check_extent(what, B, C, H, W);
 }
-
-// run `...` once with the compile-time constants KIND and FLAG of the call
-#define RG_DISPATCH(kind, flag, ...)                                                                   \
-  do {                                                                                                 \
-    if ((kind) == LMN_REGION_LABELS_I64) {                                                             \
-      if (flag) { constexpr int KIND = LMN_REGION_LABELS_I64; constexpr bool FLAG = true; __VA_ARGS__; }   \
-      else { constexpr int KIND = LMN_REGION_LABELS_I64; constexpr bool FLAG = false; __VA_ARGS__; }       \
-    } else {                                                                                           \
-      if (flag) { constexpr int KIND = LMN_REGION_LABELS_U8; constexpr bool FLAG = true; __VA_ARGS__; }    \
-      else { constexpr int KIND = LMN_REGION_LABELS_U8; constexpr bool FLAG = false; __VA_ARGS__; }        \
-    }                                                                                                  \
-  } while (0)
-
-// the same with KIND alone
-#define RG_KIND(kind, ...)                                                                   \
-  do {                                                                                       \
-    if ((kind) == LMN_REGION_LABELS_I64) { constexpr int KIND = LMN_REGION_LABELS_I64; __VA_ARGS__; }  \
-    else { constexpr int KIND = LMN_REGION_LABELS_U8; __VA_ARGS__; }                         \
-  } while (0)
 
 }  // namespace
 
@@ -600,11 +520,11 @@ int lmn_region_fwd(const float* logits, const void* target, int target_kind, int
   LMN_REQUIRE(denominator == LMN_REGION_LINEAR || denominator == LMN_REGION_SQUARED, "region_fwd: unknown denominator %d", denominator);
   LMN_REQUIRE(denominator == LMN_REGION_LINEAR || kind == LMN_REGION_DICE || kind == LMN_REGION_JACCARD,
               "region_fwd: the squared denominator exists for dice and jaccard only (kind %d)", kind);
-  LMN_REQUIRE(alpha >= 0.f && beta >= 0.f && alpha - alpha == 0.f && beta - beta == 0.f, "region_fwd: alpha=%g, beta=%g must be finite and >= 0",
+  LMN_REQUIRE(alpha >= 0.f && beta >= 0.f && loss_finite(alpha) && loss_finite(beta), "region_fwd: alpha=%g, beta=%g must be finite and >= 0",
               (double)alpha, (double)beta);
-  LMN_REQUIRE(smooth >= 0.f && smooth - smooth == 0.f, "region_fwd: smooth=%g must be finite and >= 0", (double)smooth);
+  LMN_REQUIRE(smooth >= 0.f && loss_finite(smooth), "region_fwd: smooth=%g must be finite and >= 0", (double)smooth);
   LMN_REQUIRE(exponent > 0.f && exponent <= 8.f, "region_fwd: exponent=%g not in (0, 8]", (double)exponent);
-  LMN_REQUIRE(scale - scale == 0.f, "region_fwd: scale=%g is not finite", (double)scale);
+  LMN_REQUIRE(loss_finite(scale), "region_fwd: scale=%g is not finite", (double)scale);
   LMN_REQUIRE(kind != LMN_REGION_GDICE || !weight, "region_fwd: generalized dice takes no class weight");
   const int64_t HW = (int64_t)H * W;
   const int nk = __builtin_popcountll(class_mask), nbx = rg_nbx(head, B, C, HW), G = per_image ? B : 1;
@@ -625,26 +545,21 @@ int lmn_region_fwd(const float* logits, const void* target, int target_kind, int
   LMN_LAUNCH(loss_zero_kernel, dim3(loss_grid(2 * words, 64)), dim3(256), 0, st, (uint32_t*)counts, 2 * words);
   if (head == LMN_REGION_SOFTMAX) {
     const dim3 grid(nbx, B);
-#define RG_SUMS(CC) \
-  case CC: RG_DISPATCH(target_kind, sq, LMN_LAUNCH((rg_softmax_sums_kernel<CC, FLAG, KIND>), grid, dim3(256), 0, st, logits, target, HW, o)); break;
-    switch (C) {
-      RG_SUMS(2) RG_SUMS(3) RG_SUMS(4) RG_SUMS(8)
-      default: {
-        const size_t sh = (size_t)4 * C * RG_STRIDE * sizeof(float);
-        RG_DISPATCH(target_kind, sq, {
-          if (sh > 48 * 1024) (void)hipFuncSetAttribute   /* (with the static arrays: past 64 KB in all) */
-           ((const void*)rg_softmax_sums_gen_kernel<FLAG, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-          LMN_LAUNCH((rg_softmax_sums_gen_kernel<FLAG, KIND>), grid, dim3(256), sh, st, logits, target, C, HW, o);
-        });
-        break;
+    LOSS_SWITCH_CT(C, LOSS_SWITCH_KIND(target_kind, LOSS_SWITCH_BOOL(SQ, sq, {
+      if constexpr (CT > 0) {
+        LMN_LAUNCH((rg_softmax_sums_kernel<CT, SQ, KIND>), grid, dim3(256), 0, st, logits, target, HW, o);
+      } else {
+        const size_t sh = (size_t)4 * C * LOSS_TILE_STRIDE * sizeof(float);
+        if (sh > 48 * 1024) (void)hipFuncSetAttribute   /* (with the static arrays: past 64 KB in all) */
+         ((const void*)rg_softmax_sums_gen_kernel<SQ, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+        LMN_LAUNCH((rg_softmax_sums_gen_kernel<SQ, KIND>), grid, dim3(256), sh, st, logits, target, C, HW, o);
       }
-    }
-#undef RG_SUMS
+    })));
   } else {
-    const bool vec = HW % 4 == 0 && rg_aligned(logits, 16) && rg_aligned(target, target_kind == LMN_REGION_LABELS_I64 ? 16 : 4);
+    const bool vec = HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(target, target_kind == LMN_REGION_LABELS_I64 ? 16 : 4);
     const dim3 grid(nbx, nk, B);
-    if (sq) RG_DISPATCH(target_kind, vec, LMN_LAUNCH((rg_sigmoid_sums_kernel<FLAG, true, KIND>), grid, dim3(256), 0, st, logits, target, C, HW, o));
-    else RG_DISPATCH(target_kind, vec, LMN_LAUNCH((rg_sigmoid_sums_kernel<FLAG, false, KIND>), grid, dim3(256), 0, st, logits, target, C, HW, o));
+    LOSS_SWITCH_BOOL(SQ, sq, LOSS_SWITCH_KIND(target_kind, LOSS_SWITCH_BOOL(VEC, vec,
+      LMN_LAUNCH((rg_sigmoid_sums_kernel<VEC, SQ, KIND>), grid, dim3(256), 0, st, logits, target, C, HW, o))));
   }
   const RgFin fin{kind, sq ? 1 : 0, G, nk, B, nbx, per_image ? 1 : 0, g_lmn_det ? 1 : 0, alpha, beta, smooth, exponent, scale};
   LMN_LAUNCH(rg_finish_kernel, dim3(1), dim3(256), 0, st, fin, (const float*)o.slots, weight, sums, (const int32_t*)counts, coef, per_class, loss);
@@ -663,23 +578,19 @@ int lmn_region_bwd(const float* logits, const void* target, int target_kind, int
   in.nk = __builtin_popcountll(class_mask);
   in.per_image = per_image ? 1 : 0;
   if (head == LMN_REGION_SOFTMAX) {
-    const dim3 grid(loss_grid(HW, 4096 / B > 0 ? 4096 / B : 1), B);
-#define RG_BWD(CC) \
-  case CC: RG_KIND(target_kind, LMN_LAUNCH((rg_softmax_bwd_kernel<CC, KIND>), grid, dim3(256), 0, st, logits, target, HW, in, gscale, dlogits)); break;
-    switch (C) {
-      RG_BWD(2) RG_BWD(3) RG_BWD(4) RG_BWD(8)
-      default: {
+    const dim3 grid(loss_grid_per(HW, 4096, B), B);
+    LOSS_SWITCH_CT(C, LOSS_SWITCH_KIND(target_kind, {
+      if constexpr (CT > 0) {
+        LMN_LAUNCH((rg_softmax_bwd_kernel<CT, KIND>), grid, dim3(256), 0, st, logits, target, HW, in, gscale, dlogits);
+      } else {
         const size_t sh = (size_t)C * 256 * sizeof(float);   // (<= 64 KB of LDS at C = 64)
-        RG_KIND(target_kind, LMN_LAUNCH((rg_softmax_bwd_gen_kernel<KIND>), grid, dim3(256), sh, st, logits, target, C, HW, in, gscale, dlogits));
-        break;
+        LMN_LAUNCH((rg_softmax_bwd_gen_kernel<KIND>), grid, dim3(256), sh, st, logits, target, C, HW, in, gscale, dlogits);
       }
-    }
-#undef RG_BWD
+    }));
   } else {
-    const bool vec = HW % 4 == 0 && rg_aligned(logits, 16) && rg_aligned(dlogits, 16) && rg_aligned(target, target_kind == LMN_REGION_LABELS_I64 ? 16 : 4);
-    const int64_t planes = (int64_t)B * C;
-    const dim3 grid(loss_grid(vec ? HW / 4 : HW, 4096 / planes > 0 ? 4096 / planes : 1), C, B);
-    RG_DISPATCH(target_kind, vec, LMN_LAUNCH((rg_sigmoid_bwd_kernel<FLAG, KIND>), grid, dim3(256), 0, st, logits, target, C, HW, in, class_mask, gscale, dlogits));
+    const bool vec = HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(dlogits, 16) && lmn_aligned(target, target_kind == LMN_REGION_LABELS_I64 ? 16 : 4);
+    const dim3 grid(loss_grid_per(vec ? HW / 4 : HW, 4096, (int64_t)B * C), C, B);
+    LOSS_SWITCH_KIND(target_kind, LOSS_SWITCH_BOOL(VEC, vec, LMN_LAUNCH((rg_sigmoid_bwd_kernel<VEC, KIND>), grid, dim3(256), 0, st, logits, target, C, HW, in, class_mask, gscale, dlogits)));
   }
   return lmn_launch_status("region_bwd");
 }

@@ -9,50 +9,11 @@
 #include "loss_common.h"
 #include "../../include/lmnet_sigmoid.h"
 
+static_assert(LMN_SIG_T_U8 == LOSS_LABELS_U8 && LMN_SIG_T_I64 == LOSS_LABELS_I64, "loss_common.h reads the target kinds of lmnet_sigmoid.h");
+
 namespace {
 
-constexpr int SG_MAXC = 64;
 constexpr int SG_NSUM = 6, SG_NFLT = 4;   // words per class in sums; the float ones among them (slot copies in deterministic mode)
-
-// E consecutive targets of a plane as 0, 1 or 2 (void: every value but 0 and 1).  KIND 0: uint8, 1: int64.
-template <int KIND, int E>
-__device__ __forceinline__ void sg_load_t(const void* __restrict__ plane, int64_t i, int (&t)[E]) {
-  if constexpr (KIND == LMN_SIG_T_U8) {
-    const uint8_t* p = (const uint8_t*)plane + i;
-    if constexpr (E == 4) {
-      const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t v = (w >> (8 * j)) & 255u;
-        t[j] = v <= 1u ? (int)v : 2;
-      }
-    } else {
-      const uint32_t v = p[0];
-      t[0] = v <= 1u ? (int)v : 2;
-    }
-  } else {
-    const int64_t* p = (const int64_t*)plane + i;
-    if constexpr (E == 4) {
-      const longlong2 a = *reinterpret_cast<const longlong2*>(p), b = *reinterpret_cast<const longlong2*>(p + 2);
-      const int64_t v[4] = {a.x, a.y, b.x, b.y};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) t[j] = (uint64_t)v[j] <= 1ull ? (int)v[j] : 2;
-    } else {
-      const int64_t v = p[0];
-      t[0] = (uint64_t)v <= 1ull ? (int)v : 2;
-    }
-  }
-}
-template <int E>
-__device__ __forceinline__ void sg_load_z(const float* __restrict__ plane, int64_t i, float (&z)[E]) {
-  if constexpr (E == 4) {
-    const f32x4 v = ld4(plane + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) z[j] = v[j];
-  } else {
-    z[0] = plane[i];
-  }
-}
 
 template <int KIND, bool VEC, bool FOCAL>
 __global__ __launch_bounds__(256) void sigloss_sums_kernel(const float* __restrict__ logits, const void* __restrict__ target,
@@ -69,8 +30,8 @@ __global__ __launch_bounds__(256) void sigloss_sums_kernel(const float* __restri
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
     float z[E];
     int t[E];
-    sg_load_z<E>(lg, q * E, z);
-    sg_load_t<KIND, E>(tg, q * E, t);
+    loss_load_z<E>(lg, q * E, z);
+    loss_load_t<KIND, E>(tg, q * E, t);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       if (t[j] > 1) continue;                         // void: adds to no sum
@@ -164,8 +125,8 @@ __global__ __launch_bounds__(256) void sigloss_bwd_kernel(const float* __restric
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
     float z[E], d[E];
     int t[E];
-    sg_load_z<E>(lg, q * E, z);
-    sg_load_t<KIND, E>(tg, q * E, t);
+    loss_load_z<E>(lg, q * E, z);
+    loss_load_t<KIND, E>(tg, q * E, t);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       d[j] = 0.f;                                     // void: +0
@@ -177,8 +138,7 @@ __global__ __launch_bounds__(256) void sigloss_bwd_kernel(const float* __restric
       if (FOCAL) v += k_f * focal_grad(s, on, fk);
       d[j] = gs * v;
     }
-    if constexpr (VEC) st4(dl + q * 4, f32x4{d[0], d[1], d[2], d[3]});
-    else dl[q] = d[0];
+    loss_store<E>(dl, q * E, d);
   }
 }
 
@@ -203,8 +163,8 @@ __global__ __launch_bounds__(256) void sigmoid_stats_kernel(const float* __restr
 #pragma unroll
     for (int j = 0; j < E; ++j) { z[j] = 0.f; t[j] = 2; }
     if (in) {
-      sg_load_z<E>(lg, q * E, z);
-      if constexpr (HAS_T) sg_load_t<KIND, E>(tg, q * E, t);
+      loss_load_z<E>(lg, q * E, z);
+      if constexpr (HAS_T) loss_load_t<KIND, E>(tg, q * E, t);
     }
     uint32_t packed = 0;
 #pragma unroll
@@ -240,13 +200,8 @@ __global__ __launch_bounds__(256) void sigmoid_stats_kernel(const float* __restr
   }
 }
 
-// blocks per plane: enough for one 256-lane trip each, capped so that the whole grid stays near `cap` blocks
-inline int sg_grid_x(int64_t items, int planes, int cap) { return loss_grid(items, cap / planes > 0 ? cap / planes : 1); }
-
-inline bool sg_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 int sg_check_sizes(const char* what, int B, int C, int64_t HW) {
-  LMN_REQUIRE(C >= 1 && C <= SG_MAXC, "%s: C=%d not in [1, %d]", what, C, SG_MAXC);
+  LMN_REQUIRE(C >= 1 && C <= LOSS_MAXC, "%s: C=%d not in [1, %d]", what, C, LOSS_MAXC);
   LMN_REQUIRE(B > 0 && HW > 0 && HW < (1LL << 31) && (int64_t)B * C <= 65535 && (int64_t)B * HW < (1LL << 31),
               "%s: B=%d, C=%d, HW=%lld (need B >= 1, 1 <= HW < 2^31, B * C <= 65535, B * HW < 2^31)", what, B, C, (long long)HW);
   return 0;
@@ -259,18 +214,6 @@ int sg_check(const char* what, int B, int C, int64_t HW, const lmn_sig_param_t* 
   LMN_REQUIRE(p->target_kind == LMN_SIG_T_U8 || p->target_kind == LMN_SIG_T_I64, "%s: unknown target_kind %d", what, (int)p->target_kind);
   return 0;
 }
-
-// run `...` once with the compile-time constants KIND, VEC of the call
-#define SG_DISPATCH(kind, vec, ...)                                                        \
-  do {                                                                                     \
-    if ((kind) == LMN_SIG_T_I64) {                                                         \
-      if (vec) { constexpr int KIND = LMN_SIG_T_I64; constexpr bool VEC = true; __VA_ARGS__; }  \
-      else { constexpr int KIND = LMN_SIG_T_I64; constexpr bool VEC = false; __VA_ARGS__; }     \
-    } else {                                                                               \
-      if (vec) { constexpr int KIND = LMN_SIG_T_U8; constexpr bool VEC = true; __VA_ARGS__; }   \
-      else { constexpr int KIND = LMN_SIG_T_U8; constexpr bool VEC = false; __VA_ARGS__; }      \
-    }                                                                                      \
-  } while (0)
 
 }  // namespace
 
@@ -285,9 +228,9 @@ int lmn_sigloss_fwd(const float* logits, const void* target, const float* w_bce,
   hipStream_t st = (hipStream_t)stream;
   const bool focal = param->focal_scale > 0.f;
   const int kind = param->target_kind;
-  const bool vec = HW % 4 == 0 && sg_aligned(logits, 16) && sg_aligned(target, kind == LMN_SIG_T_I64 ? 16 : 4);
+  const bool vec = HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(target, kind == LMN_SIG_T_I64 ? 16 : 4);
   const int planes = B * C;
-  const int gx = sg_grid_x(vec ? HW / 4 : HW, planes, 2048);
+  const int gx = loss_grid_per(vec ? HW / 4 : HW, 2048, planes);
   const FocalK fk{param->focal_gamma, param->focal_alpha};
   const SgFinishK fin{param->smooth, param->bce_scale, param->dice_scale, param->focal_scale};
   LMN_LAUNCH(loss_zero_kernel, dim3(1), dim3(256), 0, st, (uint32_t*)sums, (int64_t)LMN_SIG_SUMS_WORDS(C));
@@ -297,10 +240,8 @@ int lmn_sigloss_fwd(const float* logits, const void* target, const float* w_bce,
     slots = lmn_det_slots(st, (size_t)B * gx * SG_NFLT * C);
     LMN_REQUIRE(slots, "sigloss_fwd: deterministic mode: no scratch");
   }
-  SG_DISPATCH(kind, vec, {
-    if (focal) LMN_LAUNCH((sigloss_sums_kernel<KIND, VEC, true>), dim3(gx, planes), dim3(256), 0, st, logits, target, pos_weight, C, HW, fk, (uint32_t*)sums, slots);
-    else LMN_LAUNCH((sigloss_sums_kernel<KIND, VEC, false>), dim3(gx, planes), dim3(256), 0, st, logits, target, pos_weight, C, HW, fk, (uint32_t*)sums, slots);
-  });
+  LOSS_SWITCH_KIND(kind, LOSS_SWITCH_BOOL(VEC, vec, LOSS_SWITCH_BOOL(FOCAL, focal,
+    LMN_LAUNCH((sigloss_sums_kernel<KIND, VEC, FOCAL>), dim3(gx, planes), dim3(256), 0, st, logits, target, pos_weight, C, HW, fk, (uint32_t*)sums, slots))));
   if (slots) lmn_det_sum(st, slots, B * gx, (int64_t)SG_NFLT * C, (float*)sums + 2 * C);
   LMN_LAUNCH(sigloss_finish_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)sums, w_bce, w_dice, C, fin, loss4, coef);
   return lmn_launch_status("sigloss_fwd");
@@ -313,14 +254,12 @@ int lmn_sigloss_bwd(const float* logits, const void* target, const float* pos_we
   hipStream_t st = (hipStream_t)stream;
   const bool focal = param->focal_scale > 0.f;
   const int kind = param->target_kind;
-  const bool vec = HW % 4 == 0 && sg_aligned(logits, 16) && sg_aligned(dlogits, 16) && sg_aligned(target, kind == LMN_SIG_T_I64 ? 16 : 4);
+  const bool vec = HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(dlogits, 16) && lmn_aligned(target, kind == LMN_SIG_T_I64 ? 16 : 4);
   const int planes = B * C;
-  const int gx = sg_grid_x(vec ? HW / 4 : HW, planes, 4096);
+  const int gx = loss_grid_per(vec ? HW / 4 : HW, 4096, planes);
   const FocalK fk{param->focal_gamma, param->focal_alpha};
-  SG_DISPATCH(kind, vec, {
-    if (focal) LMN_LAUNCH((sigloss_bwd_kernel<KIND, VEC, true>), dim3(gx, planes), dim3(256), 0, st, logits, target, pos_weight, coef, gscale, C, HW, fk, dlogits);
-    else LMN_LAUNCH((sigloss_bwd_kernel<KIND, VEC, false>), dim3(gx, planes), dim3(256), 0, st, logits, target, pos_weight, coef, gscale, C, HW, fk, dlogits);
-  });
+  LOSS_SWITCH_KIND(kind, LOSS_SWITCH_BOOL(VEC, vec, LOSS_SWITCH_BOOL(FOCAL, focal,
+    LMN_LAUNCH((sigloss_bwd_kernel<KIND, VEC, FOCAL>), dim3(gx, planes), dim3(256), 0, st, logits, target, pos_weight, coef, gscale, C, HW, fk, dlogits))));
   return lmn_launch_status("sigloss_bwd");
 }
 
@@ -334,21 +273,19 @@ int lmn_sigmoid_stats(const float* logits, const void* target, int target_kind, 
   if (int rc = sg_check_sizes("sigmoid_stats", B, C, HW)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const bool has_t = stats != nullptr;                // (a target without stats is not read)
-  const bool vec = HW % 4 == 0 && sg_aligned(logits, 16) && (!has_t || sg_aligned(target, target_kind == LMN_SIG_T_I64 ? 16 : 4)) &&
-                   (!labels_out || sg_aligned(labels_out, 4));
+  const bool vec = HW % 4 == 0 && lmn_aligned(logits, 16) && (!has_t || lmn_aligned(target, target_kind == LMN_SIG_T_I64 ? 16 : 4)) &&
+                   (!labels_out || lmn_aligned(labels_out, 4));
   const int planes = B * C;
-  const int gx = sg_grid_x(vec ? HW / 4 : HW, planes, 1024);
+  const int gx = loss_grid_per(vec ? HW / 4 : HW, 1024, planes);
   unsigned long long* so = (unsigned long long*)stats;
   if (has_t) {
     const int64_t words = (int64_t)planes * 8;
     LMN_LAUNCH(loss_zero_kernel, dim3(loss_grid(words, 64)), dim3(256), 0, st, (uint32_t*)stats, words);
-    SG_DISPATCH(target_kind, vec, {
-      LMN_LAUNCH((sigmoid_stats_kernel<KIND, VEC, true>), dim3(gx, planes), dim3(256), 0, st, logits, target, logit_threshold, HW, so, labels_out);
-    });
+    LOSS_SWITCH_KIND(target_kind, LOSS_SWITCH_BOOL(VEC, vec,
+      LMN_LAUNCH((sigmoid_stats_kernel<KIND, VEC, true>), dim3(gx, planes), dim3(256), 0, st, logits, target, logit_threshold, HW, so, labels_out)));
   } else {
-    SG_DISPATCH(LMN_SIG_T_U8, vec, {
-      LMN_LAUNCH((sigmoid_stats_kernel<KIND, VEC, false>), dim3(gx, planes), dim3(256), 0, st, logits, target, logit_threshold, HW, so, labels_out);
-    });
+    LOSS_SWITCH_KIND(LOSS_LABELS_U8, LOSS_SWITCH_BOOL(VEC, vec,
+      LMN_LAUNCH((sigmoid_stats_kernel<KIND, VEC, false>), dim3(gx, planes), dim3(256), 0, st, logits, target, logit_threshold, HW, so, labels_out)));
   }
   return lmn_launch_status("sigmoid_stats");
 }

@@ -19,8 +19,7 @@ static_assert(LMN_SOFT_LABELS_U8 == LOSS_LABELS_U8 && LMN_SOFT_LABELS_I64 == LOS
 
 namespace {
 
-constexpr int SF_MAXC = 64;
-constexpr int SF_MAXNS = 1 + 3 * SF_MAXC;
+constexpr int SF_MAXNS = 1 + 3 * LOSS_MAXC;
 
 struct SfArgs {
   const float* logits;
@@ -41,12 +40,6 @@ struct SfOut {
   float* slots;   // deterministic mode, else NULL
   int ns;
 };
-
-__device__ __forceinline__ double sf_wave_sum(double v) {
-#pragma unroll
-  for (int m = 1; m <= 32; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // The ONE log routine: lse of v / T over the C classes of a pixel (max-subtracted), then log softmax(v / T)_c = sf_logp(v_c, T, s).
 // log q of the teacher and log p of the student both come from here; the division and the subtractions are compiled without contraction
@@ -266,7 +259,7 @@ __global__ __launch_bounds__(CT > 0 ? 256 : 64) void sf_softmax_bwd_kernel(SfArg
   constexpr int NT = CT > 0 ? 256 : 64, UNR = CT > 0 ? CT : 1;
   constexpr bool TEACH = READER >= LMN_SOFT_TEACHER_F32;
   extern __shared__ float sf_lds[];
-  __shared__ float s_a[SF_MAXC], s_c[SF_MAXC], s_w[SF_MAXC];
+  __shared__ float s_a[LOSS_MAXC], s_c[LOSS_MAXC], s_w[LOSS_MAXC];
   const int C = CT > 0 ? CT : a.C, b = blockIdx.y, lane = threadIdx.x & 63;
   if (!TEACH && (int)threadIdx.x < C) {
     s_a[threadIdx.x] = coef[1 + 2 * threadIdx.x];
@@ -333,18 +326,6 @@ __global__ __launch_bounds__(CT > 0 ? 256 : 64) void sf_softmax_bwd_kernel(SfArg
   }
 }
 
-// E consecutive elements of a plane of teacher logits (fp32 or bf16) or student logits
-template <typename TT, int E>
-__device__ __forceinline__ void sf_load(const TT* __restrict__ plane, int64_t i, float (&v)[E]) {
-  if constexpr (E == 4) {
-    const f32x4 r = ld4(plane + i);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = r[k];
-  } else {
-    v[0] = ld1(plane + i);
-  }
-}
-
 // the Bernoulli divergence of one element and the two probabilities: q = sigmoid(zt / T), p = sigmoid(z / T), every log a softplus of
 // the same sig_point
 __device__ __forceinline__ float sf_sig_kl(float z, float zt, float T, float& p, float& q) {
@@ -368,8 +349,8 @@ __global__ __launch_bounds__(256) void sf_sigmoid_sums_kernel(SfArgs a, SfOut o)
   const int64_t items = a.hw / E;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
     float z[E], zt[E];
-    sf_load<float, E>(lg, q * E, z);
-    sf_load<TT, E>(tg, q * E, zt);
+    loss_load_z<E>(lg, q * E, z);
+    loss_load_z<E>(tg, q * E, zt);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       if (a.ya && (uint64_t)loss_label(a.ya, a.kind, plane + q * E + j) > 1ull) continue;   // void: adds to no sum
@@ -409,8 +390,8 @@ __global__ __launch_bounds__(256) void sf_sigmoid_bwd_kernel(SfArgs a, const flo
   const int64_t items = a.hw / E;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
     float z[E], zt[E], d[E];
-    sf_load<float, E>(lg, q * E, z);
-    sf_load<TT, E>(tg, q * E, zt);
+    loss_load_z<E>(lg, q * E, z);
+    loss_load_z<E>(tg, q * E, zt);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
       d[j] = 0.f;                                        // void: +0
@@ -419,8 +400,7 @@ __global__ __launch_bounds__(256) void sf_sigmoid_bwd_kernel(SfArgs a, const flo
       (void)sf_sig_kl(z[j], zt[j], a.T, p, qq);
       d[j] = gs * (c0 * (p - qq));
     }
-    if constexpr (VEC) st4(dl + q * 4, f32x4{d[0], d[1], d[2], d[3]});
-    else dl[q] = d[0];
+    loss_store<E>(dl, q * E, d);
   }
 }
 
@@ -435,13 +415,13 @@ struct SfFin {
 __global__ __launch_bounds__(256) void sf_finish_kernel(SfFin f, const float* __restrict__ slots, const float* __restrict__ w_dice,
                                                         float* __restrict__ sums, const int32_t* __restrict__ counts, float* __restrict__ coef,
                                                         float* __restrict__ terms) {
-  __shared__ double s_part[SF_MAXC];
+  __shared__ double s_part[LOSS_MAXC];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (f.det) {
     for (int e = wv; e < f.ns; e += 4) {
       double v = 0.0;
       for (int64_t j = lane; j < f.nslots; j += 64) v += (double)slots[j * f.ns + e];
-      v = sf_wave_sum(v);
+      v = loss_wave_sum(v);
       if (lane == 0) sums[e] = (float)v;
     }
     __syncthreads();
@@ -479,20 +459,17 @@ __global__ __launch_bounds__(256) void sf_finish_kernel(SfFin f, const float* __
   }
 }
 
-inline bool sf_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 inline bool sf_teacher(int reader) { return reader == LMN_SOFT_TEACHER_F32 || reader == LMN_SOFT_TEACHER_BF16; }
-inline bool sf_templated(int C) { return C == 2 || C == 3 || C == 4 || C == 8; }
 
 // blocks of the sums pass per image (softmax head) or per plane (sigmoid head): a function of reader, head, B, C and HW alone, so that
 // lmn_soft_workspace can state the slots exactly
 inline int sf_nbx(int reader, int head, int B, int C, int64_t HW) {
   if (head == LMN_SOFT_SOFTMAX) {
     const int64_t items = (reader == LMN_SOFT_TEACHER_BF16 && HW % 4 == 0) ? HW / 4 : HW;
-    const int64_t cap = 1024 / B > 0 ? 1024 / B : 1;
-    return sf_templated(C) ? loss_grid(items, cap) : loss_grid(items * 4, cap * 4);   // (general C: blocks of 64 lanes)
+    const int64_t cap = loss_cap(1024, B);
+    return loss_templated(C) ? loss_grid(items, cap) : loss_grid(items * 4, cap * 4);   // (general C: blocks of 64 lanes)
   }
-  const int64_t planes = (int64_t)B * C;
-  return loss_grid(HW % 4 == 0 ? HW / 4 : HW, 2048 / planes > 0 ? 2048 / planes : 1);
+  return loss_grid_per(HW % 4 == 0 ? HW / 4 : HW, 2048, (int64_t)B * C);
 }
 inline int64_t sf_nslots(int reader, int head, int B, int C, int64_t HW) {
   return (int64_t)B * (head == LMN_SOFT_SIGMOID ? C : 1) * sf_nbx(reader, head, B, C, HW);
@@ -508,16 +485,14 @@ int sf_check(const char* what, int reader, int head, int label_kind, int B, int 
   LMN_REQUIRE(head == LMN_SOFT_SOFTMAX || sf_teacher(reader), "%s: reader %d needs a softmax head", what, reader);
   LMN_REQUIRE(B >= 1 && B <= LMN_SOFT_MAX_BATCH, "%s: B=%d not in [1, %d]", what, B, LMN_SOFT_MAX_BATCH);
   if (int rc = loss_check_head(what, C, head == LMN_SOFT_SOFTMAX, 1ull, label_kind)) return rc;
-  LMN_REQUIRE(H >= 1 && W >= 1, "%s: size %dx%d below 1", what, H, W);
-  LMN_REQUIRE((int64_t)B * C * H * W < (1LL << 31), "%s: B * C * H * W = %lld not below 2^31", what, (long long)B * C * H * W);
-  return 0;
+  return loss_check_extent(what, B, C, H, W);
 }
 
 int sf_check_target(const char* what, int reader, const void* target, const void* ya, const void* yb, const float* lam, float T) {
   if (reader == LMN_SOFT_PAIR) LMN_REQUIRE(ya && yb && lam && !target, "%s: the pair reader takes ya, yb and lam and no target", what);
   else LMN_REQUIRE(target && !yb && !lam, "%s: reader %d takes a target and neither yb nor lam", what, reader);
   LMN_REQUIRE(reader != LMN_SOFT_PROBS || !ya, "%s: the probability reader takes no label map", what);
-  LMN_REQUIRE(T > 0.f && T - T == 0.f, "%s: temperature=%g must be finite and > 0", what, (double)T);
+  LMN_REQUIRE(T > 0.f && loss_finite(T), "%s: temperature=%g must be finite and > 0", what, (double)T);
   LMN_REQUIRE(sf_teacher(reader) || T == 1.f, "%s: temperature=%g without a teacher", what, (double)T);
   return 0;
 }
@@ -527,35 +502,14 @@ inline size_t sf_lds_bytes(int reader, int C, int E) {
   return (size_t)C * 64 * 4 * (reader == LMN_SOFT_PAIR ? 1 : (E == 4 ? 3 : 2));
 }
 
-// run `...` once with the compile-time constants CT, READER and E of the call
-#define SF_READER(CTV, reader, e4, ...)                                                                                  \
+// run `...` once with the compile-time constants READER and E of the call
+#define SF_READER(reader, e4, ...)                                                                                       \
   do {                                                                                                                   \
-    constexpr int CT = CTV;                                                                                              \
     if ((reader) == LMN_SOFT_PROBS) { constexpr int READER = LMN_SOFT_PROBS; constexpr int E = 1; __VA_ARGS__; }         \
     else if ((reader) == LMN_SOFT_PAIR) { constexpr int READER = LMN_SOFT_PAIR; constexpr int E = 1; __VA_ARGS__; }      \
     else if ((reader) == LMN_SOFT_TEACHER_F32) { constexpr int READER = LMN_SOFT_TEACHER_F32; constexpr int E = 1; __VA_ARGS__; } \
     else if (e4) { constexpr int READER = LMN_SOFT_TEACHER_BF16; constexpr int E = 4; __VA_ARGS__; }                     \
     else { constexpr int READER = LMN_SOFT_TEACHER_BF16; constexpr int E = 1; __VA_ARGS__; }                             \
-  } while (0)
-#define SF_SOFTMAX(C, reader, e4, ...)                      \
-  do {                                                      \
-    switch (C) {                                            \
-      case 2: SF_READER(2, reader, e4, __VA_ARGS__); break; \
-      case 3: SF_READER(3, reader, e4, __VA_ARGS__); break; \
-      case 4: SF_READER(4, reader, e4, __VA_ARGS__); break; \
-      case 8: SF_READER(8, reader, e4, __VA_ARGS__); break; \
-      default: SF_READER(0, reader, e4, __VA_ARGS__); break; \
-    }                                                       \
-  } while (0)
-#define SF_SIGMOID(vec, bf, ...)                                                             \
-  do {                                                                                       \
-    if (vec) {                                                                               \
-      if (bf) { constexpr bool VEC = true; constexpr bool BF = true; __VA_ARGS__; }          \
-      else { constexpr bool VEC = true; constexpr bool BF = false; __VA_ARGS__; }            \
-    } else {                                                                                 \
-      if (bf) { constexpr bool VEC = false; constexpr bool BF = true; __VA_ARGS__; }         \
-      else { constexpr bool VEC = false; constexpr bool BF = false; __VA_ARGS__; }           \
-    }                                                                                        \
   } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------- the batch mixer
@@ -587,10 +541,10 @@ __global__ __launch_bounds__(256) void mix_batch_kernel(const float* __restrict_
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < items; q += (int64_t)gridDim.x * 256) {
       const int64_t i = q * E;
       float va[E], vo[E];
-      sf_load<float, E>(xa, i, va);
+      loss_load_z<E>(xa, i, va);
       if (r.mode == LMN_MIX_MIXUP) {
         float vb[E];
-        sf_load<float, E>(xb, i, vb);
+        loss_load_z<E>(xb, i, vb);
 #pragma unroll
         for (int k = 0; k < E; ++k) vo[k] = mix_unfused(r.lam, va[k], r.oml, vb[k]);
       } else {
@@ -600,15 +554,14 @@ __global__ __launch_bounds__(256) void mix_batch_kernel(const float* __restrict_
           const int yy = (int)(i / W), xx = (int)(i - (int64_t)yy * W);   // (VEC: W % 4 == 0, the four pixels share a row)
           if (yy >= r.y0 && yy < r.y1 && xx + E > r.x0 && xx < r.x1) {
             float vb[E];
-            sf_load<float, E>(xb, i, vb);
+            loss_load_z<E>(xb, i, vb);
 #pragma unroll
             for (int k = 0; k < E; ++k)
               if (xx + k >= r.x0 && xx + k < r.x1) vo[k] = vb[k];
           }
         }
       }
-      if constexpr (VEC) st4(xo + i, f32x4{vo[0], vo[1], vo[2], vo[3]});
-      else xo[i] = vo[0];
+      loss_store<E>(xo, i, vo);
     }
     return;
   }
@@ -651,8 +604,8 @@ int lmn_soft_fwd(const float* logits, int reader, int head, const void* target, 
   if (int rc = sf_check("soft_fwd", reader, head, label_kind, B, C, H, W)) return rc;
   if (int rc = sf_check_target("soft_fwd", reader, target, ya, yb, lam, temperature)) return rc;
   LMN_REQUIRE(eps >= 0.f && eps <= 1.f, "soft_fwd: label smoothing eps=%g not in [0, 1]", (double)eps);
-  LMN_REQUIRE(smooth >= 0.f && smooth - smooth == 0.f, "soft_fwd: smooth=%g must be finite and >= 0", (double)smooth);
-  LMN_REQUIRE(ce_scale - ce_scale == 0.f && dice_scale - dice_scale == 0.f, "soft_fwd: scale (%g, %g) is not finite", (double)ce_scale,
+  LMN_REQUIRE(smooth >= 0.f && loss_finite(smooth), "soft_fwd: smooth=%g must be finite and >= 0", (double)smooth);
+  LMN_REQUIRE(loss_finite(ce_scale) && loss_finite(dice_scale), "soft_fwd: scale (%g, %g) is not finite", (double)ce_scale,
               (double)dice_scale);
   LMN_REQUIRE(!sf_teacher(reader) || (!w_ce && !w_dice), "soft_fwd: the teacher readers take no class weight");
   const int64_t HW = (int64_t)H * W;
@@ -668,16 +621,16 @@ int lmn_soft_fwd(const float* logits, int reader, int head, const void* target, 
   const bool bf = reader == LMN_SOFT_TEACHER_BF16;
   if (head == LMN_SOFT_SOFTMAX) {
     // (sf_nbx sizes the grid from HW alone; with an unaligned base the one-pixel instance runs on the same grid: its loop strides)
-    const bool e4 = bf && HW % 4 == 0 && sf_aligned(logits, 16) && sf_aligned(target, 8);
+    const bool e4 = bf && HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(target, 8);
     const dim3 grid(nbx, B);
-    SF_SOFTMAX(C, reader, e4, {
+    LOSS_SWITCH_CT(C, SF_READER(reader, e4, {
       const size_t sh = CT > 0 ? 0 : sf_lds_bytes(reader, C, E);
       LMN_LAUNCH((sf_softmax_sums_kernel<CT, READER, E>), grid, dim3(CT > 0 ? 256 : 64), sh, st, a, o);
-    });
+    }));
   } else {
-    const bool vec = HW % 4 == 0 && sf_aligned(logits, 16) && sf_aligned(target, bf ? 8 : 16);
+    const bool vec = HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(target, bf ? 8 : 16);
     const dim3 grid(nbx, C, B);
-    SF_SIGMOID(vec, bf, LMN_LAUNCH((sf_sigmoid_sums_kernel<VEC, BF>), grid, dim3(256), 0, st, a, o));
+    LOSS_SWITCH_BOOL(VEC, vec, LOSS_SWITCH_BOOL(BF, bf, LMN_LAUNCH((sf_sigmoid_sums_kernel<VEC, BF>), grid, dim3(256), 0, st, a, o)));
   }
   const SfFin fin{sf_teacher(reader) ? 1 : 0, C, ns, g_lmn_det ? 1 : 0, sf_nslots(reader, head, B, C, HW), temperature, smooth, ce_scale, dice_scale};
   LMN_LAUNCH(sf_finish_kernel, dim3(1), dim3(256), 0, st, fin, (const float*)o.slots, w_dice, sums, (const int32_t*)counts, coef, terms);
@@ -697,18 +650,17 @@ int lmn_soft_bwd(const float* logits, int reader, int head, const void* target, 
   const SfArgs a{logits, target, ya, yb, lam, w_ce, label_kind, C, HW, temperature, eps};
   const bool bf = reader == LMN_SOFT_TEACHER_BF16;
   if (head == LMN_SOFT_SOFTMAX) {
-    const bool e4 = bf && HW % 4 == 0 && sf_aligned(logits, 16) && sf_aligned(dlogits, 16) && sf_aligned(target, 8);
-    const int64_t items = e4 ? HW / 4 : HW, cap = 4096 / B > 0 ? 4096 / B : 1;
-    const dim3 grid(sf_templated(C) ? loss_grid(items, cap) : loss_grid(items * 4, cap * 4), B);
-    SF_SOFTMAX(C, reader, e4, {
+    const bool e4 = bf && HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(dlogits, 16) && lmn_aligned(target, 8);
+    const int64_t items = e4 ? HW / 4 : HW, cap = loss_cap(4096, B);
+    const dim3 grid(loss_templated(C) ? loss_grid(items, cap) : loss_grid(items * 4, cap * 4), B);
+    LOSS_SWITCH_CT(C, SF_READER(reader, e4, {
       const size_t sh = CT > 0 ? 0 : sf_lds_bytes(reader, C, E);
       LMN_LAUNCH((sf_softmax_bwd_kernel<CT, READER, E>), grid, dim3(CT > 0 ? 256 : 64), sh, st, a, coef, gscale, dlogits);
-    });
+    }));
   } else {
-    const bool vec = HW % 4 == 0 && sf_aligned(logits, 16) && sf_aligned(dlogits, 16) && sf_aligned(target, bf ? 8 : 16);
-    const int64_t planes = (int64_t)B * C;
-    const dim3 grid(loss_grid(vec ? HW / 4 : HW, 4096 / planes > 0 ? 4096 / planes : 1), C, B);
-    SF_SIGMOID(vec, bf, LMN_LAUNCH((sf_sigmoid_bwd_kernel<VEC, BF>), grid, dim3(256), 0, st, a, coef, gscale, dlogits));
+    const bool vec = HW % 4 == 0 && lmn_aligned(logits, 16) && lmn_aligned(dlogits, 16) && lmn_aligned(target, bf ? 8 : 16);
+    const dim3 grid(loss_grid_per(vec ? HW / 4 : HW, 4096, (int64_t)B * C), C, B);
+    LOSS_SWITCH_BOOL(VEC, vec, LOSS_SWITCH_BOOL(BF, bf, LMN_LAUNCH((sf_sigmoid_bwd_kernel<VEC, BF>), grid, dim3(256), 0, st, a, coef, gscale, dlogits)));
   }
   return lmn_launch_status("soft_bwd");
 }
@@ -737,11 +689,9 @@ int lmn_mix_batch(const float* x, const void* y, int label_kind, const int32_t* 
   }
   hipStream_t st = (hipStream_t)stream;
   LMN_HIP_OK(hipMemcpyAsync(rows_dev, rows, sizeof(MixRow) * (size_t)B, hipMemcpyHostToDevice, st), "mix_batch");
-  const bool vec = W % 4 == 0 && sf_aligned(x, 16) && sf_aligned(x_out, 16);
-  const int64_t planes = (int64_t)B * (Cin + 1);
-  const dim3 grid(loss_grid(vec ? HW / 4 : HW, 4096 / planes > 0 ? 4096 / planes : 1), Cin + 1, B);
-  if (vec) LMN_LAUNCH((mix_batch_kernel<true>), grid, dim3(256), 0, st, x, y, label_kind, (const MixRow*)rows_dev, Cin, H, W, x_out, ya_out, yb_out, lam_out);
-  else LMN_LAUNCH((mix_batch_kernel<false>), grid, dim3(256), 0, st, x, y, label_kind, (const MixRow*)rows_dev, Cin, H, W, x_out, ya_out, yb_out, lam_out);
+  const bool vec = W % 4 == 0 && lmn_aligned(x, 16) && lmn_aligned(x_out, 16);
+  const dim3 grid(loss_grid_per(vec ? HW / 4 : HW, 4096, (int64_t)B * (Cin + 1)), Cin + 1, B);
+  LOSS_SWITCH_BOOL(VEC, vec, LMN_LAUNCH((mix_batch_kernel<VEC>), grid, dim3(256), 0, st, x, y, label_kind, (const MixRow*)rows_dev, Cin, H, W, x_out, ya_out, yb_out, lam_out));
   return lmn_launch_status("mix_batch");
 }
 
