@@ -252,9 +252,10 @@ def optim_workspace_words(n):
     return 2 * optim_blocks(n) + OPTIM_CTRL_WORDS + OPTIM_GROUP_WORDS if n > 0 else 0
 
 
-# The C ABI, one list per header: every symbol that header declares.  The headers stay apart, one per feature; HEADERS is the one
-# registry of them.  load() checks the library against it, tests/test_host_cpu.py checks it against the headers, and the guard manifest
-# (tests/guard.py) partitions EXPORTS, so that a new export in any header needs a guard test or a stated reason why none applies.
+# The C ABI, one list per header: every symbol that header declares.  The headers stay apart, one per feature; HEADERS (below the
+# lists) is the one registry of all sixteen.  load() checks the library against it, tests/test_host_cpu.py checks it against the
+# headers, and the guard manifest (tests/guard.py) partitions EXPORTS, so that a new export in any header needs a guard test or a
+# stated reason why none applies.  A new header joins by its list and its line in HEADERS (and STRUCTS / RETURNS_INT64 where they apply).
 SYMBOLS = [
     "lmn_abi_version", "lmn_sizeof_conv_args", "lmn_sizeof_src", "lmn_sizeof_wgrad_args", "lmn_last_error",
     "lmn_conv_pack_size", "lmn_conv_pack", "lmn_conv_pack_batch", "lmn_sizeof_pack_job", "lmn_conv_fwd", "lmn_conv_dma_config", "lmn_conv_chain_ok", "lmn_conv_wgrad", "lmn_conv_wgrad_workspace",
@@ -277,59 +278,35 @@ SYMBOLS_LOSS = ["lmn_sizeof_loss_param", "lmn_segloss_ex_fwd", "lmn_segloss_ex_b
 # include/lmnet_sigmoid.h: the loss and the statistics of sigmoid heads
 SYMBOLS_SIGMOID = ["lmn_sizeof_sig_param", "lmn_sigloss_fwd", "lmn_sigloss_bwd", "lmn_sigmoid_stats"]
 
-HEADERS = {"lmnet_hip.h": SYMBOLS, "lmnet_oneof.h": SYMBOLS_ONEOF, "lmnet_loss.h": SYMBOLS_LOSS, "lmnet_sigmoid.h": SYMBOLS_SIGMOID}
-EXPORTS = [name for names in HEADERS.values() for name in names]
-
-# every struct mirror whose size the library reports, with the export that reports it.  (DwPre, SeFuse, SeBwd and SeParamsT
-# have no lmn_sizeof_* export and stay unchecked.)
-STRUCTS = [(ConvArgs, "lmn_sizeof_conv_args"), (SrcT, "lmn_sizeof_src"), (WgradArgs, "lmn_sizeof_wgrad_args"),
-           (PackJob, "lmn_sizeof_pack_job"), (ReduceJob, "lmn_sizeof_reduce_job"), (AugParam, "lmn_sizeof_aug_param"),
-           (PostParam, "lmn_sizeof_post_param"), (OneOfParam, "lmn_sizeof_oneof_param"), (LossParam, "lmn_sizeof_loss_param"),
-           (SigParam, "lmn_sizeof_sig_param")]
-
-# include/optim/lmnet_optim.h: parameter groups, clipping, the loss-scale skip and EMA of the one-launch AdamW.  A list of its own
-# beside EXPORTS: HEADERS / STRUCTS and the guard manifest are pinned by tests/test_host_cpu.py and tests/guard.py as they stand.
-# load() checks these symbols and the struct size all the same; tests/test_optim_cpu.py checks the list against the header and
-# ties the entries that write device memory to tests/test_guard_optim_gpu.py.
+# include/optim/lmnet_optim.h: groups, clipping, the loss-scale skip and EMA of the one-launch AdamW (lm_net_amd.optim.FusedAdamW)
 SYMBOLS_OPTIM = ["lmn_sizeof_optim_param", "lmn_optim_workspace", "lmn_optim_prepare", "lmn_adamw_step_ex"]
 
-# include/tiles/lmnet_tiles.h: tiled and flip-averaged inference (lm_net_amd.infer.TiledPredictor).  A list of its own for the same
-# reason; tests/test_tiles_cpu.py checks it against the header and ties the two entries to tests/test_guard_tiles_gpu.py.
+# include/tiles/lmnet_tiles.h: tiled and flip-averaged inference (lm_net_amd.infer.TiledPredictor)
 SYMBOLS_TILES = ["lmn_sizeof_tile_param", "lmn_tile_gather", "lmn_tile_blend"]
 
-# include/curves/lmnet_curves.h: score histograms over a threshold table (lm_net_amd.metrics.CurveMeter).  A list of its own for the
-# same reason, and no struct; tests/test_curves_cpu.py checks it against the header and ties lmn_curve_hist to
-# tests/test_guard_curves_gpu.py.
+# include/curves/lmnet_curves.h: score histograms over a threshold table (lm_net_amd.metrics.CurveMeter)
 SYMBOLS_CURVES = ["lmn_curve_workspace", "lmn_curve_hist"]
 
-# include/volume/lmnet_volume.h: per-case 3D surface distances and overlap (lm_net_amd.metrics.VolumeSurfaceMeter).  A list of its own
-# for the same reason, and no struct; tests/test_volume_cpu.py checks it against the header and ties the two entries that write device
-# memory to tests/test_guard_volume_gpu.py.
+# include/volume/lmnet_volume.h: per-case 3D surface distances and overlap (lm_net_amd.metrics.VolumeSurfaceMeter)
 SYMBOLS_VOLUME = ["lmn_volume_workspace", "lmn_volume_labels", "lmn_volume_dist"]
 VOLUME_MAX_SIDE = 1024       # LMN_VOLUME_* of the header
 VOLUME_NSTAT_I = 9
 VOLUME_NSTAT_F = 2
 
-# include/volpost/lmnet_volpost.h: 3D connected-component cleaning of a label volume (lm_net_amd.post.VolumePostprocess).  A list of its
-# own for the same reason, and no struct; tests/test_volpost_cpu.py checks it against the header and ties the two entries that write
-# device memory to tests/test_guard_volpost_gpu.py.
+# include/volpost/lmnet_volpost.h: 3D connected-component cleaning of a label volume (lm_net_amd.post.VolumePostprocess)
 SYMBOLS_VOLPOST = ["lmn_volpost_workspace", "lmn_cc3d_label", "lmn_volpost_clean"]
 VOLPOST_MAX_SIDE = 1024      # LMN_VOLPOST_* of the header
 VOLPOST_MAX_KEEP = 4
 VOLPOST_NSTAT = 4
 
-# include/lesion/lmnet_lesion.h: the components of a predicted and a target volume and the join between them (lm_net_amd.metrics.
-# LesionMeter).  A list of its own for the same reason, and no struct; tests/test_lesion_cpu.py checks it against the header and ties
-# lmn_lesion_match to tests/test_guard_lesion_gpu.py.
+# include/lesion/lmnet_lesion.h: the components of two volumes and the join between them (lm_net_amd.metrics.LesionMeter)
 SYMBOLS_LESION = ["lmn_lesion_workspace", "lmn_lesion_match"]
 LESION_MAX_SIDE = 1024       # LMN_LESION_* of the header
 LESION_MIN_SLOTS = 64
 LESION_MAX_SLOTS = 1 << 22
 LESION_NCTRL = 4
 
-# include/distmap/lmnet_distmap.h: dense signed squared distance maps of label masks and the boundary / Hausdorff losses on them
-# (lm_net_amd.loss.distance_maps, BoundaryLoss, HausdorffDTLoss).  A list of its own for the same reason, and no struct;
-# tests/test_distmap_cpu.py checks it against the header and ties the three device entries to tests/test_guard_distmap_gpu.py.
+# include/distmap/lmnet_distmap.h: signed squared distance maps and the losses on them (lm_net_amd.loss.BoundaryLoss, HausdorffDTLoss)
 SYMBOLS_DISTMAP = ["lmn_dist_workspace", "lmn_dist_map", "lmn_dist_loss_fwd", "lmn_dist_loss_bwd"]
 DISTMAP_MAX_SIDE = 1024      # LMN_DISTMAP_* of the header
 DISTMAP_LABELS_U8 = 0
@@ -342,9 +319,7 @@ DISTMAP_BOUNDARY = 0
 DISTMAP_HAUSDORFF = 1
 DISTMAP_SUMS_WORDS = 4
 
-# include/lovasz/lmnet_lovasz.h: the Lovasz-Softmax loss and the Lovasz hinge on a stable segmented device sort (lm_net_amd.loss.
-# LovaszLoss, lovasz_ranks).  A list of its own for the same reason, and no struct; tests/test_lovasz_cpu.py checks it against the
-# header and ties the three device entries to tests/test_guard_lovasz_gpu.py.
+# include/lovasz/lmnet_lovasz.h: Lovasz-Softmax and the Lovasz hinge on a segmented device sort (lm_net_amd.loss.LovaszLoss)
 SYMBOLS_LOVASZ = ["lmn_lovasz_workspace", "lmn_lovasz_order", "lmn_lovasz_fwd", "lmn_lovasz_bwd"]
 LOVASZ_TILE = 2048           # LMN_LOVASZ_* of the header
 LOVASZ_SCAN_THREADS = 64
@@ -355,9 +330,7 @@ LOVASZ_SOFTMAX = 0
 LOVASZ_SIGMOID = 1
 LOVASZ_SUMS_WORDS = 4
 
-# include/region/lmnet_region.h: the region-overlap losses -- Dice, Jaccard, Tversky and generalized Dice, per batch or per image
-# (lm_net_amd.loss.RegionLoss, region_sums).  A list of its own for the same reason, and no struct; tests/test_region_cpu.py checks
-# it against the header and ties the two device entries to tests/test_guard_region_gpu.py.
+# include/region/lmnet_region.h: Dice, Jaccard, Tversky and generalized Dice, per batch or per image (lm_net_amd.loss.RegionLoss)
 SYMBOLS_REGION = ["lmn_region_workspace", "lmn_region_fwd", "lmn_region_bwd"]
 REGION_DICE = 0              # LMN_REGION_* of the header
 REGION_JACCARD = 1
@@ -371,9 +344,7 @@ REGION_LABELS_U8 = 0
 REGION_LABELS_I64 = 1
 REGION_MAX_BATCH = 65535
 
-# include/slices/lmnet_slices.h: the statistics of an int16 / uint8 volume and the gather into fp32 2.5D batches (lm_net_amd.data.
-# VolumeSlicer).  A list of its own for the same reason, and no struct; tests/test_slices_cpu.py checks it against the header and ties
-# the two device entries to tests/test_guard_slices_gpu.py.
+# include/slices/lmnet_slices.h: volume statistics and the gather into fp32 2.5D batches (lm_net_amd.data.VolumeSlicer)
 SYMBOLS_SLICES = ["lmn_slices_workspace", "lmn_slices_stats", "lmn_slices_gather"]
 SLICES_I16 = 0               # LMN_SLICES_* of the header
 SLICES_U8 = 1
@@ -396,10 +367,7 @@ SLICES_MAX_BATCH = 65535
 SLICES_NSTAT = 8
 SLICES_NO_FOREGROUND = -32769
 
-# include/soft/lmnet_soft.h: the soft-target criteria -- cross entropy + Dice against probabilities or a Mixup pair, distillation against
-# a teacher's logits -- and the Mixup / CutMix batch mixer (lm_net_amd.loss.SoftSegLoss, DistillLoss, lm_net_amd.data.DeviceMix).  A
-# list of its own for the same reason, and no struct; tests/test_soft_cpu.py checks it against the header and ties the three device
-# entries to tests/test_guard_soft_gpu.py.
+# include/soft/lmnet_soft.h: soft-target criteria and the Mixup / CutMix mixer (lm_net_amd.loss.SoftSegLoss, DistillLoss, lm_net_amd.data.DeviceMix)
 SYMBOLS_SOFT = ["lmn_soft_workspace", "lmn_soft_fwd", "lmn_soft_bwd", "lmn_mix_batch"]
 SOFT_PROBS = 0               # LMN_SOFT_* of the header
 SOFT_PAIR = 1
@@ -415,9 +383,7 @@ MIX_MIXUP = 1
 MIX_CUTMIX = 2
 MIX_ROW_WORDS = 8
 
-# include/hard/lmnet_hard.h: the hard-pixel criterion -- top-k and OHEM cross entropy on an exact device radix select
-# (lm_net_amd.loss.HardPixelLoss, hard_pixel_values).  A list of its own for the same reason, and no struct; tests/test_hard_cpu.py
-# checks it against the header and ties the two device entries to tests/test_guard_hard_gpu.py.
+# include/hard/lmnet_hard.h: top-k and OHEM cross entropy on a device radix select (lm_net_amd.loss.HardPixelLoss)
 SYMBOLS_HARD = ["lmn_hard_workspace", "lmn_hard_fwd", "lmn_hard_bwd"]
 HARD_SOFTMAX = 0             # LMN_HARD_* of the header
 HARD_SIGMOID = 1
@@ -428,6 +394,27 @@ HARD_MAX_GROUPS = 1024
 HARD_RECORD_WORDS = 5
 HARD_BINS_HIGH = 2048
 HARD_BINS_LOW = 1024
+
+HEADERS = {"lmnet_hip.h": SYMBOLS, "lmnet_oneof.h": SYMBOLS_ONEOF, "lmnet_loss.h": SYMBOLS_LOSS, "lmnet_sigmoid.h": SYMBOLS_SIGMOID,
+           "optim/lmnet_optim.h": SYMBOLS_OPTIM, "tiles/lmnet_tiles.h": SYMBOLS_TILES, "curves/lmnet_curves.h": SYMBOLS_CURVES,
+           "volume/lmnet_volume.h": SYMBOLS_VOLUME, "volpost/lmnet_volpost.h": SYMBOLS_VOLPOST, "lesion/lmnet_lesion.h": SYMBOLS_LESION,
+           "distmap/lmnet_distmap.h": SYMBOLS_DISTMAP, "lovasz/lmnet_lovasz.h": SYMBOLS_LOVASZ, "region/lmnet_region.h": SYMBOLS_REGION,
+           "slices/lmnet_slices.h": SYMBOLS_SLICES, "soft/lmnet_soft.h": SYMBOLS_SOFT, "hard/lmnet_hard.h": SYMBOLS_HARD}     # path under include/
+EXPORTS = [name for names in HEADERS.values() for name in names]
+
+# every struct mirror whose size the library reports, with the export that reports it.  (DwPre, SeFuse, SeBwd and SeParamsT
+# have no lmn_sizeof_* export and stay unchecked.)
+STRUCTS = [(ConvArgs, "lmn_sizeof_conv_args"), (SrcT, "lmn_sizeof_src"), (WgradArgs, "lmn_sizeof_wgrad_args"),
+           (PackJob, "lmn_sizeof_pack_job"), (ReduceJob, "lmn_sizeof_reduce_job"), (AugParam, "lmn_sizeof_aug_param"),
+           (PostParam, "lmn_sizeof_post_param"), (OneOfParam, "lmn_sizeof_oneof_param"), (LossParam, "lmn_sizeof_loss_param"),
+           (SigParam, "lmn_sizeof_sig_param"), (OptimParam, "lmn_sizeof_optim_param"), (TileParam, "lmn_sizeof_tile_param")]
+
+# the entries that do not return int: ctypes cuts a 64-bit result to 32 bits unless told (tests/test_host_cpu.py: the headers' prototypes)
+RETURNS_INT64 = ["lmn_conv_pack_size", "lmn_conv_wgrad_workspace", "lmn_surface_workspace", "lmn_post_workspace", "lmn_plan_record_end",
+                 "lmn_plan_size", "lmn_plan_host_profile", "lmn_prof_end", "lmn_oneof_workspace", "lmn_optim_workspace", "lmn_curve_workspace",
+                 "lmn_volume_workspace", "lmn_volpost_workspace", "lmn_lesion_workspace", "lmn_dist_workspace", "lmn_lovasz_workspace",
+                 "lmn_region_workspace", "lmn_slices_workspace", "lmn_soft_workspace", "lmn_hard_workspace"]
+RETURNS_OTHER = {"lmn_last_error": C.c_char_p, "lmn_plan_create": C.c_void_p}
 
 _lib = None
 
@@ -442,26 +429,13 @@ def load():
             "lm_net_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C lm_net_amd/csrc`). The LM-Net hot path has no non-HIP fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS + SYMBOLS_OPTIM + SYMBOLS_TILES + SYMBOLS_CURVES + SYMBOLS_VOLUME + SYMBOLS_VOLPOST + SYMBOLS_LESION + SYMBOLS_DISTMAP + SYMBOLS_LOVASZ + SYMBOLS_REGION + SYMBOLS_SLICES + SYMBOLS_SOFT + SYMBOLS_HARD:
+    for name in EXPORTS:
         if not hasattr(lib, name):
             raise RuntimeError("lm_net_amd: %s does not export %s" % (LIB_PATH, name))
-    lib.lmn_last_error.restype = C.c_char_p
-    lib.lmn_conv_pack_size.restype = C.c_int64
-    lib.lmn_conv_wgrad_workspace.restype = C.c_int64
-    lib.lmn_surface_workspace.restype = C.c_int64
-    lib.lmn_post_workspace.restype = C.c_int64
-    lib.lmn_oneof_workspace.restype = C.c_int64
-    lib.lmn_optim_workspace.restype = C.c_int64
-    lib.lmn_curve_workspace.restype = C.c_int64
-    lib.lmn_volume_workspace.restype = C.c_int64
-    lib.lmn_volpost_workspace.restype = C.c_int64
-    lib.lmn_lesion_workspace.restype = C.c_int64
-    lib.lmn_dist_workspace.restype = C.c_int64
-    lib.lmn_lovasz_workspace.restype = C.c_int64
-    lib.lmn_region_workspace.restype = C.c_int64
-    lib.lmn_slices_workspace.restype = C.c_int64
-    lib.lmn_soft_workspace.restype = C.c_int64
-    lib.lmn_hard_workspace.restype = C.c_int64
+    for name in RETURNS_INT64:
+        getattr(lib, name).restype = C.c_int64
+    for name, restype in RETURNS_OTHER.items():
+        getattr(lib, name).restype = restype
     # (the only entries with a 64-bit integer or a float ahead of the pointer block: declared, so that a Python int cannot be cut)
     vp, ci, cf = C.c_void_p, C.c_int, C.c_float
     lib.lmn_hard_workspace.argtypes = [ci] * 6
@@ -469,13 +443,9 @@ def load():
     lib.lmn_hard_fwd.argtypes = [vp, vp, ci, ci, ci, cf, C.c_int64, cf, cf, ci, ci, ci, ci, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
     lib.lmn_hard_bwd.restype = ci
     lib.lmn_hard_bwd.argtypes = [vp, vp, ci, ci, ci, cf, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
-    lib.lmn_plan_create.restype = C.c_void_p
-    lib.lmn_plan_record_end.restype = C.c_int64
-    lib.lmn_plan_size.restype = C.c_int64
-    lib.lmn_prof_end.restype = C.c_int64
     if lib.lmn_abi_version() != ABI_VERSION:
         raise RuntimeError("lm_net_amd: ABI version mismatch")
-    for struct, sizeof in STRUCTS + [(OptimParam, "lmn_sizeof_optim_param"), (TileParam, "lmn_sizeof_tile_param")]:
+    for struct, sizeof in STRUCTS:
         n = getattr(lib, sizeof)()
         if n != C.sizeof(struct):
             raise RuntimeError("lm_net_amd: layout of %s differs between hip.py (%d bytes) and the library (%s() = %d)"
@@ -2432,7 +2402,6 @@ class Plan:
     def host_profile(self):
         """Runs the plan once; -> {entry point: (ops, host microseconds)}"""
         lib = load()
-        lib.lmn_plan_host_profile.restype = C.c_int64
         buf = C.create_string_buffer(1 << 16)
         n = int(lib.lmn_plan_host_profile(self.h, buf, _i64(1 << 16)))
         if n < 0:

@@ -154,6 +154,38 @@ class GuardPool(_Guarded):
         return sum((nb + guard + 2 * GRANULE) for nb in tensors_bytes) + guard + GRANULE
 
 
+JUNK = 0xA5
+
+
+def pools(inputs, outputs, device, fill):
+    """(plain tensors, GuardPool, guarded tensors) for one direct call of a C entry, run once on each side: `inputs` name -> tensor,
+    copied in; `outputs` name -> (shape, dtype).  The pool holds every tensor at its exact size.  fill="junk": every output byte on
+    both sides is JUNK (an entry that writes all of its outputs: whatever it leaves shows).  fill="poison": the plain uint8 outputs
+    hold POISON as the pool's bodies do, the other plain outputs are uninitialised (an entry that writes part of a uint8 case buffer:
+    the test compares the untouched part)."""
+    if fill not in ("junk", "poison"):
+        raise ValueError("pools: fill is 'junk' or 'poison', got %r" % (fill,))
+    plain = {k: v.to(device) for k, v in inputs.items()}
+    plain.update({k: torch.empty(s, dtype=dt, device=device) for k, (s, dt) in outputs.items()})
+    pool = GuardPool(device, GuardPool.size_for([v.numel() * v.element_size() for v in plain.values()]))
+    guarded = {k: pool.take(k, None, None, init=v.to(device)) for k, v in inputs.items()}
+    guarded.update({k: pool.take(k, s, dt) for k, (s, dt) in outputs.items()})
+    for d in (plain, guarded):
+        for k, (_, dt) in outputs.items():
+            if fill == "junk":
+                d[k].view(torch.uint8).fill_(JUNK)
+            elif dt == torch.uint8:
+                d[k].fill_(POISON)
+    return plain, pool, guarded
+
+
+def sizes(pool, plain):
+    """name -> bytes of every tensor of the pool, asserted equal to the plain tensors' sizes: nothing is rounded up."""
+    got = {e[0]: e[2] for e in pool.entries}
+    assert got == {k: v.numel() * v.element_size() for k, v in plain.items()}
+    return got
+
+
 def junk_pattern(device):
     """128 fp32 values (two granules) that are finite, non-zero and of the order 1e3 both as fp32 and as either bf16 half; the fp32
     signs alternate, the bf16 signs go + + - -.  1024 + 8 k is exact in bf16."""
@@ -296,6 +328,8 @@ KERN = "tests/test_guard_kernels_gpu.py"
 ONEOF = "tests/test_guard_oneof_gpu.py"
 LOSS = "tests/test_guard_loss_gpu.py"
 SIGMOID = "tests/test_guard_sigmoid_gpu.py"
+OPTIM, TILES, CURVES, VOLUME, VOLPOST, LESION, DISTMAP, LOVASZ, REGION, SLICES, SOFT, HARD = (
+    "tests/test_guard_%s_gpu.py" % x for x in ("optim", "tiles", "curves", "volume", "volpost", "lesion", "distmap", "lovasz", "region", "slices", "soft", "hard"))
 
 
 def _fam(*wrappers):
@@ -306,6 +340,7 @@ def _fam(*wrappers):
 # C entry -> (test file, test function, `hip.` wrapper through which that test issues the entry).  tests/test_guard_cpu.py checks that
 # this and EXEMPT partition hip.EXPORTS (every header's list) and that the named test's file calls `hip.<wrapper>` -- or, where the
 # test reaches the entry through a class of the package, asserts the wrapper's name in its launch log: a new export needs a guard test.
+# A new header joins here: its device entries in COVERED with a guard test of their own, the rest in EXEMPT with the reason.
 # (The engine-allocated side of the same entries -- every intermediate of the model's own pass -- is tests/test_guard_model_gpu.py.)
 COVERED = dict(_fam(
     "conv_fwd", "conv_wgrad", "reparam_fold", "reparam_wfin", "affine2", "bnact_fwd_fin", "bnact_bwd_fin",
@@ -343,7 +378,39 @@ COVERED.update({
     "lmn_sigloss_fwd": (SIGMOID, "test_loss_and_stats_entries", "sigloss_fwd"),
     "lmn_sigloss_bwd": (SIGMOID, "test_loss_and_stats_entries", "sigloss_bwd"),
     "lmn_sigmoid_stats": (SIGMOID, "test_loss_and_stats_entries", "sigmoid_stats"),
+    "lmn_optim_prepare": (OPTIM, "test_prepare_and_step_entries", "optim_prepare"),
+    "lmn_adamw_step_ex": (OPTIM, "test_prepare_and_step_entries", "adamw_step_ex"),
+    "lmn_tile_gather": (TILES, "test_gather_and_blend_entries", "tile_gather"),
+    "lmn_tile_blend": (TILES, "test_gather_and_blend_entries", "tile_blend"),
+    "lmn_curve_hist": (CURVES, "test_curve_hist_entry", "curve_hist"),
+    "lmn_volume_labels": (VOLUME, "test_volume_labels_entry", "volume_labels"),
+    "lmn_volume_dist": (VOLUME, "test_volume_dist_entry", "volume_dist"),
+    "lmn_cc3d_label": (VOLPOST, "test_cc3d_label_entry", "cc3d_label"),
+    "lmn_volpost_clean": (VOLPOST, "test_volpost_clean_entry", "volpost_clean"),
+    "lmn_lesion_match": (LESION, "test_lesion_match_entry", "lesion_match"),
+    "lmn_dist_map": (DISTMAP, "test_dist_map_entry", "dist_map"),
+    "lmn_dist_loss_fwd": (DISTMAP, "test_dist_loss_entries", "dist_loss_fwd"),
+    "lmn_dist_loss_bwd": (DISTMAP, "test_dist_loss_entries", "dist_loss_bwd"),
+    "lmn_lovasz_order": (LOVASZ, "test_lovasz_order_entry", "lovasz_order"),
+    "lmn_lovasz_fwd": (LOVASZ, "test_lovasz_loss_entries", "lovasz_fwd"),
+    "lmn_lovasz_bwd": (LOVASZ, "test_lovasz_loss_entries", "lovasz_bwd"),
+    "lmn_region_fwd": (REGION, "test_region_loss_entries", "region_fwd"),
+    "lmn_region_bwd": (REGION, "test_region_loss_entries", "region_bwd"),
+    "lmn_slices_stats": (SLICES, "test_slices_entries", "slices_stats"),
+    "lmn_slices_gather": (SLICES, "test_slices_entries", "slices_gather"),
+    "lmn_soft_fwd": (SOFT, "test_soft_loss_entries", "soft_fwd"),
+    "lmn_soft_bwd": (SOFT, "test_soft_loss_entries", "soft_bwd"),
+    "lmn_mix_batch": (SOFT, "test_mix_batch_entry", "mix_batch"),
+    "lmn_hard_fwd": (HARD, "test_hard_entries", "hard_fwd"),
+    "lmn_hard_bwd": (HARD, "test_hard_entries", "hard_bwd"),
 })
+
+# The files under the strict rule -> what the named test function must hold besides: it CALLS `hip.<wrapper>(` AND compares a
+# LaunchLog's `names` with a list that holds the wrapper (the general rule accepts either), and it runs the entry on a guard pool --
+# these words.  (The AdamW step updates its inputs in place: its test carves the workspace at exactly hip.optim_workspace(n) instead.)
+_POOL, _POOLS = ("GuardPool", "assert_clean", "assert_inputs_unchanged"), ("pools(", "assert_clean", "assert_inputs_unchanged")
+STRICT = {LOSS: _POOL, SIGMOID: _POOL, OPTIM: ("GuardPool", "assert_clean", "hip.optim_workspace(n)"), TILES: _POOL, CURVES: _POOL, VOLUME: _POOLS, VOLPOST: _POOLS,
+          LESION: _POOLS, DISTMAP: _POOLS, LOVASZ: _POOLS, REGION: _POOLS, SLICES: _POOLS, SOFT: _POOLS, HARD: _POOLS}
 
 # entries that take no device output pointer -> why no guard test applies
 _HOST = "host arithmetic only: returns a number, touches no device memory"
@@ -357,6 +424,12 @@ EXEMPT = {
     "lmn_surface_workspace": _HOST + " (tested as a bound by test_surface_dist)",
     "lmn_post_workspace": _HOST + " (tested as a bound by test_post_clean_render_and_cc_label)",
     "lmn_oneof_workspace": _HOST + " (tested as a bound by test_augment_oneof_u8_every_member: the workspace is carved at exactly this)",
+    "lmn_sizeof_optim_param": _HOST, "lmn_sizeof_tile_param": _HOST,
+    **{"lmn_%s_workspace" % x: _HOST + " (tested as a bound by %s: the workspace is carved at exactly this)" % test for x, test in (
+        ("optim", "test_prepare_and_step_entries"), ("curve", "test_curve_hist_entry"), ("volume", "test_volume_dist_entry"),
+        ("volpost", "test_volpost_clean_entry"), ("lesion", "test_lesion_match_entry"), ("dist", "test_dist_map_entry"),
+        ("lovasz", "test_lovasz_order_entry"), ("region", "test_region_loss_entries"), ("slices", "test_slices_entries"),
+        ("soft", "test_soft_loss_entries"), ("hard", "test_hard_entries"))},
     "lmn_conv_chain_ok": "launch predicate, " + _HOST, "lmn_conv_wgrad_up2_ok": "launch predicate, " + _HOST,
     "lmn_conv_wgrad_job": "geometry query into a host struct, " + _HOST,
     "lmn_conv_dma_config": "process-wide dispatch switch, host state only",

@@ -1,5 +1,5 @@
 """CPU: the host side of the distance maps and their losses (include/distmap/lmnet_distmap.h; lm_net_amd.loss.distance_maps,
-BoundaryLoss, HausdorffDTLoss): registry and header agree, the guard rule for the three device entries, the argument checks of the C
+BoundaryLoss, HausdorffDTLoss): registry and header agree, the argument checks of the C
 entries (rejected before any HIP call, with fake device pointers), the workspace formula, the classes' ValueErrors, the restatement
 tests/distmap_ref.py against scipy.ndimage.distance_transform_edt, brute force and hand-computed planes, its gradients against
 finite differences, and the conditions the GPU tests rest on.  No GPU needed."""
@@ -19,57 +19,23 @@ DEVICE_ENTRIES = ["lmn_dist_map", "lmn_dist_loss_fwd", "lmn_dist_loss_bwd"]
 
 # ---------------------------------------------------------------- ABI
 def test_registry_and_header_agree():
-    """hip.SYMBOLS_DISTMAP against include/distmap/lmnet_distmap.h: the header declares exactly the list and no struct, the library
-    exports the names, no name belongs to another list, and the #defines equal the hip.DISTMAP_* constants."""
+    """The feature's own part of the registry: the literal list, its place in hip.HEADERS, the number of #defines, the header's
+    citations and the package's exports.  (Header / export / layout / return-type / constants checks: tests/test_host_cpu.py.)"""
     from lm_net_amd import hip
-    lib = hip.load()
     assert hip.SYMBOLS_DISTMAP == ["lmn_dist_workspace"] + DEVICE_ENTRIES
+    assert hip.HEADERS["distmap/lmnet_distmap.h"] is hip.SYMBOLS_DISTMAP
     header = open(os.path.join(ROOT, "include", "distmap", "lmnet_distmap.h")).read()
-    declared = set(re.findall(r"^(?:int|int64_t) (lmn_[a-z0-9_]+)\s*\(", header, re.M))
-    assert declared == set(hip.SYMBOLS_DISTMAP) and all(hasattr(lib, name) for name in hip.SYMBOLS_DISTMAP), declared ^ set(hip.SYMBOLS_DISTMAP)
-    for other in (hip.EXPORTS, hip.SYMBOLS_OPTIM, hip.SYMBOLS_TILES, hip.SYMBOLS_CURVES, hip.SYMBOLS_VOLUME, hip.SYMBOLS_VOLPOST,
-                  hip.SYMBOLS_LESION):
-        assert not set(hip.SYMBOLS_DISTMAP) & set(other)
-    assert not any(name.startswith("lmn_sizeof_") for name in hip.SYMBOLS_DISTMAP)
-    assert re.findall(r"^\}\s*(lmn_\w+_t)\s*;", header, re.M) == []
-    defs = {k: int(v) for k, v in re.findall(r"^#define (LMN_DISTMAP_\w+) (\d+)\b", header, re.M)}
-    mine = {"LMN_" + k: v for k, v in vars(hip).items() if k.startswith("DISTMAP_")}
-    assert defs == mine and len(defs) == 10, (defs, mine)
+    assert len(re.findall(r"^#define LMN_DISTMAP_\w+ \d+\b", header, re.M)) == 10
     assert (hip.DISTMAP_MAX_SIDE, hip.DISTMAP_FLAG_EMPTY, hip.DISTMAP_FLAG_FULL, hip.DISTMAP_SUMS_WORDS) == (1024, 1, 2, 4)
     for cite in ("SIGNED SQUARED", "THE PLANE IS ALL 0", "posmask.any()", "one_hot2dist", "rint((edt(M) + edt(~M))^2) == |sd2|",
                  "never NaN", "is not pinned", "dist_map: ", "dist_loss_fwd: ", "dist_loss_bwd: ", "at most W - 1 steps"):
         assert cite in header, cite
-    # the header sits in a subdirectory: the top-level headers are still exactly hip.HEADERS
-    assert sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")) == sorted(hip.HEADERS)
     import lm_net_amd
     from lm_net_amd import loss
     for name in ("BoundaryLoss", "HausdorffDTLoss", "distance_maps"):
         assert getattr(lm_net_amd, name) is getattr(loss, name) and name in lm_net_amd.__all__
     for doc in (loss.BoundaryLoss.__doc__, loss.distance_maps.__doc__):
         assert "Deliberate difference" in doc
-
-
-def test_every_entry_that_writes_device_memory_has_its_guard_test():
-    """The rule of the guard manifest (tests/guard.py, tests/test_guard_cpu.py) for hip.SYMBOLS_DISTMAP: lmn_dist_workspace is host
-    arithmetic (the exemption pattern of test_guard_cpu.py); the three device entries are issued, through their hip. wrappers, inside
-    the named tests of tests/test_guard_distmap_gpu.py, which assert the launch log; each wrapper's source issues its C entry."""
-    from lm_net_amd import hip
-    from test_guard_cpu import EXEMPT_OK, _code
-    covered = {"lmn_dist_map": ("test_dist_map_entry", "dist_map"), "lmn_dist_loss_fwd": ("test_dist_loss_entries", "dist_loss_fwd"),
-               "lmn_dist_loss_bwd": ("test_dist_loss_entries", "dist_loss_bwd")}
-    exempt = {"lmn_dist_workspace"}
-    assert set(covered) | exempt == set(hip.SYMBOLS_DISTMAP) and not set(covered) & exempt
-    assert all(EXEMPT_OK.match(k) for k in exempt) and not any(EXEMPT_OK.match(k) for k in covered)
-    src = _code(open(os.path.join(ROOT, "tests", "test_guard_distmap_gpu.py")).read())
-    hip_src = open(os.path.join(ROOT, "lm_net_amd", "hip.py")).read()
-    for entry, (test, wrapper) in covered.items():
-        fn = re.search(r"^def %s\(.*?(?=^def |^class |^@|\Z)" % test, src, re.M | re.S).group(0)
-        assert re.search(r"\bhip\.%s\(" % wrapper, fn), wrapper
-        assert any('"%s"' % wrapper in m for m in re.findall(r"\.names == \[([^\]]*)\]", fn)), wrapper
-        body = re.search(r"^def %s\(.*?(?=^def |^class |\Z)" % wrapper, hip_src, re.M | re.S).group(0)
-        assert re.search(r"\b%s\b" % entry, body), (entry, wrapper)
-        assert "_pools(" in fn and "assert_clean" in fn and "assert_inputs_unchanged" in fn, test
-    assert "GuardPool(DEV, GuardPool.size_for(" in re.search(r"^def _pools\(.*?(?=^def |^class |^@|\Z)", src, re.M | re.S).group(0)
 
 
 # ---------------------------------------------------------------- argument checks

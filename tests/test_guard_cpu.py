@@ -107,6 +107,33 @@ def test_arena_exhaustion():
         g.alloc((65,))
 
 
+@pytest.mark.parametrize("fill", ["junk", "poison"])
+def test_pools_carve_every_tensor_at_its_exact_size(fill):
+    """guard.pools / guard.sizes, which the guard tests of the feature headers share: a pool of size_for the tensors, inputs copied in
+    and registered, outputs at their exact sizes, and the fill each file names."""
+    inputs = dict(x=torch.arange(7, dtype=torch.float32), y=torch.arange(5, dtype=torch.int64))
+    outputs = dict(u=((3, 5), torch.uint8), f=((9,), torch.float32), e=((0,), torch.uint8))
+    plain, pool, guarded = guard.pools(inputs, outputs, CPU, fill=fill)
+    assert isinstance(pool, GuardPool) and pool.nbytes == -(-GuardPool.size_for([28, 40, 15, 36, 0]) // 256) * 256
+    assert list(plain) == list(guarded) == ["x", "y", "u", "f", "e"] and all(guarded[k] is pool.t[k] for k in guarded)
+    assert guard.sizes(pool, plain) == dict(x=28, y=40, u=15, f=36, e=0)
+    assert set(pool.inputs) == {"x", "y"} and all(torch.equal(plain[k], inputs[k]) and torch.equal(guarded[k], inputs[k]) for k in inputs)
+    pool.assert_clean()
+    pool.assert_inputs_unchanged()
+    for d in (plain, guarded):
+        assert bool((d["u"] == (guard.JUNK if fill == "junk" else guard.POISON)).all())
+    if fill == "junk":
+        assert all(bool((d["f"].view(torch.uint8) == guard.JUNK).all()) for d in (plain, guarded))
+    else:
+        assert bool((guarded["f"].view(torch.uint8) == guard.POISON).all())      # untouched: the pool's own poison
+    with pytest.raises(AssertionError):
+        guard.sizes(pool, dict(plain, f=plain["f"][:8]))
+    with pytest.raises(ValueError, match="fill"):
+        guard.pools(inputs, outputs, CPU, fill=0xA5)
+    with pytest.raises(TypeError):
+        guard.pools(inputs, outputs, CPU)                                         # no default: a file names its fill
+
+
 # ------------------------------------------------------------------------------------------------------------------ sensitivity
 def test_pool_detector_names_tensor_side_and_offset():
     p = GuardPool(CPU, 1 << 16)
@@ -188,7 +215,7 @@ def test_manifest_partitions_the_c_abi():
     from lm_net_amd import hip
     cov, ex = set(guard.COVERED), set(guard.EXEMPT)
     assert not (cov & ex), sorted(cov & ex)
-    assert len(set(hip.EXPORTS)) == len(hip.EXPORTS) == sum(len(v) for v in hip.HEADERS.values())
+    assert len(set(hip.EXPORTS)) == len(hip.EXPORTS) == sum(len(v) for v in hip.HEADERS.values()) == 139
     assert cov | ex == set(hip.EXPORTS), (sorted(set(hip.EXPORTS) - cov - ex), sorted((cov | ex) - set(hip.EXPORTS)))
     bad = sorted(k for k in ex if not EXEMPT_OK.match(k))
     assert not bad, "entries with a device output pointer need a guard test: %s" % bad
@@ -196,7 +223,11 @@ def test_manifest_partitions_the_c_abi():
     # the pattern must not swallow an entry that writes device memory
     for k in ("lmn_conv_fwd", "lmn_conv_pack", "lmn_conv_pack_batch", "lmn_conv_wgrad", "lmn_wgrad_reduce_batch", "lmn_fill", "lmn_surface_dist",
               "lmn_post_clean", "lmn_cc_label", "lmn_adamw_step", "lmn_dw_fwd_bn", "lmn_reparam_fold", "lmn_augment_oneof_u8",
-              "lmn_segloss_ex_fwd", "lmn_segloss_ex_bwd", "lmn_image_stats", "lmn_sigloss_fwd", "lmn_sigloss_bwd", "lmn_sigmoid_stats"):
+              "lmn_segloss_ex_fwd", "lmn_segloss_ex_bwd", "lmn_image_stats", "lmn_sigloss_fwd", "lmn_sigloss_bwd", "lmn_sigmoid_stats",
+              "lmn_optim_prepare", "lmn_adamw_step_ex", "lmn_tile_gather", "lmn_tile_blend", "lmn_curve_hist", "lmn_volume_labels", "lmn_volume_dist",
+              "lmn_cc3d_label", "lmn_volpost_clean", "lmn_lesion_match", "lmn_dist_map", "lmn_dist_loss_fwd", "lmn_dist_loss_bwd", "lmn_lovasz_order",
+              "lmn_lovasz_fwd", "lmn_lovasz_bwd", "lmn_region_fwd", "lmn_region_bwd", "lmn_slices_stats", "lmn_slices_gather", "lmn_soft_fwd",
+              "lmn_soft_bwd", "lmn_mix_batch", "lmn_hard_fwd", "lmn_hard_bwd"):
         assert not EXEMPT_OK.match(k) and k in cov, k
 
 
@@ -210,6 +241,7 @@ def test_manifest_matches_the_gpu_test_sources():
     """Every COVERED entry names a test function that exists in its file and whose body calls (or, for the model file, lists as
     reached and asserts at run time) the entry's `hip.` wrapper -- or, where it reaches the entry through a class of the package,
     compares a LaunchLog's `names` with a list that holds the wrapper's name; the wrapper's source really issues that C entry.
+    In a file of guard.STRICT the function must do both, and hold the file's words: it runs the entry on a guard pool and checks it.
     A docstring counts for nothing."""
     from lm_net_amd import hip
     src = {f: _code(open(os.path.join(ROOT, f)).read()) for f in sorted({v[0] for v in guard.COVERED.values()} | {guard.MODEL})}
@@ -226,11 +258,16 @@ def test_manifest_matches_the_gpu_test_sources():
             called = re.search(r"\bhip\.%s\b" % re.escape(wrapper), fn.group(0))       # (inside the named test function)
             logged = any('"%s"' % wrapper in m for m in re.findall(r"\.names == \[([^\]]*)\]", fn.group(0)))
             assert called or logged, (entry, wrapper)
+            if f in guard.STRICT:
+                assert re.search(r"\bhip\.%s\(" % re.escape(wrapper), fn.group(0)) and logged, (entry, wrapper, bool(called), logged)
+                missing = [w for w in guard.STRICT[f] if w not in fn.group(0)]
+                assert not missing, (entry, test, missing)
         assert callable(getattr(hip, wrapper)), (entry, wrapper)
         body = re.search(r"^def %s\(.*?(?=^def |^class |\Z)" % re.escape(wrapper), hip_src, re.M | re.S)
         if body is None:                                             # a class (PackPlan.refresh issues lmn_conv_pack_batch)
             body = re.search(r"^class %s\b.*?(?=^class |^def |\Z)" % re.escape(wrapper), hip_src, re.M | re.S)
         assert body is not None and re.search(r"\b%s\b" % entry, body.group(0)), (entry, wrapper)
+    assert set(guard.STRICT) <= set(src) and all("assert_clean" in words for words in guard.STRICT.values())
     # the stripping itself: a docstring that names a wrapper satisfies neither rule
     fake = _code('"""calls hip.fake_wrapper( and asserts log.names == ["fake_wrapper"]"""\nx = 1\n' + "'''hip.fake_wrapper('''\n")
     assert "fake_wrapper" not in fake and "x = 1" in fake

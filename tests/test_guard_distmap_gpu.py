@@ -9,31 +9,11 @@ import pytest
 import torch
 
 import distmap_ref as R
-from guard import GuardPool, LaunchLog
+from guard import LaunchLog, pools, sizes
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 SHAPES = [(37, 45), (130, 67)]
-JUNK = 0xA5
-
-
-def _pools(inputs, outputs):
-    """(plain tensors, GuardPool, guarded tensors) of the same inputs and output shapes; the output bodies hold junk."""
-    plain = {k: v.to(DEV) for k, v in inputs.items()}
-    plain.update({k: torch.empty(s, dtype=dt, device=DEV) for k, (s, dt) in outputs.items()})
-    pool = GuardPool(DEV, GuardPool.size_for([v.numel() * v.element_size() for v in plain.values()]))
-    guarded = {k: pool.take(k, None, None, init=v.to(DEV)) for k, v in inputs.items()}
-    guarded.update({k: pool.take(k, s, dt) for k, (s, dt) in outputs.items()})
-    for d in (plain, guarded):
-        for k in outputs:
-            d[k].view(torch.uint8).fill_(JUNK)
-    return plain, pool, guarded
-
-
-def _sizes(pool, plain):
-    got = {e[0]: e[2] for e in pool.entries}
-    assert got == {k: v.numel() * v.element_size() for k, v in plain.items()}     # exact sizes: nothing is rounded up
-    return got
 
 
 @pytest.mark.parametrize("source", ["labels", "softmax", "sigmoid"])
@@ -57,14 +37,14 @@ def test_dist_map_entry(shape, source):
         hip.dist_map(x["src"], C, mask, x["workspace"], x["sd2"], x["flags"], mode=mode, threshold=thr)
         torch.cuda.synchronize()
 
-    plain, pool, guarded = _pools(dict(src=src), outputs)
+    plain, pool, guarded = pools(dict(src=src), outputs, DEV, fill="junk")
     run(plain)
     with LaunchLog(pool) as log:
         run(guarded)
     pool.assert_clean("dist_map entry")
     pool.assert_inputs_unchanged()
     assert log.names == ["dist_map"]
-    got = _sizes(pool, plain)
+    got = sizes(pool, plain)
     up = lambda v: (v + 255) // 256 * 256
     assert got["workspace"] == ws_bytes == up(B * nk * H * W) + up(2 * B * nk * H * W) + up(4 * B * nk)
     assert got["sd2"] == 4 * B * nk * H * W and got["flags"] == 4 * B * nk
@@ -104,7 +84,7 @@ def test_dist_loss_entries(shape, head, term, C):
 
     hip.set_deterministic(True)
     try:
-        plain, pool, guarded = _pools(inputs, outputs)
+        plain, pool, guarded = pools(inputs, outputs, DEV, fill="junk")
         run(plain)
         with LaunchLog(pool) as log:
             run(guarded)
@@ -113,7 +93,7 @@ def test_dist_loss_entries(shape, head, term, C):
     pool.assert_clean("dist_loss entries")
     pool.assert_inputs_unchanged()
     assert log.names == ["dist_loss_fwd", "dist_loss_bwd"]
-    got = _sizes(pool, plain)
+    got = sizes(pool, plain)
     assert got["sums"] == 16 and got["loss"] == 4 and got["dlogits"] == 4 * lg.size
     for name in outputs:
         assert torch.equal(plain[name].view(torch.uint8), guarded[name].view(torch.uint8)), name

@@ -9,24 +9,10 @@ import pytest
 import torch
 
 import hard_ref as R
-from guard import GuardPool, LaunchLog
+from guard import LaunchLog, pools
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
-JUNK = 0xA5
-
-
-def _pools(inputs, outputs):
-    """(plain tensors, GuardPool, guarded tensors) of the same inputs and output shapes; the output bodies hold junk."""
-    plain = {k: v.to(DEV) for k, v in inputs.items()}
-    plain.update({k: torch.empty(s, dtype=dt, device=DEV) for k, (s, dt) in outputs.items()})
-    pool = GuardPool(DEV, GuardPool.size_for([v.numel() * v.element_size() for v in plain.values()]))
-    guarded = {k: pool.take(k, None, None, init=v.to(DEV)) for k, v in inputs.items()}
-    guarded.update({k: pool.take(k, s, dt) for k, (s, dt) in outputs.items()})
-    for d in (plain, guarded):
-        for k in outputs:
-            d[k].view(torch.uint8).fill_(JUNK)
-    return plain, pool, guarded
 
 
 INSTANCES = [("softmax", (1, 2, 1, 1), dict(keep=0.5)),                       # the smallest templated shape
@@ -65,7 +51,7 @@ def test_hard_entries(head, shape, kw, per_image):
         hip.hard_bwd(x["logits"], x["target"], hd, per_image, 0.7, x["weight"], x["values"], x["selection"], x["gscale"], x["dlogits"])
         torch.cuda.synchronize()
 
-    plain, pool, guarded = _pools(inputs, outputs)
+    plain, pool, guarded = pools(inputs, outputs, DEV, fill="junk")
     run(plain)
     with LaunchLog(pool) as log:
         run(guarded)

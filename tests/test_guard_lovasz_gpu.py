@@ -8,30 +8,10 @@ import pytest
 import torch
 
 import lovasz_ref as R
-from guard import GuardPool, LaunchLog
+from guard import LaunchLog, pools, sizes
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
-JUNK = 0xA5
-
-
-def _pools(inputs, outputs):
-    """(plain tensors, GuardPool, guarded tensors) of the same inputs and output shapes; the output bodies hold junk."""
-    plain = {k: v.to(DEV) for k, v in inputs.items()}
-    plain.update({k: torch.empty(s, dtype=dt, device=DEV) for k, (s, dt) in outputs.items()})
-    pool = GuardPool(DEV, GuardPool.size_for([v.numel() * v.element_size() for v in plain.values()]))
-    guarded = {k: pool.take(k, None, None, init=v.to(DEV)) for k, v in inputs.items()}
-    guarded.update({k: pool.take(k, s, dt) for k, (s, dt) in outputs.items()})
-    for d in (plain, guarded):
-        for k in outputs:
-            d[k].view(torch.uint8).fill_(JUNK)
-    return plain, pool, guarded
-
-
-def _sizes(pool, plain):
-    got = {e[0]: e[2] for e in pool.entries}
-    assert got == {k: v.numel() * v.element_size() for k, v in plain.items()}     # exact sizes: nothing is rounded up
-    return got
 
 
 @pytest.mark.parametrize("S,P", [(3, 257), (2, 3 * 2048 + 17)])
@@ -49,14 +29,14 @@ def test_lovasz_order_entry(S, P):
         hip.lovasz_order(x["keys"], x["workspace"], x["perm"])
         torch.cuda.synchronize()
 
-    plain, pool, guarded = _pools(dict(keys=torch.from_numpy(keys.view(np.int32))), outputs)
+    plain, pool, guarded = pools(dict(keys=torch.from_numpy(keys.view(np.int32))), outputs, DEV, fill="junk")
     run(plain)
     with LaunchLog(pool) as log:
         run(guarded)
     pool.assert_clean("lovasz_order entry")
     pool.assert_inputs_unchanged()
     assert log.names == ["lovasz_order"]
-    got = _sizes(pool, plain)
+    got = sizes(pool, plain)
     assert got["workspace"] == ws_bytes and got["perm"] == 4 * S * P
     assert torch.equal(plain["perm"], guarded["perm"])
     idx = np.arange(P)
@@ -88,14 +68,14 @@ def test_lovasz_loss_entries(shape, head, C, classes, per_image):
         hip.lovasz_bwd(x["logits"], x["target"], hd, mask, x["coef"], x["sums"], x["gscale"], x["dlogits"])
         torch.cuda.synchronize()
 
-    plain, pool, guarded = _pools(inputs, outputs)
+    plain, pool, guarded = pools(inputs, outputs, DEV, fill="junk")
     run(plain)
     with LaunchLog(pool) as log:
         run(guarded)
     pool.assert_clean("lovasz loss entries")
     pool.assert_inputs_unchanged()
     assert log.names == ["lovasz_fwd", "lovasz_bwd"]
-    got = _sizes(pool, plain)
+    got = sizes(pool, plain)
     assert got["sums"] == 16 and got["loss"] == 4 and got["dlogits"] == 4 * lg.size and got["counts"] == 8 * S
     for name in outputs:
         if name != "workspace":

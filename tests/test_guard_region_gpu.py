@@ -8,30 +8,10 @@ import pytest
 import torch
 
 import region_ref as R
-from guard import GuardPool, LaunchLog
+from guard import JUNK, LaunchLog, pools, sizes
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
-JUNK = 0xA5
-
-
-def _pools(inputs, outputs):
-    """(plain tensors, GuardPool, guarded tensors) of the same inputs and output shapes; the output bodies hold junk."""
-    plain = {k: v.to(DEV) for k, v in inputs.items()}
-    plain.update({k: torch.empty(s, dtype=dt, device=DEV) for k, (s, dt) in outputs.items()})
-    pool = GuardPool(DEV, GuardPool.size_for([v.numel() * v.element_size() for v in plain.values()]))
-    guarded = {k: pool.take(k, None, None, init=v.to(DEV)) for k, v in inputs.items()}
-    guarded.update({k: pool.take(k, s, dt) for k, (s, dt) in outputs.items()})
-    for d in (plain, guarded):
-        for k in outputs:
-            d[k].view(torch.uint8).fill_(JUNK)
-    return plain, pool, guarded
-
-
-def _sizes(pool, plain):
-    got = {e[0]: e[2] for e in pool.entries}
-    assert got == {k: v.numel() * v.element_size() for k, v in plain.items()}     # exact sizes: nothing is rounded up
-    return got
 
 
 @pytest.mark.parametrize("det", [False, True], ids=["atomic", "deterministic"])
@@ -66,7 +46,7 @@ def test_region_loss_entries(head, shape, kind, den, classes, per_image, det):
     was = hip.get_deterministic()
     hip.set_deterministic(det)
     try:
-        plain, pool, guarded = _pools(inputs, outputs)
+        plain, pool, guarded = pools(inputs, outputs, DEV, fill="junk")
         run(plain)
         with LaunchLog(pool) as log:
             run(guarded)
@@ -75,7 +55,7 @@ def test_region_loss_entries(head, shape, kind, den, classes, per_image, det):
     pool.assert_clean("region loss entries")
     pool.assert_inputs_unchanged()
     assert log.names == ["region_fwd", "region_bwd"]
-    got = _sizes(pool, plain)
+    got = sizes(pool, plain)
     assert got["workspace"] == ws_bytes and got["loss"] == 4 and got["dlogits"] == 4 * lg.size and got["counts"] == 8 * G * nk
     assert torch.equal(plain["counts"], guarded["counts"])
     if det:

@@ -9,22 +9,11 @@ import pytest
 import torch
 
 import volpost_ref as R
-from guard import GuardPool, LaunchLog
+from guard import LaunchLog, pools
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 SHAPES = [(3, 5, 70), (17, 66, 130)]
-
-
-def _pools(inputs, outputs):
-    """(plain tensors, GuardPool, guarded tensors) of the same inputs and output shapes."""
-    plain = {k: v.to(DEV) for k, v in inputs.items()}
-    plain.update({k: torch.full(s, 0xFF, dtype=dt, device=DEV) if dt == torch.uint8 else torch.empty(s, dtype=dt, device=DEV)
-                  for k, (s, dt) in outputs.items()})
-    pool = GuardPool(DEV, GuardPool.size_for([v.numel() * v.element_size() for v in plain.values()]))
-    guarded = {k: pool.take(k, None, None, init=v.to(DEV)) for k, v in inputs.items()}
-    guarded.update({k: pool.take(k, s, dt) for k, (s, dt) in outputs.items()})
-    return plain, pool, guarded
 
 
 @pytest.mark.parametrize("connectivity", [6, 18, 26])
@@ -39,7 +28,7 @@ def test_cc3d_label_entry(shape, connectivity):
         hip.cc3d_label(x["labels"], connectivity, x["roots"], x["sizes"])
         torch.cuda.synchronize()
 
-    plain, pool, guarded = _pools(inputs, outputs)
+    plain, pool, guarded = pools(inputs, outputs, DEV, fill="poison")
     run(plain)
     with LaunchLog(pool) as log:
         run(guarded)
@@ -71,7 +60,7 @@ def test_volpost_clean_entry(shape, connectivity):
         hip.volpost_clean(x["labels"], C, connectivity, mask, keep, minv, limit, x["workspace"], x["labels_out"], x["stats"])
         torch.cuda.synchronize()
 
-    plain, pool, guarded = _pools(inputs, outputs)
+    plain, pool, guarded = pools(inputs, outputs, DEV, fill="poison")
     run(plain)
     guarded["labels_out"].fill_(0xFF)
     with LaunchLog(pool) as log:

@@ -8,22 +8,11 @@ import pytest
 import torch
 
 import volume_ref as R
-from guard import GuardPool, LaunchLog
+from guard import LaunchLog, pools
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 SHAPES = [(3, 5, 70), (17, 66, 130)]
-
-
-def _pools(inputs, outputs):
-    """(plain tensors, GuardPool, guarded tensors) of the same inputs and output shapes."""
-    plain = {k: v.to(DEV) for k, v in inputs.items()}
-    plain.update({k: torch.full(s, 0xFF, dtype=dt, device=DEV) if dt == torch.uint8 else torch.empty(s, dtype=dt, device=DEV)
-                  for k, (s, dt) in outputs.items()})
-    pool = GuardPool(DEV, GuardPool.size_for([v.numel() * v.element_size() for v in plain.values()]))
-    guarded = {k: pool.take(k, None, None, init=v.to(DEV)) for k, v in inputs.items()}
-    guarded.update({k: pool.take(k, s, dt) for k, (s, dt) in outputs.items()})
-    return plain, pool, guarded
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
@@ -49,7 +38,7 @@ def test_volume_labels_entry(form, shape):
         hip.volume_labels(x["pred"], x["target"], C, x["lab_pred"], x["lab_target"], z0)
         torch.cuda.synchronize()
 
-    plain, pool, guarded = _pools(inputs, outputs)
+    plain, pool, guarded = pools(inputs, outputs, DEV, fill="poison")
     run(plain)
     guarded["lab_pred"].fill_(0xFF)
     guarded["lab_target"].fill_(0xFF)
@@ -81,7 +70,7 @@ def test_volume_dist_entry(shape):
         hip.volume_dist(x["lab_pred"], x["lab_target"], C, classes, spacing, x["workspace"], x["stats_i"], x["stats_f"])
         torch.cuda.synchronize()
 
-    plain, pool, guarded = _pools(inputs, outputs)
+    plain, pool, guarded = pools(inputs, outputs, DEV, fill="poison")
     run(plain)
     with LaunchLog(pool) as log:
         run(guarded)

@@ -12,28 +12,48 @@ import torch
 from helpers import GOLDEN, ROOT
 
 
+PROTOTYPE = re.compile(r"^(int|int64_t|const char\*|lmn_plan_t) (lmn_[a-z0-9_]+)\s*\(", re.M)
+
+
 def test_library_exports_every_declared_symbol():
     """hip.HEADERS against include/: every header is in the table and declares exactly its list, no name or struct typedef
-    belongs to two headers, the library exports every name, and every struct mirror has the size the library reports."""
+    belongs to two headers, the library exports every name, every struct mirror has the size the library reports, and every
+    entry's declared return type is the one the binding gives it."""
     from lm_net_amd import hip
     lib = hip.load()
     inc = os.path.join(ROOT, "include")
-    assert sorted(fn for fn in os.listdir(inc) if fn.endswith(".h")) == sorted(hip.HEADERS)
+    found = [fn for fn in os.listdir(inc) if fn.endswith(".h")]
+    found += [d + "/" + fn for d in os.listdir(inc) if os.path.isdir(os.path.join(inc, d)) for fn in os.listdir(os.path.join(inc, d)) if fn.endswith(".h")]
+    assert sorted(found) == sorted(hip.HEADERS) and len(found) == 16
     text = {fn: open(os.path.join(inc, fn)).read() for fn in hip.HEADERS}
+    returns = {}
     for fn, names in hip.HEADERS.items():
         declared = set(re.findall(r"\b(lmn_[a-z0-9_]+)\s*\(", text[fn])) - {"lmn_src_t", "lmn_stream_t"}
-        assert declared == set(names) and len(set(names)) == len(names), (fn, declared ^ set(names))
+        protos = PROTOTYPE.findall(text[fn])                         # (the stricter reading: a prototype at the start of a line)
+        assert declared == {name for _, name in protos} == set(names) and len(protos) == len(names), (fn, declared ^ set(names))
         assert all(hasattr(lib, name) for name in names), fn
+        returns.update({name: ret for ret, name in protos})
     lists = list(hip.HEADERS.values())
     assert all(not set(a) & set(b) for i, a in enumerate(lists) for b in lists[i + 1:])      # pairwise disjoint
-    assert hip.EXPORTS == [name for names in lists for name in names]
+    assert hip.EXPORTS == [name for names in lists for name in names] and len(hip.EXPORTS) == 139
+    # return types: ctypes assumes int, so a 64-bit size whose entry is missing from the table would be cut above 2 GiB
+    int64 = {name for name, ret in returns.items() if ret == "int64_t"}
+    assert set(hip.RETURNS_INT64) == int64 and len(hip.RETURNS_INT64) == 20, sorted(set(hip.RETURNS_INT64) ^ int64)
+    assert hip.RETURNS_OTHER == {"lmn_last_error": ctypes.c_char_p, "lmn_plan_create": ctypes.c_void_p}
+    assert {name: ret for name, ret in returns.items() if ret not in ("int", "int64_t")} == {"lmn_last_error": "const char*", "lmn_plan_create": "lmn_plan_t"}
+    for name, ret in returns.items():
+        want = ctypes.c_int64 if ret == "int64_t" else hip.RETURNS_OTHER.get(name, ctypes.c_int)
+        assert getattr(lib, name).restype is want, (name, ret, getattr(lib, name).restype)
     typedefs = {fn: re.findall(r"^\}\s*(lmn_\w+_t)\s*;", text[fn], re.M) for fn in text}
     names = [td for tds in typedefs.values() for td in tds]
-    assert all(typedefs.values()) and len(set(names)) == len(names)          # every header defines a struct, none is defined twice
+    assert len(set(names)) == len(names)                                     # no struct is defined twice
+    for fn, tds in typedefs.items():                                         # a header defines a struct iff it reports a size
+        assert bool(tds) == any(name.startswith("lmn_sizeof_") for name in hip.HEADERS[fn]), fn
     # A struct is named only by the header that defines it -- or by one that includes that header, since an entry of a feature header
     # may take a struct of lmnet_hip.h (lmn_augment_oneof_u8 takes lmn_aug_param_t).  No header includes a feature header, so ...
+    includes = {g: {os.path.normpath(os.path.join(os.path.dirname(g), i)) for i in re.findall(r'#include "([^"]+)"', text[g])} for g in text}
     for fn, tds in typedefs.items():
-        sees = [fn] + [g for g in text if '#include "%s"' % fn in text[g]]
+        sees = [fn] + [g for g in text if fn in includes[g]]
         for td in tds:
             named_by = [g for g in text if re.search(r"\b%s\b" % td, text[g])]
             assert set(named_by) <= set(sees), (td, fn, named_by)
@@ -41,10 +61,27 @@ def test_library_exports_every_declared_symbol():
     for fn, td in (("lmnet_oneof.h", "lmn_oneof_param_t"), ("lmnet_loss.h", "lmn_loss_param_t"), ("lmnet_sigmoid.h", "lmn_sig_param_t")):
         assert typedefs[fn] == [td] and [g for g in text if td in text[g]] == [fn], td
     assert lib.lmn_abi_version() == hip.ABI_VERSION == 15
-    assert len(hip.STRUCTS) == 10 and len({sizeof for _, sizeof in hip.STRUCTS}) == 10
-    assert {sizeof for _, sizeof in hip.STRUCTS} == {name for name in hip.EXPORTS if name.startswith("lmn_sizeof_")}
+    sizeofs = {name for name in hip.EXPORTS if name.startswith("lmn_sizeof_")}
+    assert {sizeof for _, sizeof in hip.STRUCTS} == sizeofs, sorted({sizeof for _, sizeof in hip.STRUCTS} ^ sizeofs)
+    assert len(hip.STRUCTS) == 12 and len(sizeofs) == 12
     for struct, sizeof in hip.STRUCTS:
         assert getattr(lib, sizeof)() == ctypes.sizeof(struct), (struct.__name__, sizeof)
+
+
+@pytest.mark.parametrize("header,prefixes", [
+    ("curves/lmnet_curves.h", ("CURVE_",)), ("volume/lmnet_volume.h", ("VOLUME_",)), ("volpost/lmnet_volpost.h", ("VOLPOST_",)),
+    ("lesion/lmnet_lesion.h", ("LESION_",)), ("distmap/lmnet_distmap.h", ("DISTMAP_",)), ("lovasz/lmnet_lovasz.h", ("LOVASZ_",)),
+    ("region/lmnet_region.h", ("REGION_",)), ("slices/lmnet_slices.h", ("SLICES_",)), ("soft/lmnet_soft.h", ("SOFT_", "MIX_")),
+    ("hard/lmnet_hard.h", ("HARD_",))], ids=lambda v: v if isinstance(v, str) else None)
+def test_integer_defines_equal_the_mirrored_constants(header, prefixes):
+    """Every `#define LMN_<NAME> <integer>` of the header equals hip.<NAME>, and hip has no name of the header's prefix beyond them.
+    (tiles mirrors its defines as dicts and optim has a derived one: tests/test_tiles_cpu.py, tests/test_optim_cpu.py.)"""
+    from lm_net_amd import hip
+    assert header in hip.HEADERS
+    text = open(os.path.join(ROOT, "include", header)).read()
+    defs = {k: int(v.strip("()")) for k, v in re.findall(r"^#define (LMN_(?:%s)\w+) (\(?-?\d+\)?)" % "|".join(prefixes), text, re.M)}
+    mine = {"LMN_" + k: v for k, v in vars(hip).items() if k.startswith(prefixes)}
+    assert defs and defs == mine, sorted(set(defs.items()) ^ set(mine.items()))
 
 
 def test_pack_size_arithmetic():

@@ -16,16 +16,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # ---------------------------------------------------------------- ABI
 def test_registry_header_and_struct_agree():
-    """hip.SYMBOLS_OPTIM against include/optim/lmnet_optim.h, as tests/test_host_cpu.py checks hip.HEADERS against include/*.h: the
-    header declares exactly the list, the library exports every name, no name belongs to hip.EXPORTS as well, and the struct mirror
-    has the size the library reports."""
+    """The feature's own part of the registry: the literal list, its place in hip.HEADERS, the one struct with its size and field
+    offsets, the #defines (one of them derived) and the workspace arithmetic.  (Header / export / layout / return-type checks:
+    tests/test_host_cpu.py.)"""
     from lm_net_amd import hip
     lib = hip.load()
     assert hip.SYMBOLS_OPTIM == ["lmn_sizeof_optim_param", "lmn_optim_workspace", "lmn_optim_prepare", "lmn_adamw_step_ex"]
+    assert hip.HEADERS["optim/lmnet_optim.h"] is hip.SYMBOLS_OPTIM and (hip.OptimParam, "lmn_sizeof_optim_param") in hip.STRUCTS
     header = open(os.path.join(ROOT, "include", "optim", "lmnet_optim.h")).read()
-    declared = set(re.findall(r"\b(lmn_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(hip.SYMBOLS_OPTIM) and all(hasattr(lib, name) for name in hip.SYMBOLS_OPTIM), declared ^ set(hip.SYMBOLS_OPTIM)
-    assert not set(hip.SYMBOLS_OPTIM) & set(hip.EXPORTS) and hip.ABI_VERSION == 15
     assert re.findall(r"^\}\s*(lmn_\w+_t)\s*;", header, re.M) == ["lmn_optim_param_t"]
     defs = {k: int(v) for k, v in re.findall(r"^#define (LMN_OPTIM_\w+) (\d+)\b", header, re.M)}
     assert lib.lmn_sizeof_optim_param() == ctypes.sizeof(hip.OptimParam) == defs["LMN_OPTIM_PARAM_BYTES"] == hip.OPTIM_PARAM_BYTES == 64
@@ -41,27 +39,6 @@ def test_registry_header_and_struct_agree():
         assert hip.optim_blocks(n) == blocks, n
         assert int(lib.lmn_optim_workspace(ctypes.c_int64(n))) == hip.optim_workspace_words(n) == 2 * blocks + 16 + 64, n
     assert int(lib.lmn_optim_workspace(ctypes.c_int64(0))) == hip.optim_workspace_words(0) == 0
-
-
-def test_every_entry_that_writes_device_memory_has_its_guard_test():
-    """The rule of the guard manifest (tests/guard.py, tests/test_guard_cpu.py) for hip.SYMBOLS_OPTIM: an entry is either host
-    arithmetic (the exemption pattern of test_guard_cpu.py) or is issued, through its `hip.` wrapper, inside the named test of
-    tests/test_guard_optim_gpu.py, which asserts the launch log; the wrapper's source really issues that C entry."""
-    from lm_net_amd import hip
-    from test_guard_cpu import EXEMPT_OK, _code
-    covered = {"lmn_optim_prepare": "optim_prepare", "lmn_adamw_step_ex": "adamw_step_ex"}
-    exempt = {"lmn_sizeof_optim_param", "lmn_optim_workspace"}
-    assert set(covered) | exempt == set(hip.SYMBOLS_OPTIM) and not set(covered) & exempt
-    assert all(EXEMPT_OK.match(k) for k in exempt) and not any(EXEMPT_OK.match(k) for k in covered)
-    src = _code(open(os.path.join(ROOT, "tests", "test_guard_optim_gpu.py")).read())
-    fn = re.search(r"^def test_prepare_and_step_entries\(.*?(?=^def |^class |^@|\Z)", src, re.M | re.S).group(0)
-    hip_src = open(os.path.join(ROOT, "lm_net_amd", "hip.py")).read()
-    for entry, wrapper in covered.items():
-        assert re.search(r"\bhip\.%s\(" % wrapper, fn), wrapper
-        assert any('"%s"' % wrapper in m for m in re.findall(r"\.names == \[([^\]]*)\]", fn)), wrapper
-        body = re.search(r"^def %s\(.*?(?=^def |^class |\Z)" % wrapper, hip_src, re.M | re.S).group(0)
-        assert re.search(r"\b%s\b" % entry, body), (entry, wrapper)
-    assert "GuardPool" in fn and "assert_clean" in fn and "hip.optim_workspace(n)" in fn     # exact-size buffers, carved workspace
 
 
 def test_optim_param_flags():

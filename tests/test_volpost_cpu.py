@@ -1,5 +1,5 @@
 """CPU: the host side of the 3D cleaning (include/volpost/lmnet_volpost.h, lm_net_amd.post.VolumePostprocess): registry and header
-agree, the guard rule for the three entries, the argument checks of the C entries (rejected before any HIP call, with fake device
+agree, the argument checks of the C entries (rejected before any HIP call, with fake device
 pointers), the workspace formula, the class's ValueErrors, the restatement tests/volpost_ref.py against scipy.ndimage (label with the
 three structures, binary_fill_holes with the dual structure), and the conditions the GPU tests rest on, decided by the restatement
 alone.  No GPU needed."""
@@ -18,55 +18,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # ---------------------------------------------------------------- ABI
 def test_registry_and_header_agree():
-    """hip.SYMBOLS_VOLPOST against include/volpost/lmnet_volpost.h: the header declares exactly the list and no struct, the library
-    exports the names, no name belongs to another list, and the #defines equal the hip.VOLPOST_* constants."""
+    """The feature's own part of the registry: the literal list, its place in hip.HEADERS, the number and values of its #defines, the
+    header's citations and the package's export.  (Header / export / layout / return-type / constants checks: tests/test_host_cpu.py.)"""
     from lm_net_amd import hip
-    lib = hip.load()
     assert hip.SYMBOLS_VOLPOST == ["lmn_volpost_workspace", "lmn_cc3d_label", "lmn_volpost_clean"]
+    assert hip.HEADERS["volpost/lmnet_volpost.h"] is hip.SYMBOLS_VOLPOST
     header = open(os.path.join(ROOT, "include", "volpost", "lmnet_volpost.h")).read()
-    declared = set(re.findall(r"\b(lmn_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(hip.SYMBOLS_VOLPOST) and all(hasattr(lib, name) for name in hip.SYMBOLS_VOLPOST), declared ^ set(hip.SYMBOLS_VOLPOST)
-    for other in (hip.EXPORTS, hip.SYMBOLS_OPTIM, hip.SYMBOLS_TILES, hip.SYMBOLS_CURVES, hip.SYMBOLS_VOLUME):
-        assert not set(hip.SYMBOLS_VOLPOST) & set(other)
-    assert hip.ABI_VERSION == 15 and len(hip.STRUCTS) == 10
-    assert re.findall(r"^\}\s*(lmn_\w+_t)\s*;", header, re.M) == []
-    defs = {k: int(v) for k, v in re.findall(r"^#define (LMN_VOLPOST_\w+) (\d+)\b", header, re.M)}
-    mine = {"LMN_" + k: v for k, v in vars(hip).items() if k.startswith("VOLPOST_")}
-    assert defs == mine and len(defs) == 3, (defs, mine)
+    assert len(re.findall(r"^#define LMN_VOLPOST_\w+ \d+\b", header, re.M)) == 3
     assert (hip.VOLPOST_MAX_SIDE, hip.VOLPOST_MAX_KEEP, hip.VOLPOST_NSTAT) == (1024, 4, 4)
-    assert len([k for k in vars(hip) if k.startswith("VOLUME_")]) == 3        # (tests/test_volume_cpu.py requires exactly its three)
     for cite in ("generate_binary_structure(3,", "binary_fill_holes", "DUAL connectivity", "smallest linear", "x - 1"):
         assert cite in header, cite
-    # the header sits in a subdirectory: the top-level headers are still exactly hip.HEADERS
-    assert sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")) == sorted(hip.HEADERS)
     import lm_net_amd
     from lm_net_amd.post import VolumeOutput, VolumePostprocess
     assert lm_net_amd.VolumePostprocess is VolumePostprocess and "VolumePostprocess" in lm_net_amd.__all__
     assert VolumeOutput._fields == ("labels", "stats")
     assert "one-slice volume has no holes" in VolumePostprocess.__doc__
-
-
-def test_every_entry_that_writes_device_memory_has_its_guard_test():
-    """The rule of the guard manifest (tests/guard.py, tests/test_guard_cpu.py) for hip.SYMBOLS_VOLPOST: lmn_volpost_workspace is host
-    arithmetic (the exemption pattern of test_guard_cpu.py); lmn_cc3d_label and lmn_volpost_clean are issued, through their hip.
-    wrappers, inside the named tests of tests/test_guard_volpost_gpu.py, which assert the launch log; the wrappers' sources really
-    issue those C entries."""
-    from lm_net_amd import hip
-    from test_guard_cpu import EXEMPT_OK, _code
-    covered = {"lmn_cc3d_label": ("test_cc3d_label_entry", "cc3d_label"), "lmn_volpost_clean": ("test_volpost_clean_entry", "volpost_clean")}
-    exempt = {"lmn_volpost_workspace"}
-    assert set(covered) | exempt == set(hip.SYMBOLS_VOLPOST) and not set(covered) & exempt
-    assert all(EXEMPT_OK.match(k) for k in exempt) and not any(EXEMPT_OK.match(k) for k in covered)
-    src = _code(open(os.path.join(ROOT, "tests", "test_guard_volpost_gpu.py")).read())
-    hip_src = open(os.path.join(ROOT, "lm_net_amd", "hip.py")).read()
-    for entry, (test, wrapper) in covered.items():
-        fn = re.search(r"^def %s\(.*?(?=^def |^class |^@|\Z)" % test, src, re.M | re.S).group(0)
-        assert re.search(r"\bhip\.%s\(" % wrapper, fn), wrapper
-        assert any('"%s"' % wrapper in m for m in re.findall(r"\.names == \[([^\]]*)\]", fn)), wrapper
-        body = re.search(r"^def %s\(.*?(?=^def |^class |\Z)" % wrapper, hip_src, re.M | re.S).group(0)
-        assert re.search(r"\b%s\b" % entry, body), (entry, wrapper)
-        assert "_pools(" in fn and "assert_clean" in fn and "assert_inputs_unchanged" in fn, test
-    assert "GuardPool(DEV, GuardPool.size_for(" in re.search(r"^def _pools\(.*?(?=^def |^class |^@|\Z)", src, re.M | re.S).group(0)
 
 
 # ---------------------------------------------------------------- argument checks
