@@ -26,7 +26,9 @@ struct WgradParams {
   int TH, TW, XH, XW, CSx, CSy, tiles_x, tiles_y, total_tiles;
   uint32_t mXW, mTW;  // magic multipliers: n / d == (n * m) >> 32 for n, d < 2^16
   int dbg;
+  int fill;  // wgrad3_kernel, 2 x 2-tile blocks: the waves of tile slots past the channel count take taps of the valid tiles (LMN_WGRAD_FILL)
 };
+template <int V> struct WgIC { static constexpr int value = V; };
 
 // first element (tap 0) of dW[co][ch of source sidx]: the source's own gradient tensor if the caller gave one,
 // else its column range of the concatenated dW
@@ -365,7 +367,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_lds_kernel(const WgradParams P) 
 // window 34 wide, one-tile or 2 x 2-tile blocks).  Against the general kernel:
 //  * 2 x 2-tile blocks give each wave ONE output tile (wave w: cout tile w / 2, cin tile w % 2) with all 9 taps over ALL K steps
 //    of the tile, instead of all four tiles over every fourth step: 36 accumulator VGPRs instead of 144 (room for a third
-//    resident block per CU and the prefetch registers below) and no cross-wave reduction at the end;
+//    resident block per CU and the prefetch registers below) and no cross-wave reduction at the end.  A set that reaches past the
+//    channel count (3, 5, 9 tiles on a side) has 1 or 2 valid tiles: the waves of its empty slots take some of the nine taps of a
+//    valid tile (the wave mapping table in the kernel) -- still nothing to reduce, and every sum keeps its K order;
 //  * the global loads of tile i+1 are issued BEFORE the K loop of tile i and committed to LDS after it, so a tile's memory
 //    latency hides behind this block's own MFMAs, not only behind those of the CU's other blocks;
 //  * index math is hoisted out of the per-tile / per-step paths (it ran at ~35 VALU per K step and ~25 per staged item, which
@@ -419,9 +423,25 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradParams P) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q = lane >> 4, n = lane & 15;
-  const int m_w = TS ? wv / NNT : 0, t_w = TS ? wv % NNT : 0;
   const int mset = blockIdx.y / P.nsets_n, nset = blockIdx.y - mset * P.nsets_n;
   const int mt0 = mset * NMT, nt0 = nset * NNT;
+  // Wave mapping of a 2 x 2-tile block (block-uniform inputs, scalar per wave).  vr2 / vc2: the second cout / cin tile of the set holds
+  // channels.  A slot past the channel count gets no wave; its wave takes some of the nine TAPS of a valid tile instead, over every K
+  // step and in the K order of a wave that owns a tile alone -- so every sum keeps the bits of the one-wave-per-slot mapping and the
+  // waves of a tile have nothing to add up:
+  //   both       wave w: tile (w / 2, w % 2), taps 0..8
+  //   vr2 only   waves 2m, 2m + 1: tile (m, 0), taps 0..4 / 5..8
+  //   vc2 only   waves t, t + 2: tile (0, t), taps 0..4 / 5..8
+  //   neither    waves 0, 1, 2: tile (0, 0), tap row w (taps 3w..3w + 2); wave 3 has no taps (three rows: 3 of 9 taps is the longest share
+  //              either way, and a row keeps the tap offsets immediates of one lane address)
+  // The bias gradient is summed by every wave (one add per K step) and stored by rank 0 of the tiles with t_w == 0.
+  const bool vr2 = TS && (!P.fill || mt0 + 1 < P.NMTT), vc2 = TS && (!P.fill || nt0 + 1 < P.NNTT);
+  const int m_w = vr2 ? wv >> 1 : 0, t_w = vc2 ? wv & 1 : 0;
+  const int nshare = TS ? (vr2 ? 1 : 2) * (vc2 ? 1 : 2) : 1;                              // waves of this wave's tile
+  const int rank = TS ? (vc2 ? 0 : wv & 1) + (vr2 ? 0 : wv >> 1) * (vc2 ? 1 : 2) : 0;     // this wave among them
+  const int TP0 = nshare == 2 ? rank * 5 : (nshare == 4 ? rank * 3 : 0);                  // first tap and number of taps of this wave
+  const int TPN = nshare == 2 ? 5 - rank : (nshare == 4 ? (rank < 3 ? 3 : 0) : 9);
+  const int trow = nshare == 4 && rank < 3 ? rank : 0;                                    // tap row folded into the wave's window address
   const int NP = P.TH * 32;
   const int j = tid & 3, pl = tid >> 2;  // this thread's channel quad and pixel-in-round of every staged item
 
@@ -538,9 +558,11 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradParams P) {
     if constexpr (UP) {
       // the quarter-size source window -> S2 (fp32), barrier, then the window items by interpolation
 #pragma unroll
-      for (int t = 0; t < NNT; ++t)
+      for (int t = 0; t < NNT; ++t) {
+        if (t > 0 && !vc2) continue;   // (no wave reads the planes of a slot past the channel count)
 #pragma unroll
         for (int u = 0; u < USX; ++u) *reinterpret_cast<f32x4*>(&S2[((t * SPA) + u * 64 + pl) * 16 + j * 4]) = raw_f32(vs[u][t]);
+      }
       __syncthreads();
       const int iy0 = oy0 - 1, ix0 = ox0 - 1;
       int ys0, xs0;
@@ -557,6 +579,7 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradParams P) {
         const int l00 = inb ? (y0 - ys0) * SCW + (x0 - xs0) : 0;
 #pragma unroll
         for (int t = 0; t < NNT; ++t) {
+          if (t > 0 && !vc2) continue;
           const float* sp = &S2[(t * SPA + l00) * 16 + j * 4];
           const f32x4 v00 = *reinterpret_cast<const f32x4*>(sp), v01 = *reinterpret_cast<const f32x4*>(sp + xp * 16);
           const f32x4 v10 = *reinterpret_cast<const f32x4*>(sp + yp * SCW * 16), v11 = *reinterpret_cast<const f32x4*>(sp + (yp * SCW + xp) * 16);
@@ -570,6 +593,7 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradParams P) {
     } else {
 #pragma unroll
     for (int t = 0; t < NNT; ++t) {
+      if (t > 0 && !vc2) continue;
       const bool tf = tflags[t] != 0 || tscale[t] != nullptr;  // block-uniform
 #pragma unroll
       for (int u = 0; u < UX; ++u) {
@@ -600,6 +624,7 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradParams P) {
     }   // (!UP)
 #pragma unroll
     for (int m = 0; m < NMT; ++m) {
+      if (m > 0 && !vr2) continue;
 #pragma unroll
       for (int u = 0; u < UY; ++u) {
         float* dst = yl + (m * NPA + u * 64) * CS;
@@ -645,11 +670,16 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradParams P) {
 #ifdef LMN_WG_TIMING
     tk_b = LMN_TCLK(); tk_s3 += tk_b - tk_a;
 #endif
+    // The wave's taps TPF .. TPF + NTP - 1 (of tap row trow on: 0 except in the row split) into accumulators 0 .. NTP - 1: (0, 9) for a
+    // wave that owns its tile.  Every body is branch-free with immediate tap offsets, and the K order is the same in all of them.
+    auto kloop = [&](auto tpfc, auto ntpc) __attribute__((always_inline)) {
+    constexpr int TPF = decltype(tpfc)::value, NTP = decltype(ntpc)::value;
+    auto tapoff = [&](int i) __attribute__((always_inline)) { return ((TPF + i) / 3) * XWC + (TPF + i) % 3; };
     if constexpr (BF) {
       // K steps of 16 consecutive tile pixels; lane (q, n) owns pixels 4q..4q+3 of the step, channel n
-      const uint16_t* xw = reinterpret_cast<const uint16_t*>(XS) + (t_w * XPA + q * 4) * (CS * 2) + n;
+      const uint16_t* xw = reinterpret_cast<const uint16_t*>(XS) + (t_w * XPA + trow * XWC + q * 4) * (CS * 2) + n;
       const uint16_t* yw = reinterpret_cast<const uint16_t*>(YS) + (m_w * NPA + q * 4) * (CS * 2) + n;
-      auto kfrag = [&](int ks, uint2& av, uint2 (&bv)[9]) __attribute__((always_inline)) {   // operands of the 16-pixel K step ks
+      auto kfrag = [&](int ks, uint2& av, uint2 (&bv)[NTP]) __attribute__((always_inline)) {   // operands of the 16-pixel K step ks
         const int pix0 = ks * 16, pr = pix0 >> 5, pc0 = pix0 & 31;
         const uint16_t* xp = xw + (pr * XWC + pc0) * (CS * 2);
         const uint16_t* yp = yw + pix0 * (CS * 2);
@@ -661,8 +691,8 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradParams P) {
         }
         av = uint2{h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp) {
-          const uint16_t* xt = xp + ((tp / 3) * XWC + tp % 3) * (CS * 2);
+        for (int tp = 0; tp < NTP; ++tp) {
+          const uint16_t* xt = xp + tapoff(tp) * (CS * 2);
           const uint32_t h0 = xt[0], h1 = xt[CS * 2], h2 = xt[2 * CS * 2], h3 = xt[3 * CS * 2];
           bv[tp] = uint2{h0 | (h1 << 16), h2 | (h3 << 16)};
         }
@@ -670,32 +700,44 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradParams P) {
       // two 16-pixel K steps per v_mfma_f32_16x16x32_bf16 (mfma_bf16x2: K = 32 pixels); an odd last step in the 16x16x16 form
       int ks = K0;
       for (; (ks + KSTEP) * 16 < NP; ks += 2 * KSTEP) {
-        uint2 av0, av1, bv0[9], bv1[9];
+        uint2 av0, av1, bv0[NTP], bv1[NTP];
         kfrag(ks, av0, bv0);
         kfrag(ks + KSTEP, av1, bv1);
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp) acc[tp] = mfma_bf16x2(av0, av1, bv0[tp], bv1[tp], acc[tp]);
+        for (int tp = 0; tp < NTP; ++tp)
+          acc[tp] = mfma_bf16x2(av0, av1, bv0[tp], bv1[tp], acc[tp]);
       }
       if (ks * 16 < NP) {
-        uint2 av, bv[9];
+        uint2 av, bv[NTP];
         kfrag(ks, av, bv);
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp) acc[tp] = mfma_bf16(av, bv[tp], acc[tp]);
+        for (int tp = 0; tp < NTP; ++tp)
+          acc[tp] = mfma_bf16(av, bv[tp], acc[tp]);
       }
     } else {
-      const float* xw = XS + (t_w * XPA + q) * CS + n;
+      const float* xw = XS + (t_w * XPA + trow * XWC + q) * CS + n;
       const float* yw = YS + (m_w * NPA + q) * CS + n;
       for (int ks = K0; ks * 4 < NP; ks += KSTEP) {
         const int pix0 = ks * 4, pr = pix0 >> 5, pc0 = pix0 & 31;
         const float* xp = xw + (pr * XWC + pc0) * CS;
         const float av = yw[pix0 * CS];
-        float bv[9];
+        float bv[NTP];
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp) bv[tp] = xp[((tp / 3) * XWC + tp % 3) * CS];
+        for (int tp = 0; tp < NTP; ++tp) bv[tp] = xp[tapoff(tp) * CS];
         bsum += av;
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp) acc[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[tp], acc[tp], 0, 0, 0);
+        for (int tp = 0; tp < NTP; ++tp)
+          acc[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[tp], acc[tp], 0, 0, 0);
       }
+    }
+    };
+    if constexpr (TS) {
+      if (nshare == 1) kloop(WgIC<0>(), WgIC<9>());   // (scalar tests, once per tile)
+      else if (nshare == 2 && rank == 0) kloop(WgIC<0>(), WgIC<5>());
+      else if (nshare == 2) kloop(WgIC<5>(), WgIC<4>());
+      else if (rank < 3) kloop(WgIC<0>(), WgIC<3>());
+    } else {
+      kloop(WgIC<0>(), WgIC<9>());
     }
   }
 #ifdef LMN_WG_TIMING
@@ -716,25 +758,30 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradParams P) {
   constexpr int NT = 9 * NMT * NNT;
   float* pdst = P.partial ? P.partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (NT * 256 + NMT * 16) : nullptr;
   if constexpr (TS) {
-    // every wave holds the finished sums of ITS tile: straight to the block partial (the layout of the LDS-reduced form:
-    // [tap][m][t][r][lane], then the bias sums) or to dW
+    // every wave holds the finished sums of ITS taps of its tile (accumulator i = tap TP0 + i): straight to the block partial (the
+    // layout of the LDS-reduced form: [tap][m][t][r][lane], then the bias sums) or to dW.  Slots without a wave are not written: the
+    // reduction never reads them into dW.
     const int nt = nt0 + t_w;
     int sidx = 0;
     while (sidx + 1 < A.nsrc && nt >= P.ntile_off[sidx + 1]) ++sidx;
     const int ch = (nt - P.ntile_off[sidx]) * 16 + n;
 #pragma unroll
-    for (int tp = 0; tp < 9; ++tp)
+    for (int i = 0; i < 9; ++i) {
+      const int tp = TP0 + i;
+      if (i < TPN) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (pdst) {
-          pdst[(((tp * NMT + m_w) * NNT + t_w) * 4 + r) * 64 + lane] = acc[tp][r];
-        } else {
-          const int co = (mt0 + m_w) * 16 + q * 4 + r;
-          if ((mt0 + m_w) < P.NMTT && co < A.Cout && nt < P.NNTT && ch < A.src[sidx].C)
-            atomicAdd(wgrad_dst(P, co, sidx, ch, 9) + tp, acc[tp][r]);
+        for (int r = 0; r < 4; ++r) {
+          if (pdst) {
+            pdst[(((tp * NMT + m_w) * NNT + t_w) * 4 + r) * 64 + lane] = acc[i][r];
+          } else {
+            const int co = (mt0 + m_w) * 16 + q * 4 + r;
+            if ((mt0 + m_w) < P.NMTT && co < A.Cout && nt < P.NNTT && ch < A.src[sidx].C)
+              atomicAdd(wgrad_dst(P, co, sidx, ch, 9) + tp, acc[i][r]);
+          }
         }
       }
-    if (t_w == 0) {
+    }
+    if (t_w == 0 && rank == 0) {
       float v = bsum;
       v += __shfl_xor(v, 16, 64);
       v += __shfl_xor(v, 32, 64);
@@ -1416,6 +1463,13 @@ static int wgrad_v1_env() {
   if (v < 0) { const char* e = getenv("LMN_WGRAD_V1"); v = e ? atoi(e) : 1; }
   return v;
 }
+// LMN_WGRAD_FILL=0: the 2 x 2-tile blocks of wgrad3_kernel keep one wave on every tile slot, those past the channel count included
+// (A/B runs; WgradParams.fill).  Both mappings give the same bits.
+static int wgrad_fill_env() {
+  static int v = -1;
+  if (v < 0) { const char* e = getenv("LMN_WGRAD_FILL"); v = e ? (atoi(e) != 0) : 1; }
+  return v;
+}
 static bool wgrad_v1(const lmn_wgrad_args_t& a) { return a.ksize == 3 && a.stride == 1 && wgrad_v1_env() != 0; }
 static int wgrad_blocks_total(const lmn_wgrad_args_t& a) {
   static int c = -1;
@@ -1558,6 +1612,7 @@ static int wgrad_setup(const lmn_wgrad_args_t& A, WgradParams& P, WgGeom& G) {
   P.tiles_y = (Gm.Hout + P.TH - 1) / P.TH;
   P.total_tiles = A.B * P.tiles_x * P.tiles_y;
   P.dbg = 0;
+  P.fill = wgrad_fill_env();
   LMN_REQUIRE(P.XH * P.XW < 65536 && P.TH * P.TW < 65536, "conv_wgrad: tile too large");
   P.mXW = (uint32_t)((1ull << 32) / (uint32_t)P.XW + 1);
   P.mTW = (uint32_t)((1ull << 32) / (uint32_t)P.TW + 1);
